@@ -37,9 +37,14 @@ Tap point: (A) kernel boundary.
 `python bench.py --gpus N` (N > 1, no torchrun) launches the N ranks itself;
 under torchrun (WORLD_SIZE set) it is one rank of the job.
 
-After the timed region the very entry points that were timed are run once
-more from known generator states and compared with the oracle
-(config.verified); a mismatch fails the benchmark.
+A plain run sets up, warms up, times --steps steps and prints the line.
+`--dump-outputs DIR` then writes what the last timed step computed (rank 0's
+shard) as DIR/<name>.npy.  Everything else sits behind `--full`: the CPU
+baseline, per-kernel times and rooflines, the queue-nlive and Philox legs, the
+runs-per-GPU sweep, the RCCL record gather, the end-to-end legs, and the oracle
+check -- the very entry points that were timed run once more from known
+generator states and are compared with the oracle (config.verified); a
+mismatch fails the benchmark.
 """
 import argparse
 import json
@@ -60,6 +65,8 @@ FP64_PEAK_TFLOPS = 78.6  # vector fp64 (datasheet)
 MAX_ELLS = 8
 GATE_QUEUE = 512  # walkers in flight per run for which ln Z passes the gate against the reference (K = nlive does not)
 RWALK_SCALE = 0.27  # acceptance ~0.5 on the contour shells: the reference's tuned state (facc = 0.5)
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: all files together (21 MB at the default shard)
+DUMP_SEED = 7  # the fixed sample of runs kept when a larger shard exceeds it
 # the REAL dynesty 3.0.0 on C2, one core of the build container (it cannot
 # travel to the GPU box: /root/reference does not exist there)
 REFERENCE_C2_PROPOSALS_PER_S_1CORE = 44.0e3
@@ -226,6 +233,30 @@ class Shard:
                     logl=c.from_device(self.d_logl, (k,), np.float64),
                     accept=c.from_device(self.d_na, (k,), np.int32),
                     reject=c.from_device(self.d_nr, (k,), np.int32))
+
+    def fetch_outputs(self, max_bytes=DUMP_MAX_BYTES, seed=DUMP_SEED):
+        """What the last queue fill of a step hands its caller (the rebuilt, enlarged MultiEllipsoid records of every
+        run and the walkers of the fill, per run), as float64 arrays.  Ellipsoid slots past a run's nells are zeroed
+        (never written by the rebuild).  Above `max_bytes` a fixed, seeded sample of runs is kept (`runs_sampled`)."""
+        c, r, me, d, kq = self.ctx, self.runs, self.me, self.d, self.kq
+        n = r * kq
+        out = self.fetch_bound()
+        out.update(u=c.from_device(self.d_u, (r, kq, d), np.float64),
+                   v=c.from_device(self.d_v, (r, kq, d), np.float64),
+                   logl=c.from_device(self.d_logl, (r, kq), np.float64),
+                   accept=c.from_device(self.d_na, (n,), np.int32).reshape(r, kq),
+                   reject=c.from_device(self.d_nr, (n,), np.int32).reshape(r, kq))
+        unused = np.arange(me)[None, :] >= out["nells"][:, None]
+        for key in ("ctrs", "covs", "ams", "axes", "axlens", "logvols"):
+            out[key][unused] = 0.0
+        out = {key: a.astype(np.float64) for key, a in out.items()}
+        total = sum(a.nbytes for a in out.values())
+        if total > max_bytes:
+            keep = max(1, r * max_bytes // total - 1)
+            sel = np.sort(np.random.default_rng(seed).choice(r, keep, replace=False))
+            out = {key: a[sel] for key, a in out.items()}
+            out["runs_sampled"] = sel.astype(np.float64)
+        return out
 
     def reset_rng(self):
         c = self.ctx
@@ -408,6 +439,12 @@ def main():
     ap.add_argument("--walks", type=int, default=45)
     ap.add_argument("--queue", type=int, default=GATE_QUEUE,
                     help="walkers in flight per run (the queue size of the evidence gate)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures or checks: CPU baseline, "
+                         "per-kernel times and rooflines, queue-nlive / Philox legs, runs sweep, oracle check, RCCL "
+                         "record gather, end-to-end legs (the --no-* options and --lean trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0's shard) as DIR/<name>.npy, float64")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--preroll", type=int, default=80,
                     help="untimed steps before the warm-up (GPU clock ramp)")
@@ -419,10 +456,13 @@ def main():
     ap.add_argument("--no-verify", action="store_true",
                     help="skip the oracle check of the timed entry points (diagnostic)")
     ap.add_argument("--lean", action="store_true",
-                    help="profiling runs: only the timed launch shape (no CPU / end-to-end / oracle-check / "
-                         "queue-nlive / Philox legs), so that per-kernel averages are those of the headline step")
+                    help="with --full, for profiling runs: only the timed launch shape (no CPU / end-to-end / "
+                         "oracle-check / queue-nlive / Philox legs), so that per-kernel averages are those of the "
+                         "headline step")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.lean:
         args.no_cpu = args.no_e2e = args.no_verify = True
 
@@ -446,7 +486,7 @@ def main():
     # CPU baseline first, while this process holds no HIP / torch state: the all-cores leg forks
     # its workers (256 spawned interpreters took 30 s to start on the GPU box's host)
     cpu = None
-    if not args.no_cpu and world == 1 and rank == 0:
+    if args.full and not args.no_cpu and world == 1 and rank == 0:
         u0c, loglstar_c = make_shard(prob, args.runs, args.nlive, 1000 + rank)
         cpu = cpu_baseline(prob, u0c, args.nlive, RWALK_SCALE, loglstar_c, args.walks, args.cpu_seconds)
         del u0c
@@ -474,7 +514,7 @@ def main():
     d = prob.ndim
     runs, nlive = args.runs, args.nlive
     sh = Shard(ctx, prob, runs, nlive, args.walks, seed=1000 + rank, entropy=(21, rank, 0, 0), queue=args.queue)
-    k, kq, nq = sh.k, sh.kq, sh.nq
+    kq, nq = sh.kq, sh.nq
 
     ev = [ctx.event() for _ in range(4)]
 
@@ -506,10 +546,67 @@ def main():
     t = torch.tensor([wall], dtype=torch.float64, device="cuda")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall = float(t.item())
+    props_per_launch = runs * kq * args.walks
+    props_per_step_rank = props_per_launch * nq
+    value = world * props_per_step_rank * args.steps / wall
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in sh.fetch_outputs().items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    if args.full:
+        extra = full_legs(args, ctx, sh, prob, torch, dist, dev, rank, world, ev, nrep=5)
+    if rank == 0:
+        line = {
+            "metric": "proposals/sec + ellipsoid-rebuilds/sec, 25-D corr-Normal "
+                      "nlive=2000 (multi/rwalk)",
+            "value": value,
+            "unit": "proposals/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "preroll_steps": args.preroll,
+            "ms_per_step": wall / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": f"C2 x {runs} independent runs per GPU (C5 shard); "
+                            f"per step and run: 1 MultiEllipsoid rebuild + enlarge 1.25 + "
+                            f"{nq} queue fills of K={kq} walkers x {args.walks} rwalk steps "
+                            f"(= one bound-update interval at the queue size that passes the "
+                            f"ln Z gate); live sets uniform inside the likelihood contour",
+                "ndim": d, "nlive": nlive, "walks": args.walks, "queue_size": kq,
+                "queue_fills_per_step": nq,
+                "runs_per_gpu": runs, "tap_point": "A (kernel boundary)",
+                "rebuild_in_step": not args.no_rebuild,
+                "rebuilds_per_s": (0.0 if args.no_rebuild else
+                                   world * runs * args.steps / wall),
+                "rwalk_launches_per_step": nq,
+                "device_ms_per_step": dev_ms,
+                "rng": "PCG64 + ziggurat, stream-identical to numpy.random.Generator (parity mode)",
+            },
+        }
+        if args.full:
+            line["rccl_ranks"] = extra.pop("rccl_ranks")
+            line["config"].update(extra.pop("config"))
+            line.update(extra)
+        if cpu is not None:  # the CPU baseline is timed on rank 0 at N = 1 only
+            line["cpu_baseline"] = cpu
+        os.write(record_fd, (json.dumps(line) + "\n").encode())
+    dist.destroy_process_group()
+
+
+def full_legs(args, ctx, sh, prob, torch, dist, dev, rank, world, ev, nrep):
+    """--full: what the benchmark measures and checks beyond the headline, after its timed region.  Returns the
+    fields it adds to the line (rank 0)."""
+    runs, nlive, k, kq, nq, d = sh.runs, sh.nlive, sh.k, sh.kq, sh.nq, sh.d
+    props_per_launch = runs * kq * args.walks
+    props_per_step_rank = props_per_launch * nq
 
     # per-kernel durations (HIP events on the launch stream), outside the
     # timed region so the event records do not perturb it
-    nrep = 5
     t_rb = t_wk = 0.0
     for i in range(nrep):
         ctx.record(ev[0])
@@ -531,9 +628,6 @@ def main():
     status, nells = bnd["status"], bnd["nells"]
     assert np.all(nacc + nrej == args.walks)
     assert np.all(status == 0), status
-    props_per_launch = runs * kq * args.walks
-    props_per_step_rank = props_per_launch * nq
-    value = world * props_per_step_rank * args.steps / wall
 
     # The same interval as ONE launch of nlive walkers per run (queue size = nlive: the headline of rounds
     # 1-2), and both shapes in the throughput RNG mode (hiprand Philox) -- outside the timed region
@@ -684,43 +778,15 @@ def main():
                          for k, e in wl.items() if k.startswith(("rwalkq_kernel", "itemgen_kernel", "k_ell", "k_split",
                                                                  "k_root_parts"))}
         line = {
-            "metric": "proposals/sec + ellipsoid-rebuilds/sec, 25-D corr-Normal "
-                      "nlive=2000 (multi/rwalk)",
-            "value": value,
-            "unit": "proposals/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "preroll_steps": args.preroll,
-            "ms_per_step": wall / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
             "rccl_ranks": rccl_ranks,
             "config": {
-                "workload": f"C2 x {runs} independent runs per GPU (C5 shard); "
-                            f"per step and run: 1 MultiEllipsoid rebuild + enlarge 1.25 + "
-                            f"{nq} queue fills of K={kq} walkers x {args.walks} rwalk steps "
-                            f"(= one bound-update interval at the queue size that passes the "
-                            f"ln Z gate); live sets uniform inside the likelihood contour",
-                "ndim": d, "nlive": nlive, "walks": args.walks, "queue_size": kq,
-                "queue_fills_per_step": nq,
-                "runs_per_gpu": runs, "tap_point": "A (kernel boundary)",
-                "rebuild_in_step": not args.no_rebuild,
-                "rebuilds_per_s": (0.0 if args.no_rebuild else
-                                   world * runs * args.steps / wall),
                 "rebuild_kernel_ms": t_rb, "rwalk_kernel_ms": t_wk,
-                "rwalk_launches_per_step": nq,
-                "device_ms_per_step": dev_ms,
                 "proposals_per_s_rwalk_kernel_only":
                     world * props_per_launch / (t_wk * 1e-3),
                 "rebuilds_per_s_rebuild_kernel_only":
                     world * runs / (t_rb * 1e-3) if t_rb > 0 else None,
                 "nells_per_run": float(nells.mean()),
                 "accept_frac": float(nacc.sum() / props_per_launch),
-                "rng": "PCG64 + ziggurat, stream-identical to numpy.random.Generator (parity mode)",
                 "runs_per_gpu_sweep": sweep,
                 "tap_B": tap_b_record(),
                 "verified": verified,
@@ -777,10 +843,7 @@ def main():
                         "per level, not 12"}
         if e2e is not None:
             line["config"]["end_to_end"] = e2e
-        if cpu is not None:  # the CPU baseline is timed on rank 0 at N = 1 only
-            line["cpu_baseline"] = cpu
-        os.write(record_fd, (json.dumps(line) + "\n").encode())
-    dist.destroy_process_group()
+        return line
 
 
 def c3_leg(ctx, runs=16, queue=1024):

@@ -92,7 +92,7 @@ def test_bench_under_a_preset_visible_device_list():
     env = dict(os.environ, HIP_VISIBLE_DEVICES="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--lean", "--steps", "3", "--warmup", "1", "--preroll", "2"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--lean", "--steps", "3", "--warmup", "1", "--preroll", "2"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

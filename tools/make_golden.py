@@ -592,6 +592,67 @@ def gen_nsloop(out):
     print("wrote", out, len(g), "arrays; niter", niter, "fills", len(fills), "logz", g["run/logz_final"])
 
 
+def gen_merge(out):
+    """dynesty.utils.merge_runs on short static C1 runs (tests/test_merge_cpu.py): the per-run arrays the device
+    hands to ensemble.merge_logz / merge_static_runs and the reference's merged results."""
+    import dynesty
+    from dynesty import utils as dyu
+    import inputs
+    prob = inputs.problem("C1")
+    g = {}
+    # 1) ln Z and its error: four runs of nlive 100
+    res = []
+    for s in range(4):
+        sm = dynesty.NestedSampler(prob.loglikelihood, prob.prior_transform, 3, nlive=100, bound='single',
+                                   sample='unif', rstate=np.random.default_rng(s))
+        sm.run_nested(dlogz=0.1, print_progress=False)
+        res.append(sm.results)
+    merged = dyu.merge_runs(res, print_progress=False)
+    nit = [r.niter for r in res]
+    dead = np.zeros((4, max(nit)))
+    for i, r in enumerate(res):
+        dead[i, :nit[i]] = r.logl[:nit[i]]
+    g["logz/dead"], g["logz/nit"] = dead, np.array(nit, dtype=np.int64)
+    g["logz/live"] = np.array([np.asarray(r.logl[r.niter:]) for r in res])
+    g["logz/logz"], g["logz/logzerr"] = np.float64(merged.logz[-1]), np.float64(merged.logzerr[-1])
+    # 2) every per-point field: three runs of nlive 60
+    R, N = 3, 60
+    res = []
+    for s in range(R):
+        sm = dynesty.NestedSampler(prob.loglikelihood, prob.prior_transform, 3, nlive=N, bound='single',
+                                   sample='unif', rstate=np.random.default_rng(100 + s))
+        sm.run_nested(dlogz=0.3, print_progress=False)
+        res.append(sm.results)
+    ref = dyu.merge_runs(res, print_progress=False)
+    nit = [r.niter for r in res]
+    dead_l, dead_u = np.zeros((R, max(nit))), np.zeros((R, max(nit), 3))
+    live_l, live_u = np.zeros((R, N)), np.zeros((R, N, 3))
+    dead_i = np.zeros((3, R, max(nit)), dtype=np.int64)
+    live_it = np.zeros((R, N), dtype=np.int64)
+    for i, r in enumerate(res):
+        dead_l[i, :nit[i]] = r.logl[:nit[i]]
+        dead_u[i, :nit[i]] = r.samples_u[:nit[i]]
+        dead_i[0, i, :nit[i]] = r.samples_id[:nit[i]]
+        dead_i[1, i, :nit[i]] = r.samples_it[:nit[i]]
+        dead_i[2, i, :nit[i]] = r.ncall[:nit[i]]
+        # the device hands the final live points over in SLOT order (slot = the reference's 'id'), not sorted
+        sl = np.argsort(r.samples_id[nit[i]:])
+        assert (np.asarray(r.samples_id[nit[i]:])[sl] == np.arange(N)).all()
+        live_l[i] = np.asarray(r.logl[nit[i]:])[sl]
+        live_u[i] = np.asarray(r.samples_u[nit[i]:])[sl]
+        live_it[i] = np.asarray(r.samples_it[nit[i]:])[sl]
+    g.update({"static/nit": np.array(nit, dtype=np.int64), "static/dead_l": dead_l, "static/dead_u": dead_u,
+              "static/live_l": live_l, "static/live_u": live_u, "static/dead_i": dead_i, "static/live_it": live_it})
+    for k in ("samples_id", "samples_it", "ncall", "logl", "samples_n", "samples_u", "samples", "logvol", "logwt",
+              "logz", "information", "logzerr"):
+        g["ref/" + k] = np.asarray(getattr(ref, k))
+    g["ref/niter"] = np.int64(ref.niter)
+    g["ref/importance_weights"] = np.asarray(ref.importance_weights())
+    g["ref/eff"] = np.float64(ref.eff)
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(g), "arrays")
+
+
 if __name__ == "__main__":
     import_reference()
     gdir = os.path.join(ROOT, "tests", "golden")
@@ -611,5 +672,7 @@ if __name__ == "__main__":
         gen_wide(os.path.join(gdir, "wide.npz"))
     if "nsloop" in which:
         gen_nsloop(os.path.join(gdir, "nsloop.npz"))
+    if "merge" in which:  # not in the default list: tests/test_merge_cpu.py
+        gen_merge(os.path.join(gdir, "merge.npz"))
     if "livesets" in which:  # not in the default list: two partial reference runs (minutes)
         gen_livesets(os.path.join(gdir, "livesets.npz"))

@@ -6,7 +6,7 @@ timeout 900 python -m pytest tests/test_gpu_rwalkq.py tests/test_gpu_philox.py t
 tail -5 $O/pytest.log
 timeout 300 python tools/rwq_time.py 30 > $O/rwq_time.json 2>&1
 cat $O/rwq_time.json
-timeout 600 python bench.py --lean --steps 100 --warmup 5 > $O/bench_lean.json 2> $O/bench_lean.err
+timeout 600 python bench.py --full --lean --steps 100 --warmup 5 > $O/bench_lean.json 2> $O/bench_lean.err
 cat $O/bench_lean.json | head -c 3000
 cd /tmp; export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O -o bench -- python $GRAFT_REPO_ROOT/bench.py --lean --steps 20 --warmup 5 > $GRAFT_REPO_ROOT/$O/bench_under_rocprof.json 2> $GRAFT_REPO_ROOT/$O/rocprof.log

@@ -1,6 +1,6 @@
 # final records of round 6, second half, on the box (through tools/stage_reference.sh)
 O=gpurun_out/r6final2; mkdir -p $O
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_line_with_reference.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_line_with_reference.json 2> $O/bench.err
 timeout 900 python -m pytest tests/test_gpu_same_seed_hw.py -q 2>&1 | tail -5 > $O/same_seed.txt
 cp gpurun_out/same_seed_hw.json $O/ 2>/dev/null
 timeout 900 python tools/tapb_hw.py $O 30 > $O/tapb.log 2>&1
