@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <string>
 #include <vector>
@@ -58,7 +59,7 @@ struct dh_ctx {
   // side stream of the rebuild: the root's full eigen-system is solved there while the tree is built
   // on `stream` (fork after k_root, join before k_finish); created on first use
   hipStream_t side_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_leaf = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // rwalk kernel form (dh_set_rwalk_form): 0 / 2 = four lanes per walker (walkq.hip) wherever that kernel is
   // built -- decided by the problem alone, never by the launch size --, 1 = one walker per lane always
   int rwalk_form = 0;
@@ -67,6 +68,9 @@ struct dh_ctx {
   // the occupancy query (and guards with a spin limit that fails the run instead of hanging the device).  Off by
   // default: the cooperative path costs launch latency on the rebuild's critical path (EXPERIMENTS.md).
   int coop_launch = 0;
+  // DH_SPLIT_RESIDENT_PCT: the share of the chip's workgroup slots a chunk of k_split's parts may count on (rebuild.hip;
+  // lower it where another process shares the GPU)
+  int split_resident_pct = 87;
   // unit-cube sampler form (env DH_CUBE_FORM): 0 = four lanes per walker for launches that would leave SIMDs empty with
   // one walker per lane, 1 = one walker per lane always, 2 = four lanes always (PCG64 streams, ndim <= 32)
   int cube_form = 0;
@@ -104,6 +108,12 @@ namespace dh {
 
 int fail(dh_ctx* ctx, int code, const char* fmt, ...);
 bool hip_ok(dh_ctx* ctx, hipError_t e, const char* what);
+
+// an integer switch from the environment: its value, or `def` where it is not set
+inline int env_int(const char* name, int def) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : def;
+}
 
 // bump allocator over the context arena (256-byte aligned); reset per call
 void arena_reset(dh_ctx* ctx);

@@ -94,7 +94,6 @@ struct RebuildArgs {
   int* kerr;          // runs: error raised inside k_split (folded into status by the next kernel)
   double* fin_lse;    // runs x max_nodes: k_finish scratch (logsumexp of a node's result list)
   int* fin_int;       // runs x max_nodes x 2: k_finish scratch (accepted split / on the output path)
-  int* rbar;          // runs x kBarStride: barrier counters of the cooperative root
   double* rootbuf;    // runs x rootbuf_stride: partials exchanged by the root's parts
   size_t rootbuf_stride;
   double* kpart;      // 2 x runs x maxp x (2d + 2): per-part partial sums, by iteration parity
@@ -108,7 +107,7 @@ struct RebuildArgs {
   int* out_fast;      // runs x max_ells: 1 = that node's record is the eigen-free form
   // persistent work-queue form of the tree (k_tree): no levels -- a node's split is queued when its
   // ellipsoid exists, its children's ellipsoids when its last part has finished the partition
-  int tree;           // 1: queue_split / split_body / ell_body feed the queue instead of the level lists
+  int tree;           // 1 (k_tree): queue_split / split_body / ell_body feed the queue instead of the level lists
   int tree_from;      // level pipeline: splits for levels >= tree_from are queued for the k_tree tail instead
   unsigned long long* tq_items;  // tq_cap work items, 0 = not published yet
   int* tq_ctl;        // [0] head (next ticket), [16] tail (next free slot), [32] items queued or in flight, [48] error
@@ -116,7 +115,6 @@ struct RebuildArgs {
   int* nbar;          // runs x max_nodes x kBarStride: per node [0] part barrier, [1] parts done, [2] first k-means partial slot
   int* kp_top;        // runs: partial-sum slots handed out by the queue form (multi-part nodes only; capacity kp_cap per run)
   int kp_cap;
-  int tq_sleep, tq_nocoh;  // diagnostics (DH_TREE_SLEEP, DH_TREE_NOCOH)
   unsigned epoch;          // rebuild launches of this context so far: part of the tag of the k-means partials
   int root_run0;           // k_root_parts: first run of this launch (the runs go in chunks that are co-resident)
 };
@@ -829,16 +827,11 @@ __device__ __forceinline__ void node_cov(const Lds& L, const double* pts, const 
 //
 // Round 5: the B operand (AM's fragments) is the same for every block of points, so a lane holds its fragments in
 // registers for the whole node (QuadB: up to 11 K steps x 3 dimension blocks) instead of re-reading them from LDS at
-// every step; a block's A operands (its K steps of x) are fetched together, one LDS round trip; and a wavefront keeps
-// TWO blocks of 16 points in flight -- four to six independent accumulation chains on the matrix pipe where one
-// block's two were each waiting for their own previous step.  Per accumulator the K steps still run in ascending
-// order: the same bits.
+// every step, and a block's A operands (its K steps of x) are fetched together, one LDS round trip.  (Two blocks of
+// points in flight per wavefront spilled 49 registers in k_ell: 1.30 -> 1.76 ms, EXPERIMENTS.md round 5.)
 // Register shape: NB dimension blocks of 16, at most KS K steps of 4.  Built for <2, 8> (17 <= D <= 32): the other
 // shapes keep the general form below -- three copies of this loop at k_ell's every call site cost more in spills
 // than they gave.
-#ifndef DH_QUAD_TWO
-#define DH_QUAD_TWO false
-#endif
 template <int NB, int KS>
 struct QuadB {
   double b[KS][NB];
@@ -890,37 +883,27 @@ __device__ __forceinline__ double tile_quadform_max(const double* tile, int LD, 
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int ksteps = (D + 3) >> 2;
   const int lj = lane & 15, lk = lane >> 4;
-  constexpr int NW = NT / 64;
-  constexpr bool TWO = DH_QUAD_TWO;
-  for (int mb = w; mb * 16 < cnt; mb += (TWO ? 2 : 1) * NW) {
-    const int pA = mb * 16, pB = (mb + NW) * 16;
-    const bool hasB = TWO && pB < cnt;  // (uniform per wavefront)
-    const bool va = pA + lj < cnt, vb = hasB && pB + lj < cnt;
-    const int xao = (pA + lj) * LD + lk, xbo = (pB + lj) * LD + lk;
-    double aA[KS], aB[TWO ? KS : 1];
+  for (int mb = w; mb * 16 < cnt; mb += NT / 64) {
+    const int p0 = mb * 16;
+    const bool va = p0 + lj < cnt;
+    const int xo = (p0 + lj) * LD + lk;
+    double av[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const bool kv = ks < ksteps && ks * 4 + lk < D;
-      aA[ks] = sel_ld(tile, xao + ks * 4, va && kv);
-      if constexpr (TWO) aB[ks] = sel_ld(tile, xbo + ks * 4, vb && kv);
+      av[ks] = sel_ld(tile, xo + ks * 4, va && kv);
     }
-    mfma_acc zA[NB], zB[NB];
+    mfma_acc z[NB];
 #pragma unroll
-    for (int n = 0; n < NB; ++n) zA[n] = zB[n] = (mfma_acc){0.0, 0.0, 0.0, 0.0};
+    for (int n = 0; n < NB; ++n) z[n] = (mfma_acc){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       if (ks < ksteps) {
 #pragma unroll
-        for (int n = 0; n < NB; ++n) {
-          zA[n] = DH_MFMA_F64(aA[ks], B.b[ks][n], zA[n]);
-          if constexpr (TWO)
-            if (hasB) zB[n] = DH_MFMA_F64(aB[ks], B.b[ks][n], zB[n]);
-        }
+        for (int n = 0; n < NB; ++n) z[n] = DH_MFMA_F64(av[ks], B.b[ks][n], z[n]);
       }
     }
-    best = quad_block_max<NB>(tile, LD, pA, cnt, D, zA, best);
-    if constexpr (TWO)
-      if (hasB) best = quad_block_max<NB>(tile, LD, pB, cnt, D, zB, best);
+    best = quad_block_max<NB>(tile, LD, p0, cnt, D, z, best);
   }
   return best;
 }
@@ -1145,13 +1128,6 @@ __device__ __forceinline__ bool regularize(const Lds& L, double* cov, int D) {
 // reference's own route (regularize: Jacobi eigh + the 100-trial loop).  The ellipsoids that
 // survive the accept test get their full eigen-system from k_out_eig at the end (same Jacobi, run
 // once per OUTPUT instead of once per tree node).
-#ifndef DH_SPD_OVERLAP
-// 1: the sweeps (wavefronts 0, 1) and the squarings (wavefronts 2, 3) of spd_fast side by side.  MEASURED AND OFF
-// (round 6, tools/r6_phase.py): bit-identical, but the sweeps are bound by the instructions of a wavefront, not by
-// latency -- on 128 threads a double sweep takes twice as long (ldl+inv 270 -> 520-700 per node, in hundreds of cycles)
-// and eats what the hidden squarings give (-25 .. -330): 64 runs 1.04 -> 1.09 ms.  The code stays for the record.
-#define DH_SPD_OVERLAP 0
-#endif
 constexpr double kFastCond = 1e7;
 constexpr int kFastSquarings = 48;
 
@@ -1196,31 +1172,6 @@ __device__ __forceinline__ void sym_square(const double* P, double* Q, int D, in
   }
 }
 
-// sym_square's matrix-core form for the wavefronts wfirst .. wfirst + nw - 1 alone (tile by tile the same products:
-// the same bits as sym_square's); D >= kMfmaMinDim; caller barriers
-__device__ __forceinline__ void sym_square_waves(const double* P, double* Q, int D, int LD, double s2, int wfirst, int nw) {
-  const int lane = threadIdx.x & 63, w = (threadIdx.x >> 6) - wfirst;
-  const int nb = (D + 15) >> 4, ksteps = (D + 3) >> 2;
-  const int lj = lane & 15, lk = lane >> 4;
-  for (int tile = w; tile < nb * nb; tile += nw) {
-    const int ti = tile / nb, tj = tile - ti * nb;
-    mfma_acc acc = {0.0, 0.0, 0.0, 0.0};
-    const int ca = ti * 16 + lj, cb = tj * 16 + lj;
-    for (int ks = 0; ks < ksteps; ++ks) {
-      const int k = ks * 4 + lk;
-      const bool kv = k < D;
-      const double av = sel_ld(P, k * LD + ca, kv && ca < D);
-      const double bv = sel_ld(P, k * LD + cb, kv && cb < D);
-      acc = DH_MFMA_F64(av, bv, acc);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = ti * 16 + lk + 4 * r;
-      if (i < D && cb < D) Q[i * LD + cb] = acc[r] * s2;
-    }
-  }
-}
-
 // 1 / x to full precision: v_rcp_f64 (2^-24, tools/micro/rsq_acc.hip) + two Newton steps
 __device__ __forceinline__ double rcp_nr(double x) {
   double y = __builtin_amdgcn_rcp(x);
@@ -1255,7 +1206,6 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
   const int istep = NT / D > 0 ? NT / D : 1;
   const int i0 = t / D;
   const int j = i0 < istep ? t - i0 * D : D;
-  const int jsh = D <= 32 ? 5 : 6;  // (the overlap experiment's 128-thread map)
   // Two sweeps per barrier (round 5): sweep k + 1 needs, of the matrix sweep k produces, row k + 1, column k + 1 and
   // the entry itself -- each of them one fma of entries of the matrix sweep k READS, so a thread forms them on its own
   // (the very expressions sweep k would have stored) and applies both sweeps to its entries before anyone has to
@@ -1265,7 +1215,7 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
   double* dst = (nswap & 1) ? L.A : L.AM;
   double* pivs = L.red;  // the D pivots
   // the copy of the covariance that outlives the sweeps (they work in L.A / L.AM): L.AX while the squarings need L.A and
-  // L.V, else L.V; none where the carve has no separate matrices (k_ell_wave's leaves: no axis wanted either)
+  // L.V, else L.V; none where the carve has no separate matrices
   double* keep = (L.V != nullptr && L.AX != L.A) ? (want_axis ? L.AX : L.V) : nullptr;
   if (cov_keep) *cov_keep = keep;
   PH_T0();
@@ -1283,45 +1233,9 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
   // (the squarings and the Rayleigh quotient read the covariance from `keep` where there is one, else from `cov`: two
   // code paths, not one pointer -- a pointer that may be LDS or global is a generic one, and its loads FLAT loads)
   const double tr_cov = wave_trace(src, D, LD);
-  // (round 6) SWEEPS AND SQUARINGS SIDE BY SIDE.  The inverse (13 double sweeps at D = 25) and the dominant eigenvector
-  // (8-14 squarings) both need only the covariance, and they ran one after the other: 12 + 8-16 us of a node's ~45.
-  // In the 256-thread kernels wavefronts 0, 1 now sweep (their 128 threads take the rows in two batches) while
-  // wavefronts 2, 3 square -- first from the untouched copy in L.AX (scaled by s0^2 in the product: powers of two,
-  // the same bits as squaring the scaled copy), then between L.V and L.AX -- meeting at the sweeps' own barriers.  A
-  // squaring chain that is not done when the sweeps are goes on with all four wavefronts, as before.  The covariance
-  // is read back from the node's global working copy afterwards (one trip) for the Rayleigh quotient and the record.
-  const int wv = threadIdx.x >> 6;
-  const bool ovl = NT == kThreads && want_axis && keep != nullptr && keep == L.AX && D <= 32 && D >= kMfmaMinDim &&
-                   !(DH_SPD_OVERLAP == 0);
-  const bool sweeper = !ovl || (wv < 2 && i0 < (128 / D > 0 ? 128 / D : 1));
-  const int istep_e = ovl ? (128 / D > 0 ? 128 / D : 1) : istep;
-  const int nslots = (D + istep_e - 1) / istep_e;  // row slots of a thread (uniform)
-  (void)jsh;
-  const double s0_o = ldexp(1.0, -(ilogb(tr_cov) + 1));  // (as below: trace of the scaled copy in [1/2, 1))
-  const double* sP = L.AX;
-  double* sQ = L.V;
-  double trP_o = tr_cov * s0_o;
-  bool conv_o = false;
-  int nsq = 0;
-  auto square_issue = [&]() {  // wavefronts 2, 3: one squaring's products
-    if (ovl && wv >= 2 && !conv_o) {
-      const double sc = ldexp(1.0, -(ilogb(trP_o * trP_o) + 1));
-      sym_square_waves(sP, sQ, D, LD, nsq == 0 ? sc * s0_o * s0_o : sc, 2, 2);
-    }
-  };
-  auto square_close = [&]() {  // ... and, behind the barrier, its trace and the convergence test
-    if (ovl && wv >= 2 && !conv_o) {
-      const double sc = ldexp(1.0, -(ilogb(trP_o * trP_o) + 1));
-      const double trQ = wave_trace(sQ, D, LD);
-      const double r = trQ / (trP_o * trP_o * sc);
-      conv_o = 1.0 - r < 1e-8;
-      trP_o = trQ;
-      const double* nP = sQ;
-      sQ = nsq == 0 ? L.AX : const_cast<double*>(sP);
-      sP = nP;
-      ++nsq;
-    }
-  };
+  // (the sweeps are bound by a wavefront's instructions: running them on two wavefronts beside the squarings on the
+  // other two lost, 1.04 -> 1.09 ms per 64 runs -- EXPERIMENTS.md round 6)
+  const int nslots = (D + istep - 1) / istep;  // row slots of a thread (uniform)
   bool ok = true;
   int k = 0;
   for (; k + 1 < D; k += 2) {
@@ -1344,7 +1258,7 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
       pivs[k] = piv;
       pivs[k1] = piv1;
     }
-    if (sweeper && j < D) {
+    if (j < D) {
       const double cj = src[k * LD + j], dj = src[k1 * LD + j];
       const double cjr = cj * rp;
       const double r1j = (j == k) ? a10 * rp : fma(-a10, cjr, dj);  // sweep k: (row k + 1, column j)
@@ -1355,7 +1269,7 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
         double ci[U], ei[U], w[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          const int i = ib + u * istep_e;
+          const int i = ib + u * istep;
           const int ic = i < D ? i : k;
           ci[u] = src[ic * LD + k];
           ei[u] = src[ic * LD + k1];
@@ -1363,7 +1277,7 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          const int i = ib + u * istep_e;
+          const int i = ib + u * istep;
           // sweep k at (i, j) and at (i, k + 1)
           double v = fma(-ci[u], cjr, w[u]);
           v = (j == k) ? ci[u] * rp : v;
@@ -1383,11 +1297,9 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
       else if (nslots == 3)
         rows(std::integral_constant<int, 3>{}, i0);
       else
-        for (int ib = i0; ib < D; ib += 4 * istep_e) rows(std::integral_constant<int, 4>{}, ib);
+        for (int ib = i0; ib < D; ib += 4 * istep) rows(std::integral_constant<int, 4>{}, ib);
     }
-    square_issue();
     __syncthreads();
-    square_close();
     double* tmp = src;
     src = dst;
     dst = tmp;
@@ -1399,21 +1311,21 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
     } else {
       const double rp = rcp_nr(piv);
       if (t == 0) pivs[k] = piv;
-      if (sweeper && j < D) {
+      if (j < D) {
         const double cj = src[k * LD + j];
         const double cjr = cj * rp;
-        for (int ib = i0; ib < D; ib += 4 * istep_e) {
+        for (int ib = i0; ib < D; ib += 4 * istep) {
           double ci[4], w[4];
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
-            const int i = ib + u * istep_e;
+            const int i = ib + u * istep;
             const int ic = i < D ? i : k;
             ci[u] = src[ic * LD + k];
             w[u] = src[ic * LD + j];
           }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
-            const int i = ib + u * istep_e;
+            const int i = ib + u * istep;
             double val = fma(-ci[u], cjr, w[u]);
             val = (j == k) ? ci[u] * rp : val;
             val = (i == k) ? ((j == k) ? -rp : cjr) : val;
@@ -1421,24 +1333,13 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
           }
         }
       }
-      square_issue();
       __syncthreads();
-      square_close();
       double* tmp = src;
       src = dst;
       dst = tmp;
     }
   }
   if (!ok) return false;
-  // the squaring wavefronts' state to everybody (read behind the barrier of the symmetrised inverse below)
-  __shared__ double s_ovl_tr;
-  __shared__ int s_ovl[3];
-  if (ovl && threadIdx.x == 128) {
-    s_ovl_tr = trP_o;
-    s_ovl[0] = conv_o ? 1 : 0;
-    s_ovl[1] = nsq;
-    s_ovl[2] = sP == L.V ? 1 : 0;
-  }
   double ld;
   {
     const int lane = t & 63;  // every wave for itself (D <= 44 < 64)
@@ -1454,7 +1355,7 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
   *logdet = ld;
   PH_ADD(13);
   // (with the copy kept in L.AX the matrix is zeroed where the axis is written, at the end)
-  if (!(want_axis && keep == L.AX)) {  // (never with the overlap: it needs keep == L.AX)
+  if (!(want_axis && keep == L.AX)) {
     for (int e = t; e < D * D; e += NT) L.AX[(e / D) * LD + e % D] = 0.0;
     if (t < D) L.lam[t] = 0.0;
   }
@@ -1479,32 +1380,17 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
   // ---- dominant eigenvector by repeated squaring ----
   double* P = L.A;
   double* Q = L.V;
-  double trP;
   bool conv = false;
-  int it0 = 0;
-  if (ovl) {
-    // what wavefronts 2, 3 have done beside the sweeps; the covariance comes back into L.A (free since the inverse was
-    // symmetrised into L.AM) from the node's global working copy
-    trP = s_ovl_tr;
-    conv = s_ovl[0] != 0;
-    it0 = s_ovl[1];
-    P = s_ovl[2] ? L.V : L.AX;
-    Q = s_ovl[2] ? L.AX : L.V;
-    if (conv)
-      for (int e = t; e < D * D; e += NT) L.A[(e / D) * LD + e % D] = cov[(e / D) * LD + e % D];
-    __syncthreads();
-  } else {
-    {
-      const double s0 = ldexp(1.0, -(ilogb(tr_cov) + 1));  // trace in [1/2, 1)
-      if (keep)
-        for (int e = t; e < D * D; e += NT) P[(e / D) * LD + e % D] = keep[(e / D) * LD + e % D] * s0;
-      else
-        for (int e = t; e < D * D; e += NT) P[(e / D) * LD + e % D] = cov[(e / D) * LD + e % D] * s0;
-    }
-    __syncthreads();
-    trP = wave_trace(P, D, LD);
+  {
+    const double s0 = ldexp(1.0, -(ilogb(tr_cov) + 1));  // trace in [1/2, 1)
+    if (keep)
+      for (int e = t; e < D * D; e += NT) P[(e / D) * LD + e % D] = keep[(e / D) * LD + e % D] * s0;
+    else
+      for (int e = t; e < D * D; e += NT) P[(e / D) * LD + e % D] = cov[(e / D) * LD + e % D] * s0;
   }
-  for (int it = it0; it < kFastSquarings && !conv; ++it) {
+  __syncthreads();
+  double trP = wave_trace(P, D, LD);
+  for (int it = 0; it < kFastSquarings && !conv; ++it) {
     // the product is scaled by a power of two (exact) chosen from tr(P)^2, the upper bound of its
     // trace: tr(P^2) / tr(P)^2 = r in [1/D, 1] is the sum of the squared eigenvalue weights of P, so the
     // stored trace stays within [1/(4D), 1) without a pass of its own
@@ -1519,10 +1405,6 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
     double* tmp = P;
     P = Q;
     Q = tmp;
-    if (ovl && conv) {  // (the covariance back into L.A, as above)
-      for (int e = t; e < D * D; e += NT) L.A[(e / D) * LD + e % D] = cov[(e / D) * LD + e % D];
-      __syncthreads();
-    }
   }
   if (!conv) return false;
   PH_ADD(14);
@@ -1587,11 +1469,10 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
   // squaring buffer that is free now (Q) and writes the axis matrix -- column 0 = sqrt(lam_max) v, zero elsewhere: the
   // same values as above
   __shared__ double s_q;
-  const double* cvm = ovl ? L.A : L.AX;  // where the covariance sits now
   if (t < 64) {
     double y = 0.0;
     if (t < D)
-      for (int k = 0; k < D; ++k) y = fma(cvm[t * LD + k], s_v[k], y);
+      for (int k = 0; k < D; ++k) y = fma(L.AX[t * LD + k], s_v[k], y);
     const double q = wave_sum(t < D ? y * s_v[t] : 0.0);
     if (t == 0) s_q = q;
   }
@@ -1600,11 +1481,11 @@ __device__ __forceinline__ bool spd_fast(const Lds& L, const double* cov, int D,
     const double q = s_q, rq = sqrt(q);
     for (int e = t; e < D * D; e += NT) {
       const int i = e / D, jj = e - i * D, o = i * LD + jj;
-      if (!ovl) Q[o] = L.AX[o];
+      Q[o] = L.AX[o];
       L.AX[o] = jj == 0 ? s_v[i] * rq : 0.0;
     }
     if (t < D) L.lam[t] = t == 0 ? q : 0.0;
-    if (cov_keep) *cov_keep = ovl ? L.A : Q;
+    if (cov_keep) *cov_keep = Q;
     __syncthreads();
     PH_ADD(15);
     return q > 0.0 && isfinite(q);
@@ -1820,9 +1701,7 @@ __device__ __forceinline__ int node_ellipsoid(const Lds& L, const RebuildArgs& a
 // store still in flight to another L2 channel can land after the counter's atomic and a partner then
 // reads the previous iteration's partial -- seen as 3 differing results in 2 700 eggbox rebuilds once
 // 128-point parts made multi-part nodes common), hence the explicit vmcnt(0).
-#ifndef DH_BAR_SLEEP
-#define DH_BAR_SLEEP 4
-#endif
+constexpr int kBarSleep = 4;  // s_sleep argument of a part barrier's poll
 __device__ __forceinline__ void drain_stores() {
   __builtin_amdgcn_s_waitcnt(0x0F70);  // gfx9 encoding: vmcnt(0), expcnt / lgkmcnt untouched
 }
@@ -1905,7 +1784,7 @@ __device__ __forceinline__ bool parts_barrier(int* bar, int target) {
     int ok = 1;
     long long spins = 0;
     while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-      __builtin_amdgcn_s_sleep(DH_BAR_SLEEP);
+      __builtin_amdgcn_s_sleep(kBarSleep);
       if (++spins > (1ll << 20)) {  // partners never arrived (would otherwise hang the device)
         ok = 0;
         break;
@@ -1967,6 +1846,11 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
+// Lloyd iterations of a split (the reference's kmeans2(iter=10)).  Iteration it publishes its partials with the tag
+// tag0 + it + 1, whose low 8 bits are the iteration's (split_body's tag0).
+constexpr int kLloydIters = 10;
+static_assert(kLloydIters + 1 <= 0xff, "the iteration tag has 8 bits");
+
 // One part's share of the k-means + partition of node [start, start+count).  q = part
 // index, np = number of parts, kp = this node's partial-sum slots (2 parities x np x KP),
 // bar = its barrier counter.  Returns n0 (size of cluster 0) or -1 on a barrier timeout;
@@ -2002,7 +1886,7 @@ __device__ int node_kmeans_part(const Lds& L, const double* pts, int* perm, int*
   __syncthreads();
   const int nb = (D + 15) >> 4;
   const int lj = lane & 15, lk = lane >> 4;
-  int lb = 0, lb_prev = -1, n0 = 0, c0_tile = 0, last_it = 9;
+  int lb = 0, lb_prev = -1, n0 = 0, c0_tile = 0, last_it = kLloydIters - 1;
   LV_ADD(lvl, 0);
   LV_SET(lvl, 5, np);
   LV_SET(lvl, 6, count);
@@ -2017,7 +1901,7 @@ __device__ int node_kmeans_part(const Lds& L, const double* pts, int* perm, int*
     __syncthreads();
   }
   unsigned long long m0 = 0ull, m1 = 0ull;  // this wave's label ballots (valid points only)
-  for (int it = 0; it < 10; ++it) {
+  for (int it = 0; it < kLloydIters; ++it) {
     // vq: nearest centroid, strict '<' so the lower index wins ties.  (round 6) The centroids ride in the lanes of two
     // registers (lane j: coordinate j) and reach the distance loop through v_readlane: two LDS loads per wave and
     // iteration instead of two per dimension and point -- with four to five parts per CU the LDS pipe was half of
@@ -2505,7 +2389,6 @@ __global__ void __launch_bounds__(kThreads, 2) k_root_parts(RebuildArgs a, int r
     double* b_am = b_cov + (size_t)rp * DD * 2;
     double* b_fmx = b_am + (size_t)DD * 2;
     double* b_flag = b_fmx + (size_t)rp * 2;
-    double* b_stat = b_flag + 2;
     const unsigned long long tg = ((unsigned long long)a.epoch << 8) | 0x8000000000000000ull;  // (+ phase 1..6)
     __shared__ int s_bad;
     if (t == 0) s_bad = 0;
@@ -2669,7 +2552,6 @@ __global__ void __launch_bounds__(kThreads, 2) k_root_parts(RebuildArgs a, int r
       if (s_bad) status = DH_ERR_HIP;
       if (t == 0 && status == DH_OK && want_split) queue_split(a, run, 0, 0, n);
     }
-    (void)b_stat;
   }
   if (q == 0 && t == 0) {
     Node r;
@@ -2718,7 +2600,7 @@ __device__ __forceinline__ void split_body(const RebuildArgs& a, const Lds& L, c
   // k_tree (a.tree): `slot` IS the node; its barrier / done counter / first partial-sum slot sit in nbar
   const bool tq = a.tree == 1;
   int* nb = tq ? a.nbar + ((size_t)run * a.max_nodes + slot) * kBarStride : nullptr;
-  const int pb = tq ? ld_agent_i(nb + 2) : (a.tree ? 0 : a.part_base[lp * a.maxw + slot]);
+  const int pb = tq ? ld_agent_i(nb + 2) : a.part_base[lp * a.maxw + slot];
   const int cur = a.tree ? slot : a.split_list[lp * a.maxw + slot];
   const int start = ld_ci(L, &v.nodes[cur].start), count = ld_ci(L, &v.nodes[cur].count),
             depth = ld_ci(L, &v.nodes[cur].depth);
@@ -2866,7 +2748,7 @@ __device__ __forceinline__ void k_split_impl(const RebuildArgs& a, int level, in
 // Returns false after an error (status set).
 // DEFER (the level kernel's eigen-free form): a node the eigen-free path declines -- or one without a mean in its
 // record, which a child never is -- goes to the work-queue tail untouched (its record is written last, so nothing of
-// it exists yet), as k_ell_wave's declined leaves do.
+// it exists yet).
 template <bool SLOW, bool DEFER = false>
 __device__ __forceinline__ bool ell_body(const RebuildArgs& a, const Lds& L, const RunView& v, int run, int level, int node) {
   const int D = a.d, t = threadIdx.x;
@@ -2919,17 +2801,16 @@ __device__ __forceinline__ bool ell_body(const RebuildArgs& a, const Lds& L, con
 template <bool SLOW, bool DEFER>
 // (two workgroups per CU: held to the 168 registers of three, with a 128-point tile so that LDS would allow it, the
 // eigen-free path spills and the rebuild loses 7 %)
-__device__ __forceinline__ void k_ell_impl(const RebuildArgs& a, int level, int G, int skip_done, int leaf_cap, int tp);
+__device__ __forceinline__ void k_ell_impl(const RebuildArgs& a, int level, int G, int skip_done, int tp);
 template <bool SLOW, bool DEFER = false>
-__global__ void __launch_bounds__(kThreads, SLOW ? 1 : 2) k_ell(RebuildArgs a, int level, int G, int skip_done, int leaf_cap,
-                                                                 int tp) {
+__global__ void __launch_bounds__(kThreads, SLOW ? 1 : 2) k_ell(RebuildArgs a, int level, int G, int skip_done, int tp) {
   WG_STAMP(1, level, 0);
   PH_LEVEL(level);
-  k_ell_impl<SLOW, DEFER>(a, level, G, skip_done, leaf_cap, tp);
+  k_ell_impl<SLOW, DEFER>(a, level, G, skip_done, tp);
   WG_STAMP(1, level, 1);
 }
 template <bool SLOW, bool DEFER>
-__device__ __forceinline__ void k_ell_impl(const RebuildArgs& a, int level, int G, int skip_done, int leaf_cap, int tp) {
+__device__ __forceinline__ void k_ell_impl(const RebuildArgs& a, int level, int G, int skip_done, int tp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // run-minor: the g-th node of EVERY run before anyone's (g + 1)-th -- workgroups are dispatched in index order at
   // a finite rate (~30 per us), and with the runs major the last run's first node started after 2 600 others
@@ -2949,10 +2830,6 @@ __device__ __forceinline__ void k_ell_impl(const RebuildArgs& a, int level, int 
   for (int slot = g; slot < cnt; slot += G) {
     // (a child is created with fmax = inf: a finite value = k_ell_wave has built this one)
     if (skip_done && v.nodes[list[slot]].fmax < INFINITY) continue;
-    if (leaf_cap > 0) {  // the leaves of this level are k_ell_wave<128>'s, on the side stream (the same test as its own)
-      const Node& nd = v.nodes[list[slot]];
-      if (nd.has_mean && nd.count >= 2 && nd.count <= leaf_cap && nd.count < 4 * D) continue;
-    }
     if (!ell_body<SLOW, DEFER>(a, L, v, run, level, list[slot])) return;
   }
 }
@@ -2961,26 +2838,26 @@ __device__ __forceinline__ void k_ell_impl(const RebuildArgs& a, int level, int 
 // The deep levels of a tree are many small nodes (the 64-run bench rebuild: 2 048 leaves of ~62 points at level
 // 5; an eggbox live set: hundreds of nodes of 8-60 points per level and run), and a level's time is the number of
 // ROUNDS its nodes need on the chip's workgroup slots: k_ell holds 256 threads, 242 registers and 77 KB of LDS per
-// node -- two nodes per CU.  k_ell_wave builds a node of at most `cap` points with ONE wavefront and an LDS carve of
-// its own (tile of cap points, two or four D x D matrices): the same routines instantiated for 64 threads
+// node -- two nodes per CU.  k_ell_wave builds a node of at most kWaveCap points with ONE wavefront and an LDS carve
+// of its own (tile of kWaveCap points, four D x D matrices): the same routines instantiated for 64 threads
 // (stage_tile / spd_fast / node_fmax / ... <64>: every element-wise loop and every MFMA tile is the same
 // instruction on the same operands whichever thread issues it), the covariance contraction with the four waves of
 // k_ell played in turn (tile_cov_accumulate's wsel: wave w takes points [64 w, 64 w + 64), partial sums folded in
 // wave order).  So a node gets the SAME BITS from either kernel (tests/test_gpu_edges.py holds the whole tree to
 // that), and which kernel builds it is a scheduling decision: k_ell_wave runs first over the level's list and takes
-// the nodes that fit (`axis` = 0: leaves only -- count < 4 D, no major axis wanted, half the matrices), marks them
-// by their finite fmax, and k_ell skips those.  A node whose eigen-free path does not apply (spd_fast false) is
-// left untouched for k_ell's in-place fallback.
+// the nodes that fit, marks them by their finite fmax, and k_ell skips those.  A node whose eigen-free path does not
+// apply (spd_fast false) is left untouched for k_ell.
 constexpr int kWaveDeclined = 2;
+constexpr int kWaveCap = 128;
 
-__host__ __device__ inline size_t wave_lds_bytes(int D, int cap, bool axis) {
+__host__ __device__ inline size_t wave_lds_bytes(int D) {
   const int LD = D | 1;
-  return ((((size_t)cap * LD + (axis ? 4 : 2) * (size_t)D * LD + 2 * (size_t)D + 64) * 8) + 15) & ~(size_t)15;
+  return ((((size_t)kWaveCap * LD + 4 * (size_t)D * LD + 2 * (size_t)D + 64) * 8) + 15) & ~(size_t)15;
 }
 
-__device__ __forceinline__ void carve_wave(Lds& L, unsigned char* smem, int D, int cap, bool axis) {
+__device__ __forceinline__ void carve_wave(Lds& L, unsigned char* smem, int D) {
   L.LD = D | 1;
-  L.TP = cap;
+  L.TP = kWaveCap;
   L.c_pts = nullptr;
   L.c_start = L.c_cnt = L.c_how = -1;
   L.coh = false;
@@ -2993,20 +2870,15 @@ __device__ __forceinline__ void carve_wave(Lds& L, unsigned char* smem, int D, i
   }
   double* p = (double*)smem;
   L.tile = p;
-  p += (size_t)cap * L.LD;
+  p += (size_t)kWaveCap * L.LD;
   L.A = p;
   p += D * L.LD;
   L.AM = p;
   p += D * L.LD;
-  if (axis) {
-    L.V = p;
-    p += D * L.LD;
-    L.AX = p;
-    p += D * L.LD;
-  } else {
-    L.V = nullptr;  // (the squarings of the major axis: not wanted for a leaf)
-    L.AX = L.A;     // spd_fast zeroes AX after its last use of A
-  }
+  L.V = p;
+  p += D * L.LD;
+  L.AX = p;
+  p += D * L.LD;
   L.mean = p;
   p += D;
   L.lam = p;
@@ -3021,68 +2893,55 @@ __device__ __forceinline__ void carve_wave(Lds& L, unsigned char* smem, int D, i
   L.j_alias = false;
 }
 
-// node_ellipsoid<true> for a child (mean in its record) of at most L.TP points, by NT / 64 wavefronts (one, or two:
-// round 5).  With two, wavefront w takes k_ell's wavefronts w, w + 2 in turn and the partial sums are still folded in
-// k_ell's wave order: the same bits from every form.
-template <int NT>
+// node_ellipsoid<true> for a child (mean in its record) of at most L.TP points by one wavefront, which plays k_ell's
+// wavefronts in turn and folds their partial sums in k_ell's wave order: the same bits from either kernel.
 __device__ __forceinline__ int node_ellipsoid_wave(const Lds& L, const RebuildArgs& a, const double* pts, const int* perm,
                                                    int start, int count, double* es, double* cov_g,
                                                    double* logvol_out, double* fmax_out) {
-  constexpr int NW = NT / 64;
   const int D = a.d, t = threadIdx.x, LD = L.LD;
   if (t < D) L.mean[t] = es[t];
   __syncthreads();
   // node_cov, one tile
-  stage_tile<NT>(L, pts, perm, start, count, D, 1);
+  stage_tile<64>(L, pts, perm, start, count, D, 1);
   {
-    const int nb = (D + 15) >> 4, lane = t & 63, lj = lane & 15, lk = lane >> 4, mw = t >> 6;
-    for (int wv0 = 0; wv0 * 64 < count; wv0 += NW) {
-      const int wv = wv0 + mw;  // the wave of k_ell this wavefront plays now
-      const bool mine = wv * 64 < count;
+    const int nb = (D + 15) >> 4, lane = t & 63, lj = lane & 15, lk = lane >> 4;
+    for (int wv = 0; wv * 64 < count; ++wv) {  // wv: the wave of k_ell this wavefront plays now
       mfma_acc acc[6];
 #pragma unroll
       for (int b = 0; b < 6; ++b) acc[b] = (mfma_acc){0.0, 0.0, 0.0, 0.0};
-      if (mine) tile_cov_accumulate(L, count, D, acc, wv);
-      for (int turn = 0; turn < NW; ++turn) {  // cov_fold_waves, one wave's turn after the other
-        if (mine && mw == turn) {
+      tile_cov_accumulate(L, count, D, acc, wv);
 #pragma unroll
-          for (int b = 0; b < 6; ++b) {
-            const int ib = b == 0 ? 0 : b == 1 ? 0 : b == 2 ? 1 : b == 3 ? 0 : b == 4 ? 1 : 2;
-            const int jb = b == 0 ? 0 : b == 1 ? 1 : b == 2 ? 1 : 2;
-            if (jb < nb) {
+      for (int b = 0; b < 6; ++b) {  // cov_fold_waves, this wave's turn
+        const int ib = b == 0 ? 0 : b == 1 ? 0 : b == 2 ? 1 : b == 3 ? 0 : b == 4 ? 1 : 2;
+        const int jb = b == 0 ? 0 : b == 1 ? 1 : b == 2 ? 1 : 2;
+        if (jb < nb) {
 #pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int i = ib * 16 + lk + 4 * r, j = jb * 16 + lj;
-                if (i < D && j < D) {
-                  double v = acc[b][r];
-                  if (wv > 0) v += L.A[i * LD + j];
-                  L.A[i * LD + j] = v;
-                }
-              }
+          for (int r = 0; r < 4; ++r) {
+            const int i = ib * 16 + lk + 4 * r, j = jb * 16 + lj;
+            if (i < D && j < D) {
+              double v = acc[b][r];
+              if (wv > 0) v += L.A[i * LD + j];
+              L.A[i * LD + j] = v;
             }
           }
         }
-        __syncthreads();
       }
+      __syncthreads();
     }
   }
-  cov_finalize<NT>(L, D, 1.0 / (double)(count - 1));
-  for (int e = t; e < D * D; e += NT) cov_g[(e / D) * LD + e % D] = L.A[(e / D) * LD + e % D];
+  cov_finalize<64>(L, D, 1.0 / (double)(count - 1));
+  for (int e = t; e < D * D; e += 64) cov_g[(e / D) * LD + e % D] = L.A[(e / D) * LD + e % D];
   __syncthreads();
   double logdet = 0.0;
-  if (!spd_fast<NT>(L, cov_g, D, a.mode == 0 && count >= 4 * D, &logdet)) return kWaveDeclined;
-  const double fmx = node_fmax<NT>(L, pts, perm, start, count, D);
+  if (!spd_fast<64>(L, cov_g, D, a.mode == 0 && count >= 4 * D, &logdet)) return kWaveDeclined;
+  const double fmx = node_fmax<64>(L, pts, perm, start, count, D);
   if (fmx > 1.0 - kRoundDelta) logdet += (double)D * log(fmx / (1.0 - kRoundDelta));
-  ellipsoid_rescale<NT>(L, cov_g, D, fmx);
+  ellipsoid_rescale<64>(L, cov_g, D, fmx);
   *fmax_out = fmin(fmx, 1.0 - kRoundDelta);
-  return ellipsoid_store_fast<NT>(L, a, es, cov_g, logdet, logvol_out);
+  return ellipsoid_store_fast<64>(L, a, es, cov_g, logdet, logvol_out);
 }
 
-// NT = 128 (round 5): the leaves of a level at D >= 14 by two wavefronts each on the side stream, beside the level
-// kernels of the splittable nodes (a leaf is only read by k_finish); a node this kernel declines is queued for the
-// work-queue tail (`defer`), which runs after the side stream has joined.
-template <int NT>
-__global__ void __launch_bounds__(NT, 3) k_ell_wave(RebuildArgs a, int level, int G, int cap, int axis, int defer) {
+__global__ void __launch_bounds__(64, 3) k_ell_wave(RebuildArgs a, int level, int G) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   PH_LEVEL(-1);
   const int run = blockIdx.x % a.runs, g = blockIdx.x / a.runs;  // (run-minor, as k_ell)
@@ -3092,22 +2951,18 @@ __global__ void __launch_bounds__(NT, 3) k_ell_wave(RebuildArgs a, int level, in
   if (a.kerr[run] != DH_OK || a.status[run] != DH_OK) return;  // (k_ell, next on the stream, reports it)
   const int D = a.d, t = threadIdx.x;
   Lds L;
-  carve_wave(L, smem, D, cap, axis != 0);
+  carve_wave(L, smem, D);
   const RunView v = view_of(a, run, L.LD);
   for (int slot = g; slot < cnt; slot += G) {
     const int node = list[slot];
     const int start = v.nodes[node].start, count = v.nodes[node].count;
-    if (!v.nodes[node].has_mean || count < 2 || count > cap || (!axis && count >= 4 * D)) continue;
+    if (!v.nodes[node].has_mean || count < 2 || count > kWaveCap) continue;
     double lv = 0.0, fmx = INFINITY;
     __syncthreads();
     L.c_pts = nullptr;
-    const int rc = node_ellipsoid_wave<NT>(L, a, v.pts, v.perm, start, count, v.estore + (size_t)node * v.NS,
-                                           v.estore + (size_t)node * v.NS + v.ES, &lv, &fmx);
-    if (rc == kWaveDeclined) {
-      // (the node is untouched: fmax = inf, no record)
-      if (defer && t == 0) (void)tq_push(a, false, run, node, 1);
-      continue;
-    }
+    const int rc = node_ellipsoid_wave(L, a, v.pts, v.perm, start, count, v.estore + (size_t)node * v.NS,
+                                       v.estore + (size_t)node * v.NS + v.ES, &lv, &fmx);
+    if (rc == kWaveDeclined) continue;  // (the node is untouched: fmax = inf, no record)
     if (rc != DH_OK) {
       set_status(a, run, rc);
       return;
@@ -3133,7 +2988,7 @@ __device__ __attribute__((noinline)) void tree_split_item(const RebuildArgs& a, 
   const int D = a.d, t = threadIdx.x;
   Lds LS;
   carve_split(LS, smem, D, a.tps);
-  LS.coh = !a.tq_nocoh;
+  LS.coh = true;
   const RunView v = view_of(a, run, LS.LD);
   if (t < D) LS.scale[t] = a.scale_g[(size_t)run * D + t];
   __syncthreads();
@@ -3142,7 +2997,7 @@ __device__ __attribute__((noinline)) void tree_split_item(const RebuildArgs& a, 
 __device__ __attribute__((noinline)) void tree_ell_item(const RebuildArgs& a, unsigned char* smem, int run, int node) {
   Lds L;
   carve(L, smem, a.d);
-  L.coh = !a.tq_nocoh;
+  L.coh = true;
   const RunView v = view_of(a, run, L.LD);
   (void)ell_body<false>(a, L, v, run, 0, node);
 }
@@ -3150,6 +3005,7 @@ __device__ __attribute__((noinline)) void tree_ell_item(const RebuildArgs& a, un
 // (the item routines take the argument block by reference, so the worker keeps a copy of it on its stack: 476 bytes
 // per lane.  Behind a call the copy is made only by workers that have work: in the kernel's own prologue it was 58 MB
 // of scratch stores -- the whole 10 us of the empty-queue launch that every rebuild ends with.)
+constexpr int kTreeSleep = 8;  // s_sleep argument of a worker's poll of a slot not yet published
 __device__ __attribute__((noinline)) void tree_worker(RebuildArgs a, unsigned char* smem) {
   __shared__ unsigned long long s_item;
   const int t = threadIdx.x;
@@ -3164,7 +3020,7 @@ __device__ __attribute__((noinline)) void tree_worker(RebuildArgs a, unsigned ch
           it = __hip_atomic_load(a.tq_items + ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (it) break;
           if ((spins & 3) == 0 && __hip_atomic_load(a.tq_ctl + 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= 0) break;
-          for (int k = 0; k < a.tq_sleep; ++k) __builtin_amdgcn_s_sleep(8);
+          __builtin_amdgcn_s_sleep(kTreeSleep);
           if (++spins > (1ll << 22)) {  // a producer died: fail loudly instead of hanging the device
             __hip_atomic_store(a.tq_ctl + 48, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             break;
@@ -3195,14 +3051,6 @@ __global__ void __launch_bounds__(kThreads, 2) k_tree(RebuildArgs a) {
   tree_worker(a, smem);
 }
 
-// ---- small subtrees, one workgroup each (round 4) -----------------------------------------------------------
-// From the level where a child has a few hundred points the level pipeline is bound by workgroup slots and by its
-// kernel boundaries, not by work: the 64-run bench tree has 512 / 1 024 / 2 048 children of ~250 / 125 / 62 points at
-// levels 3-5, every level a k_split + k_ell pair of ~225 us in which a node waits for the slowest of its level twice.
-// A child that fits the 256-point tile cannot have a big descendant, so ONE workgroup takes its whole subtree --
-// ellipsoid, k-means of the whole node (no parts, no barrier between workgroups), the children's ellipsoids, ... --
-// depth first over a small stack, with the node routines of the level kernels (same arithmetic; the tile's
-// wavefronts are grouped like the 128-point parts, so a node's sums come out as the level kernels' would) and, as
 __global__ void __launch_bounds__(kThreads) k_finish(RebuildArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   PH_LEVEL(-1);
@@ -3905,29 +3753,18 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
   // 128 points per k-means part: five k_split workgroups per CU (see carve_split) -- or 256 where five 256-point
   // tiles fit a CU's LDS as well (D <= 13): half the parts to meet at the device-scope barrier.  Measured (round 5, 64
   // sets, tools/r5_tps.sh): eggbox 2-D 4.48 -> 4.10 ms, two blobs 5-D 0.720 -> 0.704; at D = 25 256-point parts lose
-  // (1.26 -> 1.40 ms: two workgroups per CU).  DH_SPLIT_TP overrides (64 .. 256)
+  // (1.26 -> 1.40 ms: two workgroups per CU).
   a.tps = split_lds_bytes(d, 256) * 5 <= kLdsLimit ? 256 : 128;
-  if (const char* e = getenv("DH_SPLIT_TP")) {
-    const int v = atoi(e);
-    if (v == 64 || v == 128 || v == 192 || v == 256) a.tps = v;
-  }
   a.maxp = n / a.tps + a.maxw + 1;
   // eigen-free tree nodes (MultiEllipsoid.update only: Ellipsoid.update's single node IS the output)
-  a.fast = mode == 0 ? 1 : 0;
-  if (const char* e = getenv("DH_REBUILD_FAST")) a.fast = a.fast && atoi(e) != 0;  // diagnostic: 0 = eigh on every node
+  a.fast = mode == 0 && env_int("DH_REBUILD_FAST", 1) != 0 ? 1 : 0;  // diagnostic: 0 = eigh on every node
   // The tree is built by the level pipeline (k_split / k_ell per level) for a balanced tree's depth (lv levels: an
   // idle level pair costs 10 us, and the bench trees use lv = 6 exactly);
   // whatever is deeper -- unbalanced splits -- is handed to persistent workers on a work queue (k_tree: the same
   // node routines, any depth, any node size; in the common case it finds its queue empty and leaves).
-  // DH_TREE=1: the WHOLE tree by the work-queue form.  Bit-identical results (tests/test_gpu_edges.py), but
-  // measured SLOWER (round 3, 20 launches each): 64 C2 runs 1.44 vs 1.29 ms, 16 runs 1.06 vs 0.95, 16 eggbox
-  // runs 2.37 vs 2.15, one eggbox run 1.20 vs 0.99.  With 64 runs the chip is saturated either way (the time
-  // scales with the number of workers: 256 -> 2.18 ms, 384 -> 1.68, 512 -> 1.52), and the queue form loses the
-  // level pipeline's five k_split workgroups per CU (its workers carry the 77 KB layout of the ellipsoid routine:
-  // two per CU), pays agent-scope (cache-bypassing) accesses for everything a node hands to the next, and leaves
-  // the early parts of a multi-part node spinning until the late ones find a worker.
-  a.tree = 0;
-  if (const char* e = getenv("DH_TREE")) a.tree = a.fast && atoi(e) != 0;
+  // (The WHOLE tree by the work-queue form, DH_DEEP_FROM=0, gives the same bits but was measured slower in round 3:
+  // 64 C2 runs 1.44 against 1.29 ms -- it loses the level pipeline's five k_split workgroups per CU.)
+  a.tree = 0;  // (1 in k_tree's copy of the arguments only)
   // level kernels for a balanced tree's depth, the work-queue tail for the rest (DH_DEEP=0: every level
   // by level kernels and no tail, as does the diagnostic slow mode; DH_DEEP_FROM=f: the tail takes over at level f)
   // (one level pair fewer -- a balanced tree's last split level is the one with n >> L >= 4 d: five pairs for the
@@ -3935,13 +3772,12 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
   // 64-run rebuild, eggbox 5.02 against 4.51: real trees are not balanced, and what is deeper than the level kernels
   // goes to the work-queue tail, which costs more than an almost idle level pair)
   int nlev = a.levels;
-  if (a.fast && !(getenv("DH_DEEP") && atoi(getenv("DH_DEEP")) == 0)) nlev = a.levels < lv ? a.levels : lv;
-  if (a.fast && getenv("DH_DEEP_FROM")) {
-    const int f = atoi(getenv("DH_DEEP_FROM"));
-    if (f >= 1 && f < a.levels) nlev = f;
+  if (a.fast && env_int("DH_DEEP", 1) != 0) nlev = a.levels < lv ? a.levels : lv;
+  if (a.fast) {
+    const int f = env_int("DH_DEEP_FROM", -1);
+    if (f >= 0 && f < a.levels) nlev = f;
   }
-  if (a.tree) nlev = 0;
-  const bool tail = a.fast && (a.tree || nlev < a.levels);
+  const bool tail = a.fast && nlev < a.levels;
   a.tree_from = tail ? nlev : a.levels + 1;
   a.tq_cap = 0;
   a.kp_cap = 0;
@@ -4012,21 +3848,15 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
   // single-workgroup root, 447 us against 81 us per 64 runs).
   int rp = n > 1 ? (n + kThreads - 1) / kThreads : 1;
   if (rp > cap_root || (ctx->coop_launch && (long long)runs * rp > cap_root)) rp = 1;
+  if (env_int("DH_ROOT_PARTS", 1) == 0) rp = 1;  // diagnostic: the single-workgroup root for every run
   int root_chunk = runs;
   if (rp > 1 && (long long)runs * rp > cap_root) root_chunk = cap_root / rp;
-  if (getenv("DH_ROOT_ONE_LAUNCH") && atoi(getenv("DH_ROOT_ONE_LAUNCH")) == 1 && !ctx->coop_launch)
-    root_chunk = runs;  // experiment: one launch, run-major ids, relying on in-order dispatch as k_split's chunks do
-  if (getenv("DH_ROOT_CHUNK") && atoi(getenv("DH_ROOT_CHUNK")) == 0) {  // diagnostic: the form before
-    root_chunk = runs;
-    if ((long long)runs * rp > cap_root) rp = 1;
-  }
   if (mode == 0 && (n + a.tps - 1) / a.tps > cap_split)
     return fail(ctx, DH_ERR_ARG, "rebuild: the %d parts of a %d-point node exceed the %d co-resident workgroups of k_split",
                 (n + a.tps - 1) / a.tps, n, cap_split);
-  if (getenv("DH_ROOT_PARTS") && atoi(getenv("DH_ROOT_PARTS")) == 0) rp = 1;  // diagnostic
-  // zeroed counters: nnodes | nsplit (levels+1) | nell (levels) | nparts (levels+1) | kerr | rbar | kbar (levels x maxw)
+  // zeroed counters: nnodes | nsplit (levels+1) | nell (levels) | nparts (levels+1) | kerr | kbar (levels x maxw)
   // ... | kp_top (runs) | tq_ctl (64) | nbar (runs x max_nodes x kBarStride) | tq_items (tq_cap x 2 ints)   [k_tree]
-  const size_t n_cnt_old = (size_t)runs * ((size_t)3 * a.levels + 5 + kBarStride + (size_t)a.levels * a.maxw * kBarStride);
+  const size_t n_cnt_old = (size_t)runs * ((size_t)3 * a.levels + 5 + (size_t)a.levels * a.maxw * kBarStride);
   const size_t n_cnt_tree = tail ? (size_t)runs + 64 + (size_t)runs * a.max_nodes * kBarStride + 2 * (size_t)a.tq_cap + 2 : 0;
   const size_t b_cnt = (n_cnt_old + n_cnt_tree) * 4;
   a.rootbuf_stride = 2 * ((size_t)rp * (2 * (size_t)d + (size_t)d * d + 1) + (size_t)d * d + 8);  // (value, tag) pairs
@@ -4075,8 +3905,7 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
   a.nell = a.nsplit + (size_t)(a.levels + 1) * runs;
   a.nparts = a.nell + (size_t)a.levels * runs;
   a.kerr = a.nparts + (size_t)(a.levels + 1) * runs;
-  a.rbar = a.kerr + runs;
-  a.kbar = a.rbar + (size_t)runs * kBarStride;
+  a.kbar = a.kerr + runs;
   a.kp_top = a.nbar = a.tq_ctl = nullptr;
   a.tq_items = nullptr;
   if (tail) {
@@ -4132,9 +3961,9 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
   a.active = active;
   a.n_arr = n_arr;
   a.epoch = ++ctx->rebuild_epoch;
-  // k_ell's top levels: a tile of 512 points, if it fits (D <= 30); DH_ELL_TOP_TILE=0: off
+  // k_ell's top levels: a tile of 512 points, if it fits (D <= 30)
   size_t lds_top = rebuild_lds_bytes(d, 2 * kThreads);
-  if (lds_top > kLdsLimit || mode != 0 || (getenv("DH_ELL_TOP_TILE") && atoi(getenv("DH_ELL_TOP_TILE")) == 0)) lds_top = 0;
+  if (lds_top > kLdsLimit || mode != 0) lds_top = 0;
   DH_DEV_MEMO(attr_lds);
   DH_DEV_MEMO(attr_top);
   if (lds > attr_lds) {
@@ -4174,13 +4003,12 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
   }
   a.root_run0 = 0;
   bool forked = false;
-  if (a.fast && !(getenv("DH_ROOT_EIG_SIDE") && atoi(getenv("DH_ROOT_EIG_SIDE")) == 0)) {
+  if (a.fast) {
     if (!ctx->side_stream) {
-      // lowest priority: what runs here (the root's eigen-system, the leaves) is off the critical path and must not
+      // lowest priority: what runs here (the root's eigen-system) is off the critical path and must not
       // take workgroup slots / LDS from the level kernels that are ready at the same moment
       int pr_lo = 0, pr_hi = 0;
       (void)hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);
-      if (getenv("DH_SIDE_PRIO") && atoi(getenv("DH_SIDE_PRIO")) == 0) pr_lo = 0;
       if (!hip_ok(ctx, hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, pr_lo), "hipStreamCreate(side)") ||
           !hip_ok(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming), "hipEventCreate") ||
           !hip_ok(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming), "hipEventCreate"))
@@ -4192,70 +4020,19 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
     hipLaunchKernelGGL(k_root_eig, dim3(runs), dim3(kThreads), lds, ctx->side_stream, a);
     if (!hip_ok(ctx, hipEventRecord(ctx->ev_join, ctx->side_stream), "hipEventRecord(join)")) return DH_ERR_HIP;
     forked = true;
-  } else {
-    a.root_eig = nullptr;
   }
   // small nodes by one wavefront each (k_ell_wave), from the level where the average child fits -- where eight such
-  // nodes (128-point tile, four D x D matrices) share a CU's LDS: D <= 13.  Measured (tools/wave_ell_ab.py, 64 sets):
-  // eggbox 2-D 6.54 -> 4.67 ms, two blobs 5-D 0.91 -> 0.75, 3-D blob 0.71 -> 0.62.  At D = 25 the leaves-only form
-  // LOSES (1.29 -> 1.41 ms: 39 point loads and 13 matrix rows per lane and sweep outweigh the rounds saved), so
-  // above D = 13 it is off.  DH_WAVE_ELL=0: off; =1: leaves only; =2: with the axis, at any D that fits 64 KB.
-  int wave_from = nlev, wave_cap = 0, wave_axis = 0;
-  size_t lds_wave = 0;
-  if (a.fast) {
-    const char* e = getenv("DH_WAVE_ELL");
-    const int mode_w = e ? atoi(e) : -1;
-    if (mode_w != 0) {
-      wave_cap = 128;
-      const bool fits8 = wave_lds_bytes(d, wave_cap, true) * 8 <= kLdsLimit;
-      wave_axis = mode_w == 2 || (mode_w < 0 && fits8) ? 1 : 0;
-      if (!wave_axis) wave_cap = 4 * d - 1 < 128 ? 4 * d - 1 : 128;
-      lds_wave = wave_lds_bytes(d, wave_cap, wave_axis != 0);
-      if ((mode_w > 0 || fits8) && wave_cap >= 2 && lds_wave <= 64 * 1024) {
-        wave_from = 0;
-        while (wave_from < nlev && (n >> (wave_from + 1)) > 2 * wave_cap) ++wave_from;
-      }
-    }
+  // nodes (128-point tile, four D x D matrices) share a CU's LDS: D <= 13.  Measured (round 5, 64 sets): eggbox 2-D
+  // 6.54 -> 4.67 ms, two blobs 5-D 0.91 -> 0.75, 3-D blob 0.71 -> 0.62; above D = 13 the forms tried lost (1.29 -> 1.41
+  // ms at D = 25).  DH_WAVE_ELL=0: off.
+  int wave_from = nlev;
+  const size_t lds_wave = wave_lds_bytes(d);
+  if (a.fast && env_int("DH_WAVE_ELL", 1) != 0 && lds_wave * 8 <= kLdsLimit) {
+    wave_from = 0;
+    while (wave_from < nlev && (n >> (wave_from + 1)) > 2 * kWaveCap) ++wave_from;
   }
-  // Leaves beside the tree (round 5).  A child too small to be split again (count < 4 d) is read by nothing but
-  // k_finish, yet the level kernels built it on the critical path: the 2 048 leaves of the 64-run bench tree's last busy
-  // level are four rounds of k_ell's 512 workgroup slots (150 us).  Above D = 13 (below, k_ell_wave's one-wavefront form
-  // with the axis serves on the main stream) the leaves of the levels whose average child is leaf-sized go to
-  // k_ell_wave<128> on the SIDE stream -- two wavefronts and 31 KB of LDS a node: five per CU -- while the main stream
-  // goes on with the level's few splittable children and the next level pair; k_ell skips exactly the nodes that kernel
-  // takes.  The side stream joins before the work-queue tail, to which a declined leaf (eigen-free path not applicable)
-  // is queued.  Same routines, same bits (tests/test_gpu_edges.py).  Round 6: with the level kernels a third shorter the
-  // side stream no longer pays -- measured on the bench shard (tools/r6_env.sh): 64 runs 1.065 ms either way, one run
-  // 0.70 -> 0.66 and 128 runs 2.05 -> 2.01 WITHOUT it (two more event waits per level, five 31 KB leaf workgroups per
-  // CU beside the level's own) -- so it is off by default; DH_LEAF_SIDE=1 switches it on.
-  // Round 6, second half: the leaves by a light kernel of their own on the MAIN stream (DH_LEAF_MAIN=1; measured and
-  // left off).  A leaf needs neither the axis nor a second tile: k_ell_wave<256> -- the same routines with four
-  // wavefronts, a carve of the tile (4 d - 1 points) and two matrices, 31 KB instead of k_ell's 77 -- in front of the
-  // level's k_ell, which skips what it takes.  The 2 048 leaves of the 64-run bench tree's last busy level are four
-  // rounds of k_ell's two workgroups per CU (112 us); the light kernel took 90 us for them (its wave-by-wave fold, 20
-  // spilled registers at the 168 of three workgroups per CU) and k_ell another 56 for the level's splittable children:
-  // 1.04 -> 1.09 ms per 64 runs.
-  int leaf_from = nlev, leaf_cap = 0;
-  size_t lds_leaf = 0;
-  const bool leaf_side = getenv("DH_LEAF_SIDE") && atoi(getenv("DH_LEAF_SIDE")) == 1;
-  const bool leaf_main = !leaf_side && getenv("DH_LEAF_MAIN") && atoi(getenv("DH_LEAF_MAIN")) == 1;
-  if (a.fast && mode == 0 && tail && (forked || leaf_main) && wave_from >= nlev && d >= 14 && (leaf_side || leaf_main)) {
-    leaf_cap = 4 * d - 1 < 128 ? 4 * d - 1 : 128;
-    lds_leaf = wave_lds_bytes(d, leaf_cap, false);
-    if (lds_leaf <= 64 * 1024) {
-      // from the level whose average child is below 3 d points ... (n >> (L + 1)) < 4 d would start a level earlier,
-      // where most children are still splittable
-      leaf_from = 0;
-      int lf = 3 * d;
-      if (const char* e = getenv("DH_LEAF_FROM_PTS")) lf = atoi(e) > 0 ? atoi(e) : lf;
-      while (leaf_from < nlev && (n >> (leaf_from + 1)) >= lf) ++leaf_from;
-      if (!ctx->ev_leaf && !hip_ok(ctx, hipEventCreateWithFlags(&ctx->ev_leaf, hipEventDisableTiming), "hipEventCreate"))
-        return DH_ERR_HIP;
-    } else {
-      leaf_cap = 0;
-    }
-  }
-  bool side_leaves = false;
+  // (Leaves built beside the level kernels -- on the side stream, or by a light kernel of their own on the main
+  // stream -- were measured no better in round 6: EXPERIMENTS.md.)
   for (int L = 0; L < nlev; ++L) {
     // Grids no larger than the level can need (round 5): level L splits at most 2^L nodes of a run -- at most
     // n / tps + 2^L parts -- and creates at most 2^(L + 1) children.  Workgroups are dispatched at a finite rate: the
@@ -4269,72 +4046,41 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
     // (ONE context per GPU is assumed, as for k_root_parts: a second process -- or a long-lived foreign kernel -- can
     // hold slots this sizing counts on; DH_SPLIT_RESIDENT_PCT lowers the share of the chip a chunk may claim (87 by
     // default, e.g. 40 on a GPU shared by two processes), and the spin limit fails a starved run instead of hanging)
-    static const int resident_pct = [] {
-      const char* e = getenv("DH_SPLIT_RESIDENT_PCT");
-      const int v = e ? atoi(e) : 0;
-      return v >= 1 && v <= 100 ? v : 87;
-    }();
     // (round 6) no more k_ell / k_ell_wave workgroups than a few rounds of the chip: a workgroup takes every ge-th child
     // of its run (the kernels' own loops).  The bound above is the worst case; a many-mode tree's deep level (eggbox 2-D,
     // nlive 5 000, 16 runs: 1 065 parts and 1 252 children possible per run, some 200 there) was 20 000 workgroups of
     // which a fifth found work, and the dispatch of the rest half the level's time.
-    const int grid_cap = getenv("DH_LEVEL_GRID_CAP") ? atoi(getenv("DH_LEVEL_GRID_CAP")) : 1;
-    const int split_room = cap_split_level > 0 ? (int)((long long)cap_split_level * resident_pct / 100) : 1;
-    const int gp_l = gp;  // (k_split keeps the worst case: a loop over parts in it costs registers it does not have --
-                          // 5 spilled VGPRs -- and, where the parts are real, serialises two k-means chains)
-    int ge_l = ge, gw_l = ge;
-    if (grid_cap > 0) {
-      const int cap_ell = 2 * ctx->num_cu;  // (k_ell: two workgroups per CU)
-      const int want_e = 8 * cap_ell / runs > 1 ? 8 * cap_ell / runs : 1;
-      if (want_e < ge_l) ge_l = want_e;
-      // (k_ell_wave: 16 384 one-wavefront workgroups; 8 192 / 4 096 / 2 048 measured on the C3 loop: 0.088 / 0.089 / 0.089 s
-      // against 0.087 -- its time is its nodes, not its dispatch)
-      const int want_w = 16384 / runs > 1 ? 16384 / runs : 1;
-      if (want_w < gw_l) gw_l = want_w;
-    }
-    int cr = cap_split_level > 0 ? split_room / gp_l : 1;
+    const int split_room = cap_split_level > 0 ? (int)((long long)cap_split_level * ctx->split_resident_pct / 100) : 1;
+    // (k_split keeps the worst case gp: a loop over parts in it costs registers it does not have -- 5 spilled VGPRs --
+    // and, where the parts are real, serialises two k-means chains)
+    const int cap_ell = 2 * ctx->num_cu;  // (k_ell: two workgroups per CU)
+    const int want_e = 8 * cap_ell / runs > 1 ? 8 * cap_ell / runs : 1;
+    const int ge_l = want_e < ge ? want_e : ge;
+    // (k_ell_wave: 16 384 one-wavefront workgroups; 8 192 / 4 096 / 2 048 measured on the C3 loop: 0.088 / 0.089 / 0.089 s
+    // against 0.087 -- its time is its nodes, not its dispatch)
+    const int want_w = 16384 / runs > 1 ? 16384 / runs : 1;
+    const int gw_l = want_w < ge ? want_w : ge;
+    int cr = cap_split_level > 0 ? split_room / gp : 1;
     cr = cr < 1 ? 1 : (cr > runs ? runs : cr);
     const int nchunk = (runs + cr - 1) / cr;
     cr = (runs + nchunk - 1) / nchunk;  // (chunks of equal size)
-    hipLaunchKernelGGL(k_split, dim3(nchunk * cr * gp_l), dim3(kThreads), lds_split, ctx->stream, a, L, gp_l, cr);
+    hipLaunchKernelGGL(k_split, dim3(nchunk * cr * gp), dim3(kThreads), lds_split, ctx->stream, a, L, gp, cr);
     const int wave = L >= wave_from ? 1 : 0;
-    if (L >= wave_from)
-      hipLaunchKernelGGL(k_ell_wave<64>, dim3(runs * gw_l), dim3(64), lds_wave, ctx->stream, a, L, gw_l,
-                         wave_cap, wave_axis, 0);
-    const int lc = (leaf_cap > 0 && L >= leaf_from) ? leaf_cap : 0;
-    if (lc && leaf_main)
-      hipLaunchKernelGGL(k_ell_wave<256>, dim3(runs * ge), dim3(256), lds_leaf, ctx->stream, a, L, ge, leaf_cap, 0, 1);
-    if (lc && leaf_side && !hip_ok(ctx, hipEventRecord(ctx->ev_leaf, ctx->stream), "hipEventRecord(leaf fork)")) return DH_ERR_HIP;
+    if (wave) hipLaunchKernelGGL(k_ell_wave, dim3(runs * gw_l), dim3(64), lds_wave, ctx->stream, a, L, gw_l);
     // The top levels' children are several 256-point tiles each and few (one workgroup per CU or less): their
     // workgroups stage 512 points at once -- a 1 000-point child is gathered three times instead of seven (covariance
     // pass 2 + Mahalanobis pass 1, the last tile still staged), a 500-point child once instead of three times.  Only
-    // while the level's workgroups all fit the chip at one per CU (the LDS of such a tile allows no second one).
-    // (round 6: only while the level's workgroups fill at most HALF the CUs -- at 128 runs level 0's 256 one-per-CU
-    // workgroups with the big tile lost to two-per-CU with the small one: 2.09 -> 2.05 ms; 64 runs unchanged)
-    static const int top_div = getenv("DH_ELL_TOP_DIV") ? atoi(getenv("DH_ELL_TOP_DIV")) : 2;
-    const bool top = lds_top > 0 && (n >> (L + 1)) > kThreads && (long long)runs * ge * (top_div > 0 ? top_div : 1) <= ctx->num_cu;
-    if (a.fast && tail && !(getenv("DH_ELL_DEFER") && atoi(getenv("DH_ELL_DEFER")) == 0))
-      hipLaunchKernelGGL((k_ell<false, true>), dim3(runs * ge_l), dim3(kThreads), top ? lds_top : lds, ctx->stream, a, L, ge_l, wave, lc,
-                         top ? 2 * kThreads : kThreads);
+    // while the level's workgroups fill at most HALF the CUs (round 6: at 128 runs level 0's 256 one-per-CU workgroups
+    // with the big tile lost to two-per-CU with the small one, 2.09 -> 2.05 ms; the LDS of such a tile allows no second one).
+    const bool top = lds_top > 0 && (n >> (L + 1)) > kThreads && 2ll * runs * ge <= ctx->num_cu;
+    const size_t lds_ell = top ? lds_top : lds;
+    const int tp = top ? 2 * kThreads : kThreads;
+    if (a.fast && tail)
+      hipLaunchKernelGGL((k_ell<false, true>), dim3(runs * ge_l), dim3(kThreads), lds_ell, ctx->stream, a, L, ge_l, wave, tp);
     else if (a.fast)
-      hipLaunchKernelGGL(k_ell<false>, dim3(runs * ge_l), dim3(kThreads), top ? lds_top : lds, ctx->stream, a, L, ge_l, wave, lc,
-                         top ? 2 * kThreads : kThreads);
+      hipLaunchKernelGGL(k_ell<false>, dim3(runs * ge_l), dim3(kThreads), lds_ell, ctx->stream, a, L, ge_l, wave, tp);
     else
-      hipLaunchKernelGGL(k_ell<true>, dim3(runs * ge), dim3(kThreads), top ? lds_top : lds, ctx->stream, a, L, ge, 0, 0,
-                         top ? 2 * kThreads : kThreads);
-    if (lc && leaf_side) {  // (submitted after the level's k_ell: its few splittable children should get their slots first)
-      if (!hip_ok(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_leaf, 0), "hipStreamWaitEvent(leaf fork)"))
-        return DH_ERR_HIP;
-      hipLaunchKernelGGL(k_ell_wave<128>, dim3(runs * ge), dim3(128), lds_leaf, ctx->side_stream, a, L, ge,
-                         leaf_cap, 0, 1);
-      side_leaves = true;
-    }
-  }
-  if (side_leaves) {  // the join moves behind the leaves (k_root_eig is long done) and in front of the tail
-    if (!hip_ok(ctx, hipEventRecord(ctx->ev_join, ctx->side_stream), "hipEventRecord(join)") ||
-        !hip_ok(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)"))
-      return DH_ERR_HIP;
-    forked = false;
+      hipLaunchKernelGGL(k_ell<true>, dim3(runs * ge), dim3(kThreads), lds_ell, ctx->stream, a, L, ge, 0, tp);
   }
   if (tail) {
     // persistent workers: as many as can be resident (the parts of a node meet at spin barriers), but
@@ -4343,41 +4089,8 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
     at.tree = 1;
     at.kpart = kpart_tail;
     at.maxp = a.kp_cap;
-    long long want = (long long)runs * (n / a.tps + 2 * a.maxw + 1);
-    int G = (int)(want < cap_tree ? (want < 1 ? 1 : want) : cap_tree);
-    if (const char* e = getenv("DH_TREE_G")) G = atoi(e) > 0 ? atoi(e) : G;
-    at.tq_sleep = getenv("DH_TREE_SLEEP") ? atoi(getenv("DH_TREE_SLEEP")) : 1;
-    at.tq_nocoh = getenv("DH_TREE_NOCOH") ? atoi(getenv("DH_TREE_NOCOH")) : 0;
-    if (getenv("DH_TREE_STATS")) {  // diagnostic: what the level kernels left for the work-queue tail (a sync per rebuild)
-      int q[64];
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipMemcpy(q, at.tq_ctl, sizeof q, hipMemcpyDeviceToHost);
-      const int nq = q[16] > 0 ? (q[16] < a.tq_cap ? q[16] : a.tq_cap) : 0;
-      std::vector<unsigned long long> items((size_t)nq + 1);
-      if (nq > 0) (void)hipMemcpy(items.data(), at.tq_items, (size_t)nq * 8, hipMemcpyDeviceToHost);
-      int nsplit = 0, nell = 0;
-      for (int i = 0; i < nq; ++i) (items[i] & kItemSplit ? nsplit : nell) += 1;
-      {  // sizes and depths of the declined nodes
-        std::vector<Node> nd((size_t)runs * a.max_nodes);
-        (void)hipMemcpy(nd.data(), a.nodes, nd.size() * sizeof(Node), hipMemcpyDeviceToHost);
-        int hist_depth[16] = {0}, cmin = 1 << 30, cmax = 0;
-        long long csum = 0;
-        for (int i = 0; i < nq; ++i)
-          if (!(items[i] & kItemSplit)) {
-            const int r = (int)((items[i] >> 40) & 0x3fffff), nn = (int)((items[i] >> 16) & 0xffffff);
-            const Node& x = nd[(size_t)r * a.max_nodes + nn];
-            hist_depth[x.depth < 15 ? x.depth : 15] += 1;
-            cmin = x.count < cmin ? x.count : cmin;
-            cmax = x.count > cmax ? x.count : cmax;
-            csum += x.count;
-          }
-        if (nell)
-          fprintf(stderr, "  declined nodes: count %d .. %d (mean %.0f); by depth 1..6: %d %d %d %d %d %d\n", cmin, cmax, (double)csum / nell,
-                  hist_depth[1], hist_depth[2], hist_depth[3], hist_depth[4], hist_depth[5], hist_depth[6]);
-      }
-      fprintf(stderr, "rebuild tail: %d items queued by the level kernels (%d runs, n %d, d %d, %d levels): %d ellipsoids (declined by the "
-              "eigen-free path) + %d k-means parts (deeper than the level plan)\n", nq, runs, n, d, nlev, nell, nsplit);
-    }
+    const long long want = (long long)runs * (n / a.tps + 2 * a.maxw + 1);
+    const int G = (int)(want < cap_tree ? (want < 1 ? 1 : want) : cap_tree);
     hipLaunchKernelGGL(k_tree, dim3(G), dim3(kThreads), lds, ctx->stream, at);
   }
   if (forked && !hip_ok(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)")) return DH_ERR_HIP;

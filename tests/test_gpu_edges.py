@@ -169,22 +169,25 @@ def test_cooperative_root_threshold_follows_the_occupancy(ctx):
 
 
 def test_work_queue_tree_equals_the_level_kernels(ctx):
-    """The work-queue form of the tree (DH_TREE=1: persistent workers on one FIFO queue, no levels -- a node's
-    k-means is queued when its ellipsoid exists, its children when its last part has partitioned; built in
-    round 3, measured slower than the level pipeline and therefore not the default) runs the level kernels'
-    node routines, so it must reproduce the level pipeline bit for bit: single live sets and a ragged batch."""
+    """The whole tree by the work-queue form (DH_DEEP_FROM=0: persistent workers on one FIFO queue, no level
+    kernels -- a node's k-means is queued when its ellipsoid exists, its children when its last part has
+    partitioned; measured slower than the level pipeline in round 3 and therefore not the default) runs the level
+    kernels' node routines, so it must reproduce the level pipeline bit for bit: single live sets and a ragged batch."""
     import os
 
     def run(fn, tree):
-        old = os.environ.get("DH_TREE")
-        os.environ["DH_TREE"] = "1" if tree else "0"
+        old = os.environ.get("DH_DEEP_FROM")
+        if tree:
+            os.environ["DH_DEEP_FROM"] = "0"
+        else:
+            os.environ.pop("DH_DEEP_FROM", None)
         try:
             return fn()
         finally:
             if old is None:
-                os.environ.pop("DH_TREE", None)
+                os.environ.pop("DH_DEEP_FROM", None)
             else:
-                os.environ["DH_TREE"] = old
+                os.environ["DH_DEEP_FROM"] = old
     many = 0
     for name in ("c2", "c3", "two5", "ring2", "flat10", "small4", "egg13", "c2s"):
         pts = inputs.cloud(name)
@@ -217,8 +220,8 @@ def test_work_queue_tail_equals_the_level_kernels(ctx):
              (inputs.cloud("ring2"), ("5", "7"))]
 
     def run(pts, env):
-        old = {k: os.environ.get(k) for k in ("DH_DEEP", "DH_DEEP_FROM", "DH_TREE")}
-        os.environ.update(dict(env, DH_TREE="0"))  # the level pipeline
+        old = {k: os.environ.get(k) for k in ("DH_DEEP", "DH_DEEP_FROM")}
+        os.environ.update(env)
         try:
             return ctx.rebuild(pts, multi=True, want_labels=True)
         finally:
@@ -242,8 +245,8 @@ def test_work_queue_tail_equals_the_level_kernels(ctx):
 def test_one_wavefront_per_small_node_gives_the_same_bits(ctx):
     """k_ell_wave builds the small nodes of the deep levels with one wavefront each (the same routines instantiated
     for 64 threads, the covariance contraction with k_ell's four waves played in turn): which kernel builds a node is
-    a scheduling decision, so every output must be bit-identical with it off (DH_WAVE_ELL=0), on by default
-    (D <= 13), leaves only (=1) and with the major axis at any D (=2) -- single live sets and a batch."""
+    a scheduling decision, so every output must be bit-identical with it off (DH_WAVE_ELL=0) and on by default
+    (D <= 13) -- single live sets and a batch."""
     import os
     clouds = [inputs.cloud(n) for n in ("c3", "two5", "ring2", "g3", "egg13", "c2", "flat10", "small4")]
 
@@ -264,11 +267,10 @@ def test_one_wavefront_per_small_node_gives_the_same_bits(ctx):
     for pts in clouds:
         ref = run(pts, "0")
         many += ref["nells"] > 4
-        for env in (None, "1", "2"):
-            got = run(pts, env)
-            assert ref["nells"] == got["nells"] and ref["nnodes"] == got["nnodes"], env
-            for k in FIELDS + ("labels",):
-                np.testing.assert_array_equal(ref[k], got[k])
+        got = run(pts, None)
+        assert ref["nells"] == got["nells"] and ref["nnodes"] == got["nnodes"]
+        for k in FIELDS + ("labels",):
+            np.testing.assert_array_equal(ref[k], got[k])
     assert many >= 3
     # a batch of permuted eggbox live sets (the rounds of workgroup slots are what the wave form is for)
     c3 = inputs.cloud("c3")
@@ -312,12 +314,11 @@ def test_unbalanced_tree_deeper_than_the_level_plan(ctx):
     assert m.nells == got["nells"]
 
 
-def test_leaves_on_the_side_stream_give_the_same_bits(ctx):
-    """Round 5: above D = 13 the leaves of the deep levels (count < 4 d: read by nothing but the accept test) are
-    built by k_ell_wave<128> on the side stream beside the level kernels, and a leaf its eigen-free path declines is
-    queued for the work-queue tail.  Which kernel builds a node is a scheduling decision: every output bit-identical
-    with it off (DH_LEAF_SIDE=0) -- blobs whose leaves are healthy, blobs whose leaves are DEGENERATE (duplicated
-    points, clusters confined to a plane: the declined route), single live sets and a batch."""
+def test_declined_leaves_give_the_same_bits_as_the_level_kernels(ctx):
+    """Above D = 13 the level kernel's eigen-free form (k_ell<false, true>) queues a node its eigen-free path declines
+    for the work-queue tail; with the level kernels alone (DH_DEEP=0) k_ell takes the reference's route in place.
+    Every output bit-identical either way -- blobs whose leaves are healthy, blobs whose leaves are DEGENERATE
+    (duplicated points, clusters confined to a plane: the declined route), single live sets and a batch."""
     import os
     rng = np.random.default_rng(11)
     d = 16
@@ -335,20 +336,22 @@ def test_leaves_on_the_side_stream_give_the_same_bits(ctx):
             parts.append(x)
         pts = np.concatenate(parts)
         return pts[rng.permutation(len(pts))]
-    # 16 blobs of ~40 points at d = 16: the leaves (count < 4 d = 64) sit at level 3, the first level whose average
-    # child is below 3 d points, i.e. the level the side-stream kernel takes
+    # 16 blobs of ~40 points at d = 16: the leaves (count < 4 d = 64) sit at level 3
     clouds = [blobs(16, 40, "healthy"), blobs(16, 39, "dup"), blobs(16, 40, "plane"), inputs.cloud("c2")]
 
-    def run(pts, off):
-        old = os.environ.get("DH_LEAF_SIDE")
-        os.environ["DH_LEAF_SIDE"] = "0" if off else "1"  # (round 6: the side stream is opt-in)
+    def run(pts, levels_only):
+        old = os.environ.get("DH_DEEP")
+        if levels_only:
+            os.environ["DH_DEEP"] = "0"
+        else:
+            os.environ.pop("DH_DEEP", None)
         try:
             return ctx.rebuild(pts, multi=True, want_labels=True)
         finally:
             if old is None:
-                os.environ.pop("DH_LEAF_SIDE", None)
+                os.environ.pop("DH_DEEP", None)
             else:
-                os.environ["DH_LEAF_SIDE"] = old
+                os.environ["DH_DEEP"] = old
     for pts in clouds:
         ref, got = run(pts, True), run(pts, False)
         assert ref["nells"] == got["nells"] and ref["nnodes"] == got["nnodes"]
@@ -357,13 +360,12 @@ def test_leaves_on_the_side_stream_give_the_same_bits(ctx):
     assert run(clouds[0], False)["nells"] >= 5
     # a batch: 16 permutations of the degenerate cloud (declined leaves of many runs in one queue)
     sets = [clouds[1][np.random.default_rng(r).permutation(len(clouds[1]))] for r in range(16)]
-    os.environ["DH_LEAF_SIDE"] = "0"
+    got = ctx.rebuild_many(sets, multi=True)
+    os.environ["DH_DEEP"] = "0"
     try:
         ref = ctx.rebuild_many(sets, multi=True)
-        os.environ["DH_LEAF_SIDE"] = "1"
-        got = ctx.rebuild_many(sets, multi=True)
     finally:
-        del os.environ["DH_LEAF_SIDE"]
+        del os.environ["DH_DEEP"]
     for a, b in zip(ref, got):
         assert a["nells"] == b["nells"]
         for k in a:
@@ -373,17 +375,17 @@ def test_leaves_on_the_side_stream_give_the_same_bits(ctx):
 def test_root_of_more_runs_than_fit_at_once_goes_in_chunks_with_the_same_bits(ctx):
     """Round 6: the cooperative root (k_root_parts: ceil(n / 256) workgroups per run that meet at spin waits) needs
     its workgroups co-resident; 144 runs x 8 parts do not fit the 512 slots, so the runs go in chunks of 64 -- same
-    bits as the single-workgroup root the launcher fell back to before (DH_ROOT_CHUNK=0) and as 144 separate calls'
-    first runs."""
+    bits as the single-workgroup root for every run (DH_ROOT_PARTS=0, what the launcher fell back to before) and as
+    144 separate calls' first runs."""
     import os
     base = inputs.cloud("c2")
     sets = [base[np.random.default_rng(r).permutation(len(base))] for r in range(144)]
     got = ctx.rebuild_many(sets, multi=True)
-    os.environ["DH_ROOT_CHUNK"] = "0"
+    os.environ["DH_ROOT_PARTS"] = "0"
     try:
         ref = ctx.rebuild_many(sets, multi=True)
     finally:
-        del os.environ["DH_ROOT_CHUNK"]
+        del os.environ["DH_ROOT_PARTS"]
     assert len(got) == len(ref) == 144
     for a, b in zip(ref, got):
         assert a["nells"] == b["nells"] and a["nells"] >= 1
@@ -397,19 +399,16 @@ def test_root_of_more_runs_than_fit_at_once_goes_in_chunks_with_the_same_bits(ct
 
 def test_capped_level_grids_give_the_same_bits(ctx):
     """Round 6: k_ell / k_ell_wave are launched with at most a few rounds of the chip's workgroup slots and loop over
-    their run's children (DH_LEVEL_GRID_CAP=0: the worst-case grids).  A many-mode cloud in two dimensions -- hundreds of
-    small nodes per level, the shape the cap is for -- in a batch large enough for the cap to bind: every output the same."""
-    import os
+    their run's children.  A many-mode cloud in two dimensions -- hundreds of small nodes per level, the shape the cap
+    is for -- in a batch large enough for the cap to bind, against every set on its own: one run's caps (8 x 2 x the CUs
+    for k_ell, 16 384 for k_ell_wave) exceed this cloud's worst-case grids (2 x (n / 4d + 1) = 602 children per level),
+    so a single run gets the uncapped grid.  Every output the same."""
     rng = np.random.default_rng(21)
     ctrs = rng.uniform(0.1, 0.9, (40, 2))
     base = np.concatenate([c + 0.004 * rng.standard_normal((60, 2)) for c in ctrs])
     sets = [base[np.random.default_rng(r).permutation(len(base))] for r in range(48)]
     got = ctx.rebuild_many(sets, multi=True)
-    os.environ["DH_LEVEL_GRID_CAP"] = "0"
-    try:
-        ref = ctx.rebuild_many(sets, multi=True)
-    finally:
-        del os.environ["DH_LEVEL_GRID_CAP"]
+    ref = [ctx.rebuild_many([p], multi=True)[0] for p in sets]
     assert max(g["nells"] for g in got) >= 10
     for a, b in zip(ref, got):
         assert a["nells"] == b["nells"]

@@ -1,4 +1,4 @@
-"""Stress: repeated rebuilds of captured C3 / C2 live sets must be bit-identical (env: DH_SPLIT_TP, DH_DEEP)."""
+"""Stress: repeated rebuilds of captured C3 / C2 live sets must be bit-identical (env: DH_DEEP)."""
 import os, sys, numpy as np
 sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
 from dynesty_amd import _lib
