@@ -5,8 +5,11 @@
 //   RNG_PHILOX  hiprand's Philox4x32-10 device generator (hiprand_kernel.h), keyed (seed, subsequence = seq0 +
 //               walker, offset): counter based, no generator state in HBM.  The throughput mode (north_star:
 //               "hiprand for the unit-cube draws"): same algorithms, same distributions -- normals are hiprand's
-//               fp32 Box-Muller values widened to fp64, uniforms 53-bit -- but not the reference's streams, so it
-//               is validated statistically (tests/test_gpu_philox.py).
+//               fp32 Box-Muller values widened to fp64, uniforms 53-bit -- but not the reference's streams: held
+//               statistically (tests/test_gpu_philox.py) and, for the draws DESIGN.md §2 lists, to a restatement
+//               of hiprand's stream (tests/philox_ref.py, tests/test_gpu_philox_streams.py): uniforms exact,
+//               normals to 2^-18 in a direction component.  The wide entry points round the offset up to a
+//               multiple of 4 (WaveGen advances in whole blocks).
 //
 // LaneGen<RNG>: one stream per lane (walker-per-lane kernels: walk.hip, walk2.hip).
 // WaveGen<RNG>: one stream per wavefront, vector draws produced by all lanes (wave-per-walker kernels: wide.hip).

@@ -58,6 +58,8 @@ namespace {
 //               fp32 Box-Muller pairs (hiprand_normal4) widened to fp64, uniforms hiprand_uniform_double.
 //               Same algorithm, same distributions to fp32 resolution of the step direction -- the
 //               proposal stays exactly symmetric -- but NOT the reference's streams: the throughput mode.
+//               One-step proposals and 45-step chains of this kernel are held to tests/philox_ref.py's
+//               restated stream (uniforms exact, normals to 2^-18 in a direction component).
 enum : int { RNG_PCG64 = 0, RNG_PHILOX = 1 };
 
 struct RwalkArgs {

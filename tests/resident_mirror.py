@@ -85,20 +85,61 @@ def child_words(entropy, child):
 
 
 def mirror_run(ctx, prob, nlive, K, walks, bound, entropy, run, dlogz, enlarge=1.25, forced="exact", first_run=0,
-               max_fills=100000, sample="rwalk", bc=None, bootstrap=0, update_interval=None, first_update=None):
+               max_fills=100000, sample="rwalk", bc=None, bootstrap=0, update_interval=None, first_update=None,
+               rng="pcg64"):
     """The run with global index first_run + run of ns_ensemble(prob, ..., rebuild_every=1); sample = 'rwalk' |
-    'rslice' | 'slice' (`walks` is then the number of slices), bc = DH_BC_* flags per dimension or None."""
+    'rslice' | 'slice' (`walks` is then the number of slices), bc = DH_BC_* flags per dimension or None.
+
+    rng = 'philox': the throughput mode's unit-cube phase, its tries restated from hiprand's Philox stream
+    (tests/philox_ref.py) keyed as ns.hip keys it (philox_cube_key); only the unit-cube phase is mirrored in this mode."""
     from dynesty_amd import backend, bounding
     backend.set_backend(ctx)
     try:
         return _mirror(ctx, prob, nlive, K, walks, bound, entropy, first_run + run, dlogz, enlarge, forced, max_fills,
-                       sample, bc, bootstrap, update_interval, first_update)
+                       sample, bc, bootstrap, update_interval, first_update, rng)
     finally:
         backend.set_backend(None)
 
 
+def philox_cube_key(entropy, grun, K, fill):
+    """ns.hip's Philox key of the unit-cube stage: seed = (w0 << 32) ^ w1 ^ 0x9E3779B97F4A7C15 of the entropy words,
+    XOR-ed with the stage's constant 0x5BD1E995C0BE; subsequence of walker w = global run * K + w; offset = fill << 24
+    (2^24 words per walker and fill)."""
+    from dynesty_amd import _lib
+    ew = [int(x) for x in _lib.entropy_words(entropy)]
+    seed = ((ew[0] << 32) ^ (ew[1] if len(ew) > 1 else 0) ^ 0x9E3779B97F4A7C15) & M64
+    return seed ^ 0x5BD1E995C0BE, grun * K, fill << 24
+
+
+def philox_cube_fill(ctx, prob, loglstar, K, seed, seq0, offset, chunk=256):
+    """The unit-cube phase's fill on the restated stream: walker w's try t is the D uniforms 1 - uniform_double of the
+    2 D words from offset + 2 D t of subsequence seq0 + w (the lane and four-lane kernels; D has a lane kernel); the
+    first try above loglstar wins, its call count is t + 1."""
+    import philox_ref as PR
+    D = prob.ndim
+    seqs = seq0 + np.arange(K, dtype=np.uint64)
+    u_out, v_out = np.zeros((K, D)), np.zeros((K, D))
+    l_out, nc = np.zeros(K), np.zeros(K, dtype=np.int32)
+    t0 = 0
+    while (nc == 0).any():
+        t = np.arange(t0, t0 + chunk, dtype=np.uint64)
+        sq = np.repeat(seqs, chunk)
+        pos = np.tile(np.uint64(offset) + np.uint64(2 * D) * t, K)
+        w = PR.words(seed, sq, pos, 2 * D).astype(np.uint64)
+        u = 1.0 - PR.uniform_double(w[:, 0::2], w[:, 1::2])
+        v, ll = ctx.problem_eval(prob, u)
+        ll = np.asarray(ll).reshape(K, chunk)
+        for k in np.flatnonzero(nc == 0):
+            hit = np.flatnonzero(ll[k] > loglstar)
+            if len(hit):
+                j = k * chunk + hit[0]
+                u_out[k], v_out[k], l_out[k], nc[k] = u[j], v[j], ll[k, hit[0]], t0 + hit[0] + 1
+        t0 += chunk
+    return dict(u=u_out, v=v_out, logl=l_out, ncalls=nc)
+
+
 def _mirror(ctx, prob, N, K, walks, bound, entropy, grun, dlogz, enlarge, forced, max_fills, sample, bc, bootstrap,
-            upd, first):
+            upd, first, rng="pcg64"):
     from dynesty_amd import bounding
     D = prob.ndim
     # ---- ns_init: every initial point its own child stream, the run's generator child 0x80000000 + run ----
@@ -191,6 +232,7 @@ def _mirror(ctx, prob, N, K, walks, bound, entropy, grun, dlogz, enlarge, forced
             ncall_last = ncall
             ev["rebuild_fills"].append(fill)
         # ---- ns_select: four words of the run's generator seed this fill's K selection streams ----
+        assert rng == "pcg64" or cube, "rng='philox': only the unit-cube phase is mirrored"
         ent = [rg.next64() for _ in range(4)]
         states = np.empty((K, 4), dtype=np.uint64)
         start = np.zeros(K, dtype=np.int64)
@@ -208,7 +250,10 @@ def _mirror(ctx, prob, N, K, walks, bound, entropy, grun, dlogz, enlarge, forced
                 if multi:
                     xr[w] = g.next_double()
             states[w] = g.words()
-        if cube:
+        if cube and rng == "philox":
+            out = philox_cube_fill(ctx, prob, loglstar, K, *philox_cube_key(entropy, grun, K, fill))
+            q_nc = out["ncalls"].astype(np.int32)
+        elif cube:
             out = ctx.unif_batch(prob, loglstar, states)
             q_nc = out["ncalls"].astype(np.int32)
         elif sample == "unif":

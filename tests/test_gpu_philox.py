@@ -1,5 +1,7 @@
 """Throughput RNG mode of the rwalk kernel (hiprand Philox4x32-10, dh_rwalk_batch_philox): not
-stream-compatible with the reference, so it is validated statistically --
+stream-compatible with the reference.  tests/test_gpu_philox_streams.py holds the draws DESIGN.md §2 lists to a
+restated stream (tests/philox_ref.py: uniforms bit for bit, normals to 2^-18 in a direction component); here the mode
+is held statistically --
 
   * the reference's own KS tests of tests/test_ellipsoid.py (radius^ndim of a draw in the unit ball
     ~ U(0,1): test_sample / test_samples_single) applied to the kernel's one-step proposals,
