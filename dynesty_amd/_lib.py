@@ -18,6 +18,8 @@ ERR_VALUE, ERR_CONTAIN, ERR_REGION, ERR_SLICE = -1, -2, -3, -4
 ERR_HIP, ERR_ARG, ERR_QZERO, ERR_NOMEM = -5, -6, -7, -8
 
 BC_HARD, BC_PERIODIC, BC_REFLECT = 0, 1, 2
+# dh_ns_ensemble bound codes
+BOUND_CODES = dict(single=0, multi=1, balls=2, cubes=3)
 
 
 class DynHipError(RuntimeError):
@@ -102,6 +104,8 @@ SIGNATURES = {
     "dh_bootstrap_expand": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "dh_friends_update": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp,
                                _vp, _vp, _vp, _vp]),
+    "dh_friends_update_batch": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dh_friends_within": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "dh_friends_draw": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp,
                              _vp, _vp]),
@@ -821,6 +825,10 @@ class Context:
         sample: 'rwalk' | 'rslice' | 'slice' | 'unif'.  enlarge / bootstrap default as the reference's
         _get_enlarge_bootstrap (dynesty.py:169-200): (1.25, 0), and (1, 5) for 'unif'.
 
+        bound: 'multi' | 'single' with every sampler; 'balls' (RadFriends) | 'cubes' (SupFriends) with
+        sample='unif', rng='pcg64' and ndim <= 32 only -- the update batched over the due runs on the device, the
+        shapes on each run's live points of the fill.  Every other combination raises ValueError.
+
         rebuild_sync=False keeps the reference's per-run update schedule
         (sampler.py:625-674): a run's result then depends only on its own seed,
         not on how the ensemble is sharded.  rebuild_sync=True lets all runs
@@ -828,9 +836,19 @@ class Context:
         (early, never late): fewer, fuller rebuild launches, but a run's
         schedule then depends on its shard mates."""
         nd = prob.ndim
-        if bound not in ('multi', 'single'):
+        if bound not in ('multi', 'single', 'balls', 'cubes'):
             raise ValueError(f"ns_ensemble: bound={bound!r} is not supported by the device-resident "
-                             "loop ('multi' or 'single'; balls / cubes: nested.run_static)")
+                             "loop ('multi', 'single', or 'balls' / 'cubes' with sample='unif')")
+        if bound in ('balls', 'cubes'):
+            if sample != 'unif':
+                raise ValueError(f"ns_ensemble: bound={bound!r} with sample={sample!r} is not supported by the "
+                                 "device-resident loop (balls / cubes run with sample='unif' only)")
+            if rng != 'pcg64':
+                raise ValueError(f"ns_ensemble: bound={bound!r} with rng={rng!r} is not supported by the "
+                                 "device-resident loop (balls / cubes need rng='pcg64')")
+            if nd > 32:
+                raise ValueError(f"ns_ensemble: bound={bound!r} at ndim={nd} is not supported by the "
+                                 "device-resident loop (balls / cubes need ndim <= 32)")
         if sample not in ('rwalk', 'rslice', 'slice', 'unif'):
             raise ValueError(f"ns_ensemble: sample={sample!r} is not supported by the "
                              "device-resident loop ('rwalk', 'rslice', 'slice' or 'unif')")
@@ -889,7 +907,7 @@ class Context:
         self._check(self.lib.dh_ns_ensemble(
             self.handle, self.problem(prob), int(runs), int(nlive), nd,
             int(queue_size), kind + ((1 if kind == 6 else 3) if rng == 'philox' else 0), int(walks),
-            1 if bound == 'multi' else 0,
+            BOUND_CODES[bound],
             1 if rebuild_sync else 0, float(dlogz), float(enlarge), int(max_fills), int(max_iter),
             _ptr(words), words.size, int(first_run), _ptr(rec), _ptr(dead),
             _ptr(livel), _ptr(dead_u), _ptr(live_u), C.byref(nf), _ptr(pid), _ptr(pit), _ptr(pnc),
@@ -945,6 +963,29 @@ class Context:
             _ptr(axes_inv), C.byref(lv), C.byref(rmax), C.byref(ncl)))
         return dict(cov=cov, am=am, axes=axes, axes_inv=axes_inv,
                     logvol=lv.value, rmax=rmax.value, nclusters=ncl.value)
+
+    def friends_update_batch(self, points, kind, am_prev=None, in_masks=None, active=None, out=None):
+        """dh_friends_update over runs at once (dh_friends_update_batch).  points (runs, n, d); am_prev (runs, d, d)
+        or None (no clustering); in_masks (runs, B, n) bool or None (leave-one-out); active (runs,) bool or None (all).
+        out: optional dict of arrays as returned, whose inactive (and failed) runs are left untouched; returns dict
+        cov / am / axes / axes_inv (runs, d, d), logvol / rmax (runs,), nclusters / status (runs,) int32."""
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        runs, n, d = pts.shape
+        prev = None if am_prev is None else np.ascontiguousarray(am_prev, dtype=np.float64).reshape(runs, d, d)
+        nb, mk = 0, None
+        if in_masks is not None and np.asarray(in_masks).shape[1]:
+            mk = np.ascontiguousarray(in_masks, dtype=np.uint8).reshape(runs, -1, n)
+            nb = mk.shape[1]
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32).reshape(runs)
+        if out is None:
+            out = dict(cov=np.zeros((runs, d, d)), am=np.zeros((runs, d, d)), axes=np.zeros((runs, d, d)),
+                       axes_inv=np.zeros((runs, d, d)), logvol=np.zeros(runs), rmax=np.zeros(runs),
+                       nclusters=np.zeros(runs, dtype=np.int32), status=np.zeros(runs, dtype=np.int32))
+        self._check(self.lib.dh_friends_update_batch(
+            self.handle, runs, _ptr(pts), n, d, 0 if kind == 'balls' else 1, _ptr(prev), nb, _ptr(mk), _ptr(act),
+            _ptr(out["cov"]), _ptr(out["am"]), _ptr(out["axes"]), _ptr(out["axes_inv"]), _ptr(out["logvol"]),
+            _ptr(out["rmax"]), _ptr(out["nclusters"]), _ptr(out["status"])))
+        return out
 
     def friends_within(self, ctrs, kind, axes_inv, x, want_bits=False):
         """Counts (and optionally index bit rows) of the balls / cubes that

@@ -103,11 +103,13 @@ __global__ void __launch_bounds__(kBT) boot_mask_kernel(BootArgs a) {
     p += sel[i];
   }
   __syncthreads();
-  const double* src = a.pts + (size_t)run * n * d;
-  double* dst = a.bpts + rb * n * d;
-  for (int e = t; e < n * d; e += kBT) {
-    const int i = e / d, j = e - i * d;
-    if (sel[i]) dst[(size_t)pos[i] * d + j] = src[e];
+  if (a.bpts) {  // (null: the masks alone, for the friends bounds' radius)
+    const double* src = a.pts + (size_t)run * n * d;
+    double* dst = a.bpts + rb * n * d;
+    for (int e = t; e < n * d; e += kBT) {
+      const int i = e / d, j = e - i * d;
+      if (sel[i]) dst[(size_t)pos[i] * d + j] = src[e];
+    }
   }
   unsigned char* sg = a.sel + rb * n;
   for (int i = t; i < n; i += kBT) sg[i] = (unsigned char)sel[i];
@@ -228,6 +230,25 @@ int dh::bootstrap_expand_launch(dh_ctx* ctx, int runs, const double* pts, int n,
   hipLaunchKernelGGL(boot_expand_kernel, dim3(B, runs), dim3(kBT), 0, ctx->stream, a);
   hipLaunchKernelGGL(boot_finish_kernel, dim3((runs + 63) / 64), dim3(64), 0, ctx->stream, a);
   return hip_ok(ctx, hipGetLastError(), "bootstrap launch") ? DH_OK : DH_ERR_HIP;
+}
+
+int dh::boot_masks_launch(dh_ctx* ctx, int runs, int n, int B, const uint64_t* ent, const int* active,
+                          unsigned char* sel, int* scratch) {
+  if (runs < 1 || B < 1 || n < 2 || !ent || !sel || !scratch) return fail(ctx, DH_ERR_ARG, "bootstrap masks: bad arguments");
+  const size_t lds = (size_t)n * 8;
+  if (lds > 60 * 1024) return fail(ctx, DH_ERR_ARG, "bootstrap: n=%d points per run is more than the mask kernel holds", n);
+  BootArgs a{};
+  a.runs = runs;
+  a.n = n;
+  a.B = B;
+  a.ent = ent;
+  a.active = active;
+  a.bpts = nullptr;
+  a.sel = sel;
+  a.n_arr = scratch;
+  a.act = scratch + (size_t)runs * B;
+  hipLaunchKernelGGL(boot_mask_kernel, dim3(B, runs), dim3(kBT), lds, ctx->stream, a);
+  return hip_ok(ctx, hipGetLastError(), "bootstrap mask launch") ? DH_OK : DH_ERR_HIP;
 }
 
 extern "C" {

@@ -194,6 +194,13 @@ int unif_launch_runs(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, int m
                      double* logl, int32_t* ncalls, int32_t* flags, uint64_t* rng_out,
                      const double* run_loglstar, const int* run_mode, int wpr, int my_mode,
                      const PhiloxKey* philox = nullptr, const int* run_nells = nullptr, int run_me = 0);
+// the uniform sampler inside each run's RadFriends (kind 0) / SupFriends (1) bound, PCG64 streams, ndim <= 32: run r
+// = walker / wpr has n centres ctrs + r n ndim (its live points), their whitened copies ct + r n ndim, and the shape
+// axes / axes_inv + r ndim^2
+int unif_friends_launch_runs(dh_ctx* ctx, int problem, int k, int ndim, int kind, int n, const double* ctrs,
+                             const double* ct, const double* axes, const double* axes_inv, const int8_t* bc,
+                             const uint64_t* rng, double* u, double* v, double* logl, int32_t* ncalls, int32_t* flags,
+                             uint64_t* rng_out, const double* run_loglstar, const int* run_mode, int wpr, int my_mode);
 
 int rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int d, int mode, int max_ells,
                         int32_t* nells, int32_t* status, double* ctrs, double* covs, double* ams,
@@ -216,8 +223,24 @@ int eval_launch_dev(dh_ctx* ctx, int problem, int k, const double* u, double* v,
 int contains_runs_launch(dh_ctx* ctx, const double* x, int k, int d, int wpr, const double* ctrs, const double* ams,
                          const int* nells, int max_ells, int strict, const int* run_mode, int my_mode,
                          const int* bstatus, int* flag, int* first = nullptr);
+// the in-sample masks sel (runs x B x n, 1 = resampled) of _bootstrap_points (bounding.py:1593-1616) alone, from the
+// same replica streams; scratch: 2 runs B ints
+int boot_masks_launch(dh_ctx* ctx, int runs, int n, int B, const uint64_t* ent, const int* active, unsigned char* sel,
+                      int* scratch);
 // friends.hip: Y = X M (n x d times d x d) on the context's stream, device pointers
 int friends_whiten_launch(dh_ctx* ctx, const double* X, const double* M, int n, int d, double* Y);
+// the same for runs x n x d points and runs x d x d matrices, runs with sel[run] == want (sel null: all)
+int friends_whiten_runs_launch(dh_ctx* ctx, int runs, const double* X, const double* M, int n, int d, double* Y,
+                               const int* sel, int want);
+// RadFriends / SupFriends update of every run with sel[run] == 1 (null: all), device pointers, no host
+// synchronisation: dh_friends_update per run, then (log_enlarge != 0) scale_to_logvol(logvol + log_enlarge).
+// am_prev (runs x d x d, may alias am; null: no clustering); in_mask runs x nboot x n; ws of friends_batch_ws_bytes.
+// status[run] = DH_OK / DH_ERR_VALUE; a failed run's run_mode (if given) becomes 4 (the loop's MODE_WAIT).
+size_t friends_batch_ws_bytes(int runs, int n, int d, int nboot);
+int friends_update_launch(dh_ctx* ctx, int runs, const double* pts, int n, int d, int kind, const double* am_prev,
+                          int nboot, const unsigned char* in_mask, const int* sel, double log_enlarge, void* ws,
+                          double* cov, double* am, double* axes, double* axes_inv, double* logvol, double* rmax,
+                          int* nclusters, int* status, int* run_mode);
 
 // wide-D path (wide.hip): used by the dispatchers when the dimension exceeds the
 // register-resident limits.  kind: 0 rwalk, 1 rslice, 2 slice, 3 unit cube.

@@ -11,6 +11,11 @@
 //   fr_nn            leave-one-out / bootstrap nearest-neighbour distance (2- or max-norm)
 //   fr_within        membership counts + ballot bit rows of candidate points
 //   fr_draw          Bound.sample(s) from ONE generator: draws by lane 0, overlap count by the wave
+//
+// The update kernels take a run index from their last grid dimension (run r owns the rows r * n .. of the points
+// and its own d x d matrices) and skip runs with sel[r] != want: the single-set entry point launches them with one
+// run, the batched one (dh_friends_update_batch, the resident loop's rebuild) over all runs at once.  Per element the
+// arithmetic is the same in both, so a run's results are bit-identical to the single-set call on its points.
 #include <math.h>
 
 #include "ctx.h"
@@ -24,10 +29,18 @@ namespace {
 constexpr int kT = 256;
 enum : int { KIND_BALLS = 0, KIND_CUBES = 1 };
 
+// the run of this workgroup takes part (sel == null: every run)
+__device__ __forceinline__ bool fr_on(const int* sel, int want, int run) { return !sel || sel[run] == want; }
+
 // ---- Y = X M  (n x d times d x d), one thread per output --------------------------------
 __global__ void __launch_bounds__(kT) fr_matmul(const double* __restrict__ X, const double* __restrict__ M,
-                                                 int n, int d, double* __restrict__ Y) {
+                                                 int n, int d, double* __restrict__ Y, const int* sel, int want) {
   extern __shared__ double sm[];  // M, d*d
+  const int run = blockIdx.y;
+  if (!fr_on(sel, want, run)) return;
+  X += (size_t)run * n * d;
+  M += (size_t)run * d * d;
+  Y += (size_t)run * n * d;
   for (int e = threadIdx.x; e < d * d; e += kT) sm[e] = M[e];
   __syncthreads();
   const long long o = (long long)blockIdx.x * kT + threadIdx.x;
@@ -51,8 +64,14 @@ __global__ void __launch_bounds__(kT) fr_matmul(const double* __restrict__ X, co
 // i, lane = j.
 #pragma clang fp contract(off)
 __global__ void __launch_bounds__(kT) fr_adjacency(const double* __restrict__ X, const double* __restrict__ VI,
-                                                    int n, int d, unsigned long long* __restrict__ bits, int nw) {
+                                                    int n, int d, unsigned long long* __restrict__ bits, int nw,
+                                                    const int* sel, int want) {
   extern __shared__ double sm[];  // VI d*d | per wave: u d | columns [d][64]
+  const int run = blockIdx.z;
+  if (!fr_on(sel, want, run)) return;
+  X += (size_t)run * n * d;
+  VI += (size_t)run * d * d;
+  bits += (size_t)run * n * nw;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int i = blockIdx.y * 4 + wv, w = blockIdx.x;
   double* vi = sm;
@@ -83,8 +102,13 @@ __global__ void __launch_bounds__(kT) fr_adjacency(const double* __restrict__ X,
 // pushes it to its current root), then pointer jumping until stable; repeat until a round
 // changes nothing.  The fixed point is order-independent.
 __global__ void __launch_bounds__(1024) fr_components(const unsigned long long* __restrict__ bits, int n, int nw,
-                                                       int* __restrict__ label, int* __restrict__ ncomp) {
-  const int t = threadIdx.x;
+                                                       int* __restrict__ label, int* __restrict__ ncomp,
+                                                       const int* sel, int want) {
+  const int t = threadIdx.x, run = blockIdx.x;
+  if (!fr_on(sel, want, run)) return;
+  bits += (size_t)run * n * nw;
+  label += (size_t)run * n;
+  ncomp += run;
   __shared__ int changed;
   for (int i = t; i < n; i += 1024) label[i] = i;
   __syncthreads();
@@ -142,9 +166,15 @@ __global__ void __launch_bounds__(1024) fr_components(const unsigned long long* 
 }
 
 // ---- mean of every component (block = candidate root), members visited in index order -------
+// (ncomp != null: only runs with more than one cluster)
 __global__ void __launch_bounds__(64) fr_cluster_mean(const double* __restrict__ X, const int* __restrict__ label,
-                                                       int n, int d, double* __restrict__ mean) {
-  const int r = blockIdx.x;
+                                                       int n, int d, double* __restrict__ mean, const int* ncomp,
+                                                       const int* sel, int want) {
+  const int r = blockIdx.x, run = blockIdx.y;
+  if (!fr_on(sel, want, run) || (ncomp && ncomp[run] <= 1)) return;
+  X += (size_t)run * n * d;
+  label += (size_t)run * n;
+  mean += (size_t)run * n * d;
   if (label[r] != r) return;
   for (int k = threadIdx.x; k < d; k += 64) {
     double s = 0.0;
@@ -158,11 +188,23 @@ __global__ void __launch_bounds__(64) fr_cluster_mean(const double* __restrict__
   }
 }
 
+// (ncomp != null: a run with one cluster takes its points as they are, np.cov of all points)
 __global__ void __launch_bounds__(kT) fr_recentre(const double* __restrict__ X, const int* __restrict__ label,
                                                    const double* __restrict__ mean, int n, int d,
-                                                   double* __restrict__ out) {
+                                                   double* __restrict__ out, const int* ncomp, const int* sel,
+                                                   int want) {
+  const int run = blockIdx.y;
+  if (!fr_on(sel, want, run)) return;
   const long long o = (long long)blockIdx.x * kT + threadIdx.x;
   if (o >= (long long)n * d) return;
+  X += (size_t)run * n * d;
+  label += (size_t)run * n;
+  mean += (size_t)run * n * d;
+  out += (size_t)run * n * d;
+  if (ncomp && ncomp[run] <= 1) {
+    out[o] = X[o];
+    return;
+  }
   const int i = (int)(o / d), k = (int)(o - (long long)i * d);
   out[o] = X[o] - mean[(size_t)label[i] * d + k];
 }
@@ -179,9 +221,13 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return r;
 }
 
-__global__ void __launch_bounds__(kT) fr_colmean(const double* __restrict__ X, int n, int d, double* __restrict__ m) {
+__global__ void __launch_bounds__(kT) fr_colmean(const double* __restrict__ X, int n, int d, double* __restrict__ m,
+                                                  const int* sel, int want) {
   __shared__ double red[kT / 64];
-  const int k = blockIdx.x;
+  const int k = blockIdx.x, run = blockIdx.y;
+  if (!fr_on(sel, want, run)) return;
+  X += (size_t)run * n * d;
+  m += (size_t)run * d;
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += kT) s += X[(size_t)i * d + k];
   s = block_sum(s, red);
@@ -190,10 +236,13 @@ __global__ void __launch_bounds__(kT) fr_colmean(const double* __restrict__ X, i
 
 // np.cov(X, rowvar=False): entry (a, b), ddof = 1
 __global__ void __launch_bounds__(kT) fr_cov(const double* __restrict__ X, const double* __restrict__ m, int n, int d,
-                                              double* __restrict__ cov) {
+                                              double* __restrict__ cov, const int* sel, int want) {
   __shared__ double red[kT / 64];
-  const int a = blockIdx.x / d, b = blockIdx.x % d;
-  if (b < a) return;
+  const int a = blockIdx.x / d, b = blockIdx.x % d, run = blockIdx.y;
+  if (b < a || !fr_on(sel, want, run)) return;
+  X += (size_t)run * n * d;
+  m += (size_t)run * d;
+  cov += (size_t)run * d * d;
   const double ma = m[a], mb = m[b];
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += kT) s = fma(X[(size_t)i * d + a] - ma, X[(size_t)i * d + b] - mb, s);
@@ -210,9 +259,17 @@ __global__ void __launch_bounds__(kT) fr_cov(const double* __restrict__ X, const
 __global__ void __launch_bounds__(64) fr_shape(const double* __restrict__ cov, int d, double* __restrict__ am,
                                                 double* __restrict__ axes, double* __restrict__ axes_inv,
                                                 double* __restrict__ info /* [0] sum log lam, [1] n dropped */,
-                                                int* __restrict__ status) {
+                                                int* __restrict__ status, const int* sel, int want) {
   extern __shared__ double sm[];
-  const int LD = d | 1, lane = threadIdx.x;
+  const int LD = d | 1, lane = threadIdx.x, run = blockIdx.x;
+  if (!fr_on(sel, want, run)) return;
+  const size_t dd = (size_t)d * d;
+  cov += run * dd;
+  am += run * dd;
+  axes += run * dd;
+  axes_inv += run * dd;
+  info += (size_t)run * 2;
+  status += run;
   double* A = sm;
   double* V = A + d * LD;
   double* S = V + d * LD;
@@ -266,9 +323,14 @@ __global__ void __launch_bounds__(64) fr_shape(const double* __restrict__ cov, i
 // grid (ceil(n/kT), replicas).  Query i (skipped when in_mask says it was resampled), candidates j
 // (only resampled ones under a mask; j != i without one).  Output nn[b][i] (or -1 for skipped).
 __global__ void __launch_bounds__(kT) fr_nn(const double* __restrict__ Y, int n, int d, int kind,
-                                             const unsigned char* __restrict__ in_mask, double* __restrict__ nn) {
+                                             const unsigned char* __restrict__ in_mask, double* __restrict__ nn,
+                                             const int* sel, int want) {
   extern __shared__ double tile[];  // 64 x d candidate rows
-  const int b = blockIdx.y, t = threadIdx.x;
+  const int b = blockIdx.y, t = threadIdx.x, run = blockIdx.z;
+  if (!fr_on(sel, want, run)) return;
+  Y += (size_t)run * n * d;
+  if (in_mask) in_mask += (size_t)run * gridDim.y * n;
+  nn += (size_t)run * gridDim.y * n;
   const int i = blockIdx.x * kT + t;
   const unsigned char* mk = in_mask ? in_mask + (size_t)b * n : nullptr;
   const bool active = i < n && (!mk || !mk[i]);
@@ -299,8 +361,13 @@ __global__ void __launch_bounds__(kT) fr_nn(const double* __restrict__ Y, int n,
   if (i < n) nn[(size_t)b * n + i] = active ? (kind == KIND_BALLS ? sqrt(best) : best) : -1.0;
 }
 
-__global__ void __launch_bounds__(kT) fr_max(const double* __restrict__ v, long long n, double* __restrict__ out) {
+__global__ void __launch_bounds__(kT) fr_max(const double* __restrict__ v, long long n, double* __restrict__ out,
+                                              const int* sel, int want) {
   __shared__ double red[kT / 64];
+  const int run = blockIdx.x;
+  if (!fr_on(sel, want, run)) return;
+  v += (size_t)run * n;
+  out += run;
   double m = -INFINITY;
   for (long long i = threadIdx.x; i < n; i += kT) m = fmax(m, v[i]);
   for (int s = 32; s > 0; s >>= 1) m = fmax(m, __shfl_xor(m, s));
@@ -309,6 +376,56 @@ __global__ void __launch_bounds__(kT) fr_max(const double* __restrict__ v, long 
   if (threadIdx.x == 0) {
     for (int i = 1; i < kT / 64; ++i) m = fmax(m, red[i]);
     *out = m;
+  }
+}
+
+// ---- the batched update's tail, per run: dh_friends_update's host checks and scaling on the device -----------
+// Status (DH_ERR_VALUE: non-finite or singular covariance, zero radius; run_mode != null: the failed run also sits
+// the fill out, MODE_WAIT of the resident loop), the radius scaling (bounding.py:944-953), ln V of one shape, then
+// scale_to_logvol(logvol + ln enlarge) (sampler.py:506-508 with bounding.py:765-774) where log_enlarge != 0.
+// The products and quotients are those of the host tail, element by element; ln V uses the device's log / lgamma.
+__global__ void __launch_bounds__(64) fr_finish(int d, int kind, const int* __restrict__ shape_st,
+                                                 const double* __restrict__ info, const double* __restrict__ rr,
+                                                 const int* __restrict__ ncomp, double log_enlarge, double* cov,
+                                                 double* am, double* axes, double* axes_inv, double* logvol,
+                                                 double* rmax, int* nclusters, int* status, int* run_mode,
+                                                 const int* sel, int want) {
+  const int run = blockIdx.x, lane = threadIdx.x;
+  if (!fr_on(sel, want, run)) return;
+  const double r = rr[run];
+  const double* inf = info + (size_t)run * 2;
+  if (shape_st[run] != DH_OK || inf[1] > 0.5 || !(r > 0.0) || !isfinite(r)) {
+    if (lane == 0) {
+      status[run] = DH_ERR_VALUE;
+      if (run_mode) run_mode[run] = 4;
+    }
+    return;
+  }
+  const double pref = kind == KIND_BALLS ? d * log(2.0) + d * lgamma(1.5) - lgamma(d / 2.0 + 1.0) : d * log(2.0);
+  const double lv = pref + 0.5 * inf[0] + d * log(r);
+  const bool grow = log_enlarge != 0.0;
+  const double lvn = grow ? lv + log_enlarge : lv;
+  const double f = grow ? exp((lvn - lv) * (1.0 / (double)d)) : 1.0, f2 = f * f;
+  const double r2 = r * r;
+  const size_t dd = (size_t)d * d, o = (size_t)run * dd;
+  for (size_t e = lane; e < dd; e += 64) {
+    double c = cov[o + e] * r2, a = am[o + e] / r2, x = axes[o + e] * r, xi = axes_inv[o + e] / r;
+    if (grow) {
+      c *= f2;
+      a /= f2;
+      x *= f;
+      xi /= f;
+    }
+    cov[o + e] = c;
+    am[o + e] = a;
+    axes[o + e] = x;
+    axes_inv[o + e] = xi;
+  }
+  if (lane == 0) {
+    logvol[run] = lvn;
+    rmax[run] = r;
+    if (nclusters) nclusters[run] = ncomp ? ncomp[run] : 1;
+    status[run] = DH_OK;
   }
 }
 
@@ -448,8 +565,92 @@ int launch_ok(dh_ctx* ctx, const char* what) {
 
 int dh::friends_whiten_launch(dh_ctx* ctx, const double* X, const double* M, int n, int d, double* Y) {
   const size_t nd = (size_t)n * d;
-  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), (size_t)d * d * 8, ctx->stream, X, M, n, d, Y);
+  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), (size_t)d * d * 8, ctx->stream, X, M, n, d, Y,
+                     nullptr, 0);
   return hip_ok(ctx, hipGetLastError(), "friends whiten launch") ? DH_OK : DH_ERR_HIP;
+}
+
+int dh::friends_whiten_runs_launch(dh_ctx* ctx, int runs, const double* X, const double* M, int n, int d, double* Y,
+                                   const int* sel, int want) {
+  const size_t nd = (size_t)n * d;
+  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT), runs), dim3(kT), (size_t)d * d * 8, ctx->stream, X, M, n,
+                     d, Y, sel, want);
+  return hip_ok(ctx, hipGetLastError(), "friends whiten launch") ? DH_OK : DH_ERR_HIP;
+}
+
+namespace {
+inline size_t fr_al(size_t x) { return (x + 255) & ~(size_t)255; }
+int fr_adjacency_lds(dh_ctx* ctx, int d, size_t* lds) {
+  const size_t dd = (size_t)d * d;
+  *lds = (dd + 4 * ((size_t)d + (size_t)d * 64)) * 8;
+  if (*lds > 159 * 1024) return fail(ctx, DH_ERR_ARG, "friends_update: clustering needs d <= 60 (d = %d)", d);
+  DH_DEV_MEMO(attr_adj);
+  if (*lds > attr_adj) {
+    if (!hip_ok(ctx, hipFuncSetAttribute((const void*)fr_adjacency, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)*lds), "hipFuncSetAttribute(fr_adjacency)"))
+      return DH_ERR_HIP;
+    attr_adj = *lds;
+  }
+  return DH_OK;
+}
+size_t fr_shape_lds(int d) { return ((size_t)3 * d * (d | 1) + d + 128) * 8 + (128 + d + 8) * 4; }
+}  // namespace
+
+size_t dh::friends_batch_ws_bytes(int runs, int n, int d, int nboot) {
+  const size_t R = (size_t)runs, nd = (size_t)n * d, nw = (size_t)(n + 63) / 64, reps = nboot > 0 ? nboot : 1;
+  return 2 * fr_al(R * nd * 8) + fr_al(R * n * nw * 8) + fr_al(R * n * 4) + 2 * fr_al(R * 4) + fr_al(R * d * 8) +
+         fr_al(R * 16) + fr_al(R * reps * n * 8) + fr_al(R * 8) + 1024;
+}
+
+// Every stage over every run with sel[run] == 1 (sel == null: all runs) in one launch each; no host synchronisation.
+// am_prev may alias am (the clustering reads it before fr_shape writes the new metric); null: no clustering.
+int dh::friends_update_launch(dh_ctx* ctx, int runs, const double* pts, int n, int d, int kind, const double* am_prev,
+                              int nboot, const unsigned char* in_mask, const int* sel, double log_enlarge, void* ws,
+                              double* cov, double* am, double* axes, double* axes_inv, double* logvol, double* rmax,
+                              int* nclusters, int* status, int* run_mode) {
+  if (runs < 1 || n < 2 || d < 1 || d > 64 || (kind != KIND_BALLS && kind != KIND_CUBES) || nboot < 0 ||
+      (nboot > 0 && !in_mask) || !ws)
+    return fail(ctx, DH_ERR_ARG, "friends_update_launch: bad arguments");
+  const size_t R = (size_t)runs, nd = (size_t)n * d, dd = (size_t)d * d;
+  const int nw = (n + 63) / 64, reps = nboot > 0 ? nboot : 1, gb = (int)((nd + kT - 1) / kT);
+  char* p = (char*)ws;
+  auto take = [&](size_t bytes) {
+    char* o = p;
+    p += fr_al(bytes);
+    return (void*)o;
+  };
+  double* d_y = (double*)take(R * nd * 8);
+  double* d_mv = (double*)take(R * nd * 8);
+  unsigned long long* d_bits = (unsigned long long*)take(R * n * nw * 8);
+  int* d_label = (int*)take(R * n * 4);
+  int* d_nc = (int*)take(R * 4);
+  int* d_st = (int*)take(R * 4);
+  double* d_m = (double*)take(R * d * 8);
+  double* d_info = (double*)take(R * 16);
+  double* d_nn = (double*)take(R * reps * n * 8);
+  double* d_r = (double*)take(R * 8);
+  hipStream_t s = ctx->stream;
+  if (am_prev) {
+    size_t lds_adj = 0;
+    int rc = fr_adjacency_lds(ctx, d, &lds_adj);
+    if (rc) return rc;
+    hipLaunchKernelGGL(fr_adjacency, dim3(nw, (n + 3) / 4, runs), dim3(kT), lds_adj, s, pts, am_prev, n, d, d_bits, nw,
+                       sel, 1);
+    hipLaunchKernelGGL(fr_components, dim3(runs), dim3(1024), 0, s, d_bits, n, nw, d_label, d_nc, sel, 1);
+    hipLaunchKernelGGL(fr_cluster_mean, dim3(n, runs), dim3(64), 0, s, pts, d_label, n, d, d_y, d_nc, sel, 1);
+    hipLaunchKernelGGL(fr_recentre, dim3(gb, runs), dim3(kT), 0, s, pts, d_label, d_y, n, d, d_mv, d_nc, sel, 1);
+  }
+  const double* d_src = am_prev ? d_mv : pts;
+  hipLaunchKernelGGL(fr_colmean, dim3(d, runs), dim3(kT), 0, s, d_src, n, d, d_m, sel, 1);
+  hipLaunchKernelGGL(fr_cov, dim3(d * d, runs), dim3(kT), 0, s, d_src, d_m, n, d, cov, sel, 1);
+  hipLaunchKernelGGL(fr_shape, dim3(runs), dim3(64), fr_shape_lds(d), s, cov, d, am, axes, axes_inv, d_info, d_st, sel, 1);
+  hipLaunchKernelGGL(fr_matmul, dim3(gb, runs), dim3(kT), dd * 8, s, pts, axes_inv, n, d, d_y, sel, 1);
+  hipLaunchKernelGGL(fr_nn, dim3((n + kT - 1) / kT, reps, runs), dim3(kT), (size_t)64 * d * 8, s, d_y, n, d, kind,
+                     nboot > 0 ? in_mask : nullptr, d_nn, sel, 1);
+  hipLaunchKernelGGL(fr_max, dim3(runs), dim3(kT), 0, s, d_nn, (long long)reps * n, d_r, sel, 1);
+  hipLaunchKernelGGL(fr_finish, dim3(runs), dim3(64), 0, s, d, kind, d_st, d_info, d_r, am_prev ? d_nc : nullptr,
+                     log_enlarge, cov, am, axes, axes_inv, logvol, rmax, nclusters, status, run_mode, sel, 1);
+  return launch_ok(ctx, "friends_update_batch launch");
 }
 
 extern "C" {
@@ -496,34 +697,28 @@ int dh_friends_update(dh_ctx* ctx, const double* pts, int n, int d, int kind, co
   int ncl = 1;
   if (d_prev) {
     // clusters: single linkage cut at Mahalanobis distance 1 in the previous metric
-    const size_t lds_adj = (dd + 4 * ((size_t)d + (size_t)d * 64)) * 8;
-    if (lds_adj > 159 * 1024) return fail(ctx, DH_ERR_ARG, "friends_update: clustering needs d <= 60 (d = %d)", d);
-    DH_DEV_MEMO(attr_adj);
-    if (lds_adj > attr_adj) {
-      if (!hip_ok(ctx, hipFuncSetAttribute((const void*)fr_adjacency, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_adj), "hipFuncSetAttribute(fr_adjacency)"))
-        return DH_ERR_HIP;
-      attr_adj = lds_adj;
-    }
-    hipLaunchKernelGGL(fr_adjacency, dim3(nw, (n + 3) / 4), dim3(kT), lds_adj, s, d_x, d_prev, n, d, d_bits, nw);
-    hipLaunchKernelGGL(fr_components, dim3(1), dim3(1024), 0, s, d_bits, n, nw, d_label, d_nc);
+    size_t lds_adj = 0;
+    if ((rc = fr_adjacency_lds(ctx, d, &lds_adj))) return rc;
+    hipLaunchKernelGGL(fr_adjacency, dim3(nw, (n + 3) / 4), dim3(kT), lds_adj, s, d_x, d_prev, n, d, d_bits, nw,
+                       nullptr, 0);
+    hipLaunchKernelGGL(fr_components, dim3(1), dim3(1024), 0, s, d_bits, n, nw, d_label, d_nc, nullptr, 0);
     if (!down(ctx, &ncl, d_nc, 1) || !hip_ok(ctx, hipStreamSynchronize(s), "sync")) return DH_ERR_HIP;
     if (ncl > 1) {
       double* d_mean = d_y;  // the whitened copy is no longer needed
-      hipLaunchKernelGGL(fr_cluster_mean, dim3(n), dim3(64), 0, s, d_x, d_label, n, d, d_mean);
-      hipLaunchKernelGGL(fr_recentre, dim3(gb), dim3(kT), 0, s, d_x, d_label, d_mean, n, d, d_mv);
+      hipLaunchKernelGGL(fr_cluster_mean, dim3(n), dim3(64), 0, s, d_x, d_label, n, d, d_mean, nullptr, nullptr, 0);
+      hipLaunchKernelGGL(fr_recentre, dim3(gb), dim3(kT), 0, s, d_x, d_label, d_mean, n, d, d_mv, nullptr, nullptr, 0);
       d_src = d_mv;
     }
   }
-  hipLaunchKernelGGL(fr_colmean, dim3(d), dim3(kT), 0, s, d_src, n, d, d_m);
-  hipLaunchKernelGGL(fr_cov, dim3(d * d), dim3(kT), 0, s, d_src, d_m, n, d, d_cov);
-  const size_t lds_shape = ((size_t)3 * d * (d | 1) + d + 128) * 8 + (128 + d + 8) * 4;
-  hipLaunchKernelGGL(fr_shape, dim3(1), dim3(64), lds_shape, s, d_cov, d, d_am, d_ax, d_ai, d_info, d_st);
+  hipLaunchKernelGGL(fr_colmean, dim3(d), dim3(kT), 0, s, d_src, n, d, d_m, nullptr, 0);
+  hipLaunchKernelGGL(fr_cov, dim3(d * d), dim3(kT), 0, s, d_src, d_m, n, d, d_cov, nullptr, 0);
+  hipLaunchKernelGGL(fr_shape, dim3(1), dim3(64), fr_shape_lds(d), s, d_cov, d, d_am, d_ax, d_ai, d_info, d_st, nullptr,
+                     0);
   // whitened points and the radius
-  hipLaunchKernelGGL(fr_matmul, dim3(gb), dim3(kT), dd * 8, s, d_x, d_ai, n, d, d_y);
+  hipLaunchKernelGGL(fr_matmul, dim3(gb), dim3(kT), dd * 8, s, d_x, d_ai, n, d, d_y, nullptr, 0);
   hipLaunchKernelGGL(fr_nn, dim3((n + kT - 1) / kT, reps), dim3(kT), (size_t)64 * d * 8, s, d_y, n, d, kind, d_mask,
-                     d_nn);
-  hipLaunchKernelGGL(fr_max, dim3(1), dim3(kT), 0, s, d_nn, (long long)reps * n, d_r);
+                     d_nn, nullptr, 0);
+  hipLaunchKernelGGL(fr_max, dim3(1), dim3(kT), 0, s, d_nn, (long long)reps * n, d_r, nullptr, 0);
   if ((rc = launch_ok(ctx, "friends_update launch"))) return rc;
   int st = 0;
   double info[2] = {0, 0}, r = 0.0;
@@ -551,6 +746,68 @@ int dh_friends_update(dh_ctx* ctx, const double* pts, int n, int d, int kind, co
   return DH_OK;
 }
 
+// see include/dynhip.h
+int dh_friends_update_batch(dh_ctx* ctx, int runs, const double* pts, int n, int d, int kind, const double* am_prev,
+                            int nboot, const uint8_t* in_mask, const int32_t* active, double* cov, double* am,
+                            double* axes, double* axes_inv, double* logvol, double* rmax, int32_t* nclusters,
+                            int32_t* status) {
+  DH_CHECK_CTX(ctx);
+  if (runs < 1 || !pts || n < 2 || d < 1 || d > 64 || (kind != KIND_BALLS && kind != KIND_CUBES) || !cov || !am ||
+      !axes || !axes_inv || !logvol || !rmax || !status || nboot < 0 || (nboot > 0 && !in_mask))
+    return fail(ctx, DH_ERR_ARG, "friends_update_batch: bad arguments (runs >= 1, 2 <= n, 1 <= d <= 64)");
+  (void)hipSetDevice(ctx->device);
+  arena_reset(ctx);
+  const size_t R = (size_t)runs, nd = (size_t)n * d, dd = (size_t)d * d;
+  const size_t wsb = friends_batch_ws_bytes(runs, n, d, nboot);
+  const size_t need = R * nd * 8 + (am_prev ? R * dd * 8 : 0) + (nboot > 0 ? R * nboot * n : 0) + R * 4 +
+                      R * (4 * dd * 8 + 16 + 8) + wsb + 65536;
+  int rc = arena_reserve(ctx, need);
+  if (rc) return rc;
+  double* d_x = arena_up(ctx, pts, R * nd);
+  double* d_prev = am_prev ? arena_up(ctx, am_prev, R * dd) : nullptr;
+  unsigned char* d_mask = nboot > 0 ? arena_up(ctx, in_mask, R * nboot * n) : nullptr;
+  int* d_act = active ? (int*)arena_up(ctx, active, R) : nullptr;
+  double* d_cov = (double*)arena_get(ctx, R * dd * 8);
+  double* d_am = (double*)arena_get(ctx, R * dd * 8);
+  double* d_ax = (double*)arena_get(ctx, R * dd * 8);
+  double* d_ai = (double*)arena_get(ctx, R * dd * 8);
+  double* d_lv = (double*)arena_get(ctx, R * 8);
+  double* d_rm = (double*)arena_get(ctx, R * 8);
+  int* d_ncl = (int*)arena_get(ctx, R * 4);
+  int* d_st = (int*)arena_get(ctx, R * 4);
+  void* ws = arena_get(ctx, wsb);
+  if (!d_x || (am_prev && !d_prev) || (nboot > 0 && !d_mask) || (active && !d_act) || !d_cov || !d_am || !d_ax ||
+      !d_ai || !d_lv || !d_rm || !d_ncl || !d_st || !ws)
+    return DH_ERR_NOMEM;
+  rc = friends_update_launch(ctx, runs, d_x, n, d, kind, d_prev, nboot, d_mask, d_act, 0.0, ws, d_cov, d_am, d_ax, d_ai,
+                             d_lv, d_rm, d_ncl, d_st, nullptr);
+  if (rc) return rc;
+  // inactive runs' outputs stay as the caller left them: results come back through host copies
+  std::vector<double> h_m(4 * R * dd), h_s(2 * R);
+  std::vector<int32_t> h_i(2 * R);
+  if (!down(ctx, h_m.data(), d_cov, R * dd) || !down(ctx, h_m.data() + R * dd, d_am, R * dd) ||
+      !down(ctx, h_m.data() + 2 * R * dd, d_ax, R * dd) || !down(ctx, h_m.data() + 3 * R * dd, d_ai, R * dd) ||
+      !down(ctx, h_s.data(), d_lv, R) || !down(ctx, h_s.data() + R, d_rm, R) || !down(ctx, h_i.data(), d_ncl, R) ||
+      !down(ctx, h_i.data() + R, d_st, R))
+    return DH_ERR_HIP;
+  if ((rc = dh_sync(ctx))) return rc;
+  for (size_t r = 0; r < R; ++r) {
+    if (active && !active[r]) continue;
+    status[r] = h_i[R + r];
+    if (status[r] != DH_OK) continue;
+    for (size_t e = 0; e < dd; ++e) {
+      cov[r * dd + e] = h_m[r * dd + e];
+      am[r * dd + e] = h_m[R * dd + r * dd + e];
+      axes[r * dd + e] = h_m[2 * R * dd + r * dd + e];
+      axes_inv[r * dd + e] = h_m[3 * R * dd + r * dd + e];
+    }
+    logvol[r] = h_s[r];
+    rmax[r] = h_s[R + r];
+    if (nclusters) nclusters[r] = h_i[r];
+  }
+  return DH_OK;
+}
+
 int dh_friends_within(dh_ctx* ctx, const double* ctrs, int n, int d, int kind, const double* axes_inv,
                       const double* x, int m, int32_t* counts, uint64_t* bits) {
   DH_CHECK_CTX(ctx);
@@ -571,8 +828,8 @@ int dh_friends_within(dh_ctx* ctx, const double* ctrs, int n, int d, int kind, c
   int* d_cnt = (int*)arena_get(ctx, (size_t)m * 4);
   unsigned long long* d_b = bits ? (unsigned long long*)arena_get(ctx, (size_t)m * nw * 8) : nullptr;
   if (!d_c || !d_x || !d_ai || !d_ct || !d_xt || !d_cnt || (bits && !d_b)) return DH_ERR_NOMEM;
-  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), dd * 8, s, d_c, d_ai, n, d, d_ct);
-  hipLaunchKernelGGL(fr_matmul, dim3((int)((md + kT - 1) / kT)), dim3(kT), dd * 8, s, d_x, d_ai, m, d, d_xt);
+  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), dd * 8, s, d_c, d_ai, n, d, d_ct, nullptr, 0);
+  hipLaunchKernelGGL(fr_matmul, dim3((int)((md + kT - 1) / kT)), dim3(kT), dd * 8, s, d_x, d_ai, m, d, d_xt, nullptr, 0);
   hipLaunchKernelGGL(fr_within, dim3((m + 63) / 64), dim3(64), (size_t)64 * d * 8, s, d_ct, d_xt, n, m, d, kind, d_cnt,
                      d_b, nw);
   if ((rc = launch_ok(ctx, "friends_within launch"))) return rc;
@@ -603,7 +860,7 @@ int dh_friends_draw(dh_ctx* ctx, const uint64_t* state6, int nsamp, const double
   int32_t* d_q = (int32_t*)arena_get(ctx, (size_t)nsamp * 4);
   uint64_t* d_o = (uint64_t*)arena_get(ctx, 48);
   if (!d_s || !d_c || !d_ax || !d_ai || !d_ct || !d_x || !d_q || !d_o) return DH_ERR_NOMEM;
-  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), dd * 8, s, d_c, d_ai, n, d, d_ct);
+  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), dd * 8, s, d_c, d_ai, n, d, d_ct, nullptr, 0);
   hipLaunchKernelGGL(fr_draw, dim3(1), dim3(64), (size_t)3 * d * 8, s, d_s, nsamp, n, d, kind, d_c, d_ct, d_ax, d_ai,
                      return_q, d_x, d_q, d_o, ctx->zki(), ctx->zwi(), ctx->zfi());
   if ((rc = launch_ok(ctx, "friends_draw launch"))) return rc;

@@ -271,6 +271,14 @@ __global__ void __launch_bounds__(kT) ns_start(NsArgs a) {
   }
 }
 
+// ---- friends bounds: every run's metric starts as the identity (RadFriends(ndim), cov=None) -----------------
+__global__ void __launch_bounds__(256) ns_fr_eye(double* am, int runs, int d) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x, dd = (size_t)d * d;
+  if (e >= (size_t)runs * dd) return;
+  const size_t k = e % dd;
+  am[e] = (k / d == k % d) ? 1.0 : 0.0;
+}
+
 // ---- policy (sampler.py:625-674 update_bound_if_needed) ------------------------
 // One workgroup looks at all runs.  With rebuild_sync the runs of the ensemble rebuild
 // TOGETHER: as soon as any run is due, every run that already samples from a bound joins
@@ -2199,7 +2207,7 @@ int dh_ns_set_boundary(dh_ctx* ctx, int ndim, const int8_t* bc) {
 }
 
 int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int queue_size, int sampler,
-                   int walks, int bound_multi, int rebuild_sync, double dlogz, double enlarge, int64_t max_fills,
+                   int walks, int bound, int rebuild_sync, double dlogz, double enlarge, int64_t max_fills,
                    int64_t max_iter,
                    const uint32_t* entropy_words, int n_words, uint32_t first_run, double* records,
                    double* dead_logl_out, double* live_logl_out, double* dead_u_out, double* live_u_out,
@@ -2231,6 +2239,14 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
   // Philox streams (throughput RNG mode); start points and frames keep their PCG64 streams
   // sampler 6 / 7 = the uniform sampler inside the bound (UniformBoundSampler) from PCG64 / Philox streams
   const bool philox = (sampler >= 3 && sampler <= 5) || sampler == 7;
+  // bound: 0 single ellipsoid, 1 multi-ellipsoid, 2 RadFriends (balls), 3 SupFriends (cubes); the friends bounds with
+  // the uniform sampler from PCG64 streams (sampler 6) at ndim <= 32 only
+  if (bound < 0 || bound > 3) return fail(ctx, DH_ERR_ARG, "ns_ensemble: bound code %d (0 single, 1 multi, 2 balls, 3 cubes)", bound);
+  if (bound >= 2 && (sampler != 6 || ndim > kMaxRegDim))
+    return fail(ctx, DH_ERR_ARG, "ns_ensemble: bound code %d (balls / cubes) needs sampler 6 (unif, PCG64) and ndim <= %d "
+                                 "(sampler %d, ndim %d)", bound, kMaxRegDim, sampler, ndim);
+  const int bound_multi = bound == 1 ? 1 : 0;
+  const int fr_kind = bound >= 2 ? bound - 2 : -1;  // friends.hip KIND_BALLS / KIND_CUBES
   if (sampler >= 6 && sampler <= 7)
     sampler = 3;  // internal code of `unif`
   else if (philox)
@@ -2382,6 +2398,15 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
                o_lit = take(want_pt ? (size_t)R * N * 4 : 8), o_pid = take(want_pt ? (size_t)R * a.cap * 4 : 8),
                o_pit = take(want_pt ? (size_t)R * a.cap * 4 : 8), o_pnc = take(want_pt ? (size_t)R * a.cap * 4 : 8),
                o_pso = take((size_t)R * 2048 * 2);
+  // friends bounds: the shapes' axes_inv (the metric am, cov, axes and ln V sit in b_ams, b_covs, b_axes, b_lv), the
+  // live sets in each shape's whitened frame, the batched update's workspace, bootstrap masks and their scratch
+  const bool fr = fr_kind >= 0;
+  const int fr_reps = bootstrap > 0 ? bootstrap : 0;
+  const size_t o_fai = take(fr ? (size_t)R * dd * 8 : 8), o_fct = take(fr ? (size_t)R * N * D * 8 : 8),
+               o_fws = take(fr ? friends_batch_ws_bytes(R, N, D, fr_reps) : 8),
+               o_fmk = take(fr && fr_reps ? (size_t)R * fr_reps * N : 8),
+               o_fsc = take(fr && fr_reps ? (size_t)R * fr_reps * 8 : 8), o_frr = take((size_t)R * 8),
+               o_fnc = take((size_t)R * 4);
   char* base = nullptr;
   (void)hipSetDevice(ctx->device);
   if (!hip_ok(ctx, hipMalloc((void**)&base, off), "hipMalloc(ns state)")) return DH_ERR_NOMEM;
@@ -2477,6 +2502,8 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
     return cleanup(DH_ERR_HIP);
 
   hipLaunchKernelGGL(ns_init, dim3(R), dim3(kT), 0, s, a, d_ent, n_words, first_run);
+  // (friends) the metric before the first update: RadFriends(ndim) / SupFriends(ndim) with cov=None, the identity
+  if (fr) hipLaunchKernelGGL(ns_fr_eye, dim3((unsigned)(((size_t)R * dd + 255) / 256)), dim3(256), 0, s, a.b_ams, R, D);
   int rc = eval_launch_dev(ctx, problem, R * N, a.live_u, a.live_v, a.live_logl);
   if (rc) return cleanup(rc);
   size_t lds_fin = 64;  // ns_finish: the keys by slot, the keys in order, the sorted slots (large sets: global memory)
@@ -2506,6 +2533,19 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
   const bool force_check = !(getenv("DH_NS_FORCE") && atoi(getenv("DH_NS_FORCE")) == 0);  // diagnostic: 0 = no forced rebuilds
   // bound.update of the runs in rebuild_mask (+ bootstrap expansion, + enlarge): sampler.py:492-508
   auto build_bounds = [&]() -> int {
+    if (fr) {
+      // RadFriends.update / SupFriends.update of the masked runs in one launch sequence (friends.hip), clustering in
+      // each run's previous metric; the bootstrap replicas' in-sample masks from the words ns_prepare drew
+      int rc = DH_OK;
+      unsigned char* mk = fr_reps ? (unsigned char*)(base + o_fmk) : nullptr;
+      if (fr_reps)
+        rc = boot_masks_launch(ctx, R, N, fr_reps, a.boot_ent, a.rebuild_mask, mk, (int*)(base + o_fsc));
+      if (rc) return rc;
+      return friends_update_launch(ctx, R, a.live_u, N, D, fr_kind, a.b_ams, fr_reps, mk, a.rebuild_mask,
+                                   enlarge != 1.0 ? a.enlarge_log : 0.0, base + o_fws, a.b_covs, a.b_ams, a.b_axes,
+                                   (double*)(base + o_fai), a.b_lv, (double*)(base + o_frr), (int*)(base + o_fnc),
+                                   a.bstatus, a.run_mode);
+    }
     int rc = rebuild_launch_masked(ctx, R, a.live_u, N, D, bound_multi ? 0 : 1, me, a.nells, a.bstatus, a.b_ctrs,
                                    a.b_covs, a.b_ams, a.b_axes, a.b_axl, a.b_lv, a.rebuild_mask);
     if (rc) return rc;
@@ -2626,6 +2666,17 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
         // the run's threshold; r_a = calls, r_b = flags
         dh::PhiloxKey key_unif = key_slice;
         key_unif.seed ^= 0x3C6EF372FE94F82Bull;
+        if (fr) {
+          // the shapes sit on the runs' CURRENT live points (prepare_sampler: bound.ctrs = live_u every fill,
+          // internal_samplers.py:232-233): each walking run's live set in its whitened frame, one launch
+          double* fai = (double*)(base + o_fai);
+          double* fct = (double*)(base + o_fct);
+          rc = friends_whiten_runs_launch(ctx, R, a.live_u, fai, N, D, fct, a.run_mode, MODE_BOUND);
+          if (!rc)
+            rc = unif_friends_launch_runs(ctx, problem, R * K, D, fr_kind, N, a.live_u, fct, a.b_axes, fai, d_bc,
+                                          a.q_rng, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out, a.run_loglstar,
+                                          a.run_mode, K, MODE_BOUND);
+        } else
         rc = unif_launch_runs(ctx, problem, R * K, D, D, R * me, a.b_ctrs, a.b_axes, a.b_ams, a.b_cum, 0.0, d_bc,
                               a.q_rng, 0, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out, a.run_loglstar,
                               a.run_mode, K, MODE_BOUND, philox ? &key_unif : nullptr, bound_multi ? a.nells : nullptr,

@@ -376,7 +376,8 @@ struct UnifArgs {
   const double* ams_p;     // m x N x N (padded precision matrices)
   const double* cumprob;   // m   cumsum(exp(logvol_ells - logvol))
   // RadFriends / SupFriends bound (fr_kind 0 balls, 1 cubes, -1: ellipsoids): m == 1, axes_t =
-  // the common shape sqrtm(cov), ams_p = its pseudo-inverse axes_inv (both symmetric, padded)
+  // the common shape sqrtm(cov), ams_p = its pseudo-inverse axes_inv (both symmetric, padded); in the ensemble form
+  // (run_me == 1) run r has its own shape (matrix r of axes_t / ams_p) and fr_n centres from row r * fr_n on
   int fr_kind, fr_n;
   const uint64_t* rng32_in;  // optional k x 2 {has_uint32, uinteger}: NumPy's buffered half of the 32-bit draws
   uint64_t* rng32_out;       // (integers(n) of the friends bounds consumes it); carried across lock-step rounds
@@ -486,8 +487,9 @@ __global__ void __launch_bounds__(64, 2) unif_kernel(UnifArgs a) {
           if (a.fr_n > 1) idx = (int)g.bounded32((uint32_t)(a.fr_n - 1));
 #pragma unroll
           for (int i = 0; i < N; ++i) acc[i] = 0.0;
-          matvec_sgpr<N>(as_const(a.axes_t), sx, lane, nc, acc);
-          const double* c = a.fr_ctrs + (size_t)idx * nc;
+          // (ensemble form: the run's own shape and live set, eb = run)
+          matvec_sgpr<N>(as_const(a.axes_t + eb * N * N), sx, lane, nc, acc);
+          const double* c = a.fr_ctrs + (eb * a.fr_n + idx) * nc;
 #pragma unroll
           for (int i = 0; i < N; ++i) x[i] = (FULL || i < nc) ? fma(fac, acc[i], c[i]) : 0.5;
           if (a.fr_n > 1) {
@@ -498,10 +500,11 @@ __global__ void __launch_bounds__(64, 2) unif_kernel(UnifArgs a) {
               if (FULL || i < nc) sx[i * 64 + lane] = x[i];
 #pragma unroll
             for (int i = 0; i < N; ++i) acc[i] = 0.0;
-            matvec_sgpr<N>(as_const(a.ams_p), sx, lane, nc, acc);
+            matvec_sgpr<N>(as_const(a.ams_p + eb * N * N), sx, lane, nc, acc);
             int q = 0;
+            const double* ct = a.fr_ct + eb * a.fr_n * nc;
             for (int j = 0; j < a.fr_n; ++j) {
-              cdptr cj = as_const(a.fr_ct + (size_t)j * nc);
+              cdptr cj = as_const(ct + (size_t)j * nc);
               double sd = 0.0;
 #pragma unroll
               for (int i = 0; i < N; ++i) {
@@ -1294,6 +1297,68 @@ extern "C" {
 
 
 }  // extern "C"
+
+int dh::unif_friends_launch_runs(dh_ctx* ctx, int problem, int k, int ndim, int kind, int n, const double* ctrs,
+                                 const double* ct, const double* axes, const double* axes_inv, const int8_t* bc,
+                                 const uint64_t* rng, double* u, double* v, double* logl, int32_t* ncalls,
+                                 int32_t* flags, uint64_t* rng_out, const double* run_loglstar, const int* run_mode,
+                                 int wpr, int my_mode) {
+  DH_CHECK_CTX(ctx);
+  if (k <= 0) return DH_OK;
+  if (!rng || !ctrs || !ct || !axes || !axes_inv || !run_mode || !run_loglstar || n < 1 || wpr < 1 || k % wpr ||
+      (kind != 0 && kind != 1))
+    return fail(ctx, DH_ERR_ARG, "unif_friends (ensemble): bad arguments");
+  if (ndim < 1 || ndim > kMaxRegDim) return fail(ctx, DH_ERR_ARG, "unif_friends: ndim=%d > %d not built", ndim, kMaxRegDim);
+  UnifArgs a;
+  a.propose_only = 0;
+  if (!get_problem(ctx, problem, &a.prob)) return DH_ERR_ARG;
+  if (a.prob.ndim != ndim) return fail(ctx, DH_ERR_ARG, "problem ndim %d != %d", a.prob.ndim, ndim);
+  const int runs = k / wpr, N = pad_dim(ndim);
+  const size_t mats = (size_t)runs * N * N * 8;
+  int rc = ensure_axes_t(ctx, 2 * mats);
+  if (rc) return rc;
+  double* at = ctx->axes_t;
+  double* ap = ctx->axes_t + (size_t)runs * N * N;
+  hipLaunchKernelGGL(pad_mats_kernel, dim3((runs * N * N + 255) / 256), dim3(256), 0, ctx->stream, axes, runs, ndim, N,
+                     1, at);
+  hipLaunchKernelGGL(pad_mats_kernel, dim3((runs * N * N + 255) / 256), dim3(256), 0, ctx->stream, axes_inv, runs, ndim,
+                     N, 1, ap);
+  a.run_loglstar = run_loglstar;
+  a.run_mode = run_mode;
+  a.wpr = wpr;
+  a.my_mode = my_mode;
+  a.run_nells = nullptr;
+  a.run_me = 1;
+  a.ph = dh::PhiloxKey{0, 0, 0};
+  a.k = k;
+  a.ndim = ndim;
+  a.ncdim = ndim;
+  a.m = 1;
+  a.loglstar = 0.0;
+  a.ctrs = ctrs;
+  a.axes_t = at;
+  a.ams_p = ap;
+  a.cumprob = nullptr;
+  a.fr_kind = kind;
+  a.fr_n = n;
+  a.fr_ctrs = ctrs;
+  a.fr_ct = ct;
+  a.rng32_in = nullptr;
+  a.rng32_out = nullptr;
+  a.bc = bc;
+  a.rng_in = rng;
+  a.max_tries = (int64_t)1 << 32;
+  a.u = u;
+  a.v = v;
+  a.logl = logl;
+  a.ncalls = ncalls;
+  a.flags = flags;
+  a.rng_out = rng_out;
+  a.zki = ctx->zki();
+  a.zwi = ctx->zwi();
+  a.zfi = ctx->zfi();
+  return unif_dispatch(ctx, a, N);
+}
 
 namespace {
 // host-pointer form of the batched UniformBoundSampler / UnitCubeSampler; key == nullptr: PCG64 streams from `rng`

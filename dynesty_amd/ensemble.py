@@ -126,6 +126,8 @@ def run_ensemble_device(prob, total_runs, base_seed=21, world=1, rank=0,
     by the device-resident loop (`dh_ns_ensemble`, one launch sequence for the
     whole shard), then the RCCL all-gather of the per-run records.  Seeds are
     keyed on the global run id, so the table does not depend on `world`.
+    bound: 'multi' | 'single', or 'balls' / 'cubes' (RadFriends / SupFriends) with
+    sample='unif' passed in **kw -- as Context.ns_ensemble takes them.
     on_failure: 'raise' (default) or 'nan' -- what to do with a run whose status is
     not 0; with 'nan' its ln Z / error / information are NaN in the table and
     `combine_logz` leaves it out."""

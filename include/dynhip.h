@@ -447,6 +447,14 @@ int dh_ns_consume(dh_ctx* ctx, int runs, int nlive, int queue_size, double dlogz
  * latency chain per interval instead of one per fill (64 C2 runs: 0.335 s at n = 1, 0.20 s at n >= 4).  0: chosen
  * from (sampler, nlive, queue_size) alone: ceil(nlive / K) for rwalk, ceil(1.3 nlive / (4.4 K)) for the slice
  * samplers, ceil(1.3 nlive / (1.7 K)) for unif; at most 16.
+ * bound (the bound code): 0 single ellipsoid, 1 multi-ellipsoid (MultiEllipsoid), 2 RadFriends ('balls'), 3 SupFriends
+ * ('cubes').  Codes 2 / 3 need sampler 6 (unif, PCG64 streams) and ndim <= 32; any other value or combination is
+ * DH_ERR_ARG.  With a friends bound every rebuild is RadFriends.update / SupFriends.update of the runs that are due
+ * (bounding.py:876-957, 1141-1222: clusters cut in the run's previous metric -- the identity before its first update --,
+ * the covariance, its square root, the radius from leave-one-out or from the B bootstrap replicas of the resident
+ * protocol), batched over the runs on the device (dh_friends_update_batch's kernels), then scale_to_logvol(logvol +
+ * ln enlarge) where enlarge != 1; a failed update (non-finite or singular covariance, zero radius) fails its run.  The
+ * shapes sit on the run's live points of the fill (prepare_sampler: bound.ctrs = live_u).  nbound counts the updates.
  * An rwalk walker that accepted no step returns its start point with that live point's own stored ln L (an exact tie, as
  * the reference's re-evaluation gives: internal_samplers.py:970-975, sampler.py:1107-1119).
  * max_fills (0: 10^6) bounds the fills the ENSEMBLE is taken through, idle ones included: a fill in which a run
@@ -454,7 +462,7 @@ int dh_ns_consume(dh_ctx* ctx, int runs, int nlive, int queue_size, double dlogz
  * its own fills than max_fills (n_fills_out is the same count). */
 int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim,
                    int queue_size, int sampler /* 0 rwalk, 1 rslice, 2 slice; + 3: unit-cube phase and proposals from hiprand Philox streams; 6 / 7 unif */,
-                   int walks /* or slices */, int bound_multi,
+                   int walks /* or slices */, int bound /* 0 single, 1 multi, 2 balls, 3 cubes */,
                    int rebuild_sync /* 1: all runs rebuild together, see below */, double dlogz,
                    double enlarge, int64_t max_fills, int64_t max_iter,
                    const uint32_t* entropy_words, int n_words, uint32_t first_run,
@@ -549,6 +557,18 @@ int dh_friends_update(dh_ctx* ctx, const double* pts, int n, int d, int kind,
 /* RadFriends.within / overlap / contains for m candidate points (bounding.py:777-793,
  * 1043-1064): counts[c] = number of balls / cubes containing x_c; bits (optional,
  * m x ceil(n/64) words) = which ones (bit j of word j/64). */
+/* dh_friends_update over `runs` point sets at once (the resident loop's rebuild): pts runs x n x d; am_prev
+ * (runs x d x d, NULL: no clustering); in_mask runs x nboot x n; active (runs int32, NULL: all) -- an inactive run's
+ * outputs are left as they are.  Outputs per run: cov / am / axes / axes_inv (runs x d x d), logvol, rmax,
+ * nclusters (optional) and status (DH_OK, or DH_ERR_VALUE where dh_friends_update fails; a failed run's other
+ * outputs are left as they are).  Every stage is one launch over all runs with no host synchronisation between them;
+ * per run the results are bit-identical to dh_friends_update's, logvol agrees to 1e-14 (the device's log / lgamma).
+ * The call itself returns DH_OK unless its arguments or the device fail. */
+int dh_friends_update_batch(dh_ctx* ctx, int runs, const double* pts, int n, int d, int kind,
+                            const double* am_prev, int nboot, const uint8_t* in_mask, const int32_t* active,
+                            double* cov, double* am, double* axes, double* axes_inv, double* logvol,
+                            double* rmax, int32_t* nclusters, int32_t* status);
+
 int dh_friends_within(dh_ctx* ctx, const double* ctrs, int n, int d, int kind,
                       const double* axes_inv, const double* x, int m, int32_t* counts,
                       uint64_t* bits);
