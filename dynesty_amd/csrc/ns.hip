@@ -64,13 +64,12 @@ struct NsArgs {
   long long first_ncall, update_interval;
   // run_nested's other stopping rules (sampler.py:1070-1093; dh_ns_set_option): maxiter / maxcall < 0 = none,
   // logl_max = +inf = none; add_live = 0: the record is the dead points' running evidence (no final live points)
-  long long maxiter, maxcall;
-  double logl_max;
-  int add_live;
+  long long maxiter = -1, maxcall = -1;
+  double logl_max = INFINITY;
+  int add_live = 1;
   int store_samples;
   long long* prof;   // optional (DH_NS_PROF=1): cycle counters of ns_consume's phases, run 0
   int rebuild_sync;  // 1: all bound-mode runs rebuild whenever any run is due (see ns_prepare)
-  int overlap;       // 1: a run whose bound is being rebuilt sits the fill out (its rebuild runs beside the others' walk)
   int rebuild_fill;  // 1: this fill builds bounds; 0: a run that is due waits (idle) for the next fill that does
   int serial_walk;   // diagnostic (DH_NS_SERIAL=1): ns_consume walks every queue with the one-wavefront routine
   // (round 6) the slot order of every run's live points for THIS fill, sorted by the generator pass's presort workgroups
@@ -341,7 +340,7 @@ __global__ void __launch_bounds__(kT) ns_prepare(NsArgs a) {
     r.need_rebuild = need;
     if (a.force) a.force[run] = 0;
     a.rebuild_mask[run] = need;
-    a.run_mode[run] = (r.due || (a.overlap && need) || (r.fpend && !a.rebuild_fill)) ? MODE_WAIT : r.mode;
+    a.run_mode[run] = (r.due || (r.fpend && !a.rebuild_fill)) ? MODE_WAIT : r.mode;
     if (a.fx_kind) a.fx_kind[run] = need ? 1 : 0;
     a.run_loglstar[run] = r.loglstar;
     a.run_scale[run] = r.scale;
@@ -2058,6 +2057,475 @@ inline NsConsumeFn ns_consume_for(int K) {
   const int ept = (K + kT - 1) / kT;
   return ept <= 1 ? ns_consume<1> : ept <= 2 ? ns_consume<2> : ept <= 4 ? ns_consume<4> : ns_consume<8>;
 }
+
+constexpr size_t kNsLdsMax = 150 * 1024;  // dynamic LDS a workgroup of ns_consume / ns_start / ns_finish may ask for
+
+inline int ns_serial_walk() { return env_int("DH_NS_SERIAL", 0) != 0 ? 1 : 0; }
+
+// the attribute is per device (and the call is cheap): set it on every call, on this context's device
+bool ns_set_lds(dh_ctx* ctx, int K, size_t lds_max, bool finish) {
+  const hipFuncAttribute at = hipFuncAttributeMaxDynamicSharedMemorySize;
+  return hip_ok(ctx, hipFuncSetAttribute((const void*)ns_consume_for(K), at, (int)lds_max), "hipFuncSetAttribute(ns_consume)") &&
+         hip_ok(ctx, hipFuncSetAttribute((const void*)ns_start, at, (int)lds_max), "hipFuncSetAttribute(ns_start)") &&
+         (!finish || hip_ok(ctx, hipFuncSetAttribute((const void*)ns_finish, at, (int)lds_max), "hipFuncSetAttribute(ns_finish)"));
+}
+
+// ---- dh_ns_ensemble, host side: plan (arguments, options, environment) -> layout (one allocation) -> stages ----
+
+// Everything a call decides before it touches the device.
+struct NsPlan {
+  NsArgs a;  // the scalar part; the arrays come from ns_arrays
+  int problem;
+  bool philox;  // proposals (and the unit-cube phase) from Philox streams
+  int fr_kind;  // friends.hip KIND_BALLS / KIND_CUBES, -1: ellipsoids
+  int fr_reps;  // bootstrap replicas of the friends update
+  int every;    // bounds are built every `every`-th fill
+  bool enlarged, force_check, presort_ok, want_pt, want_prof;
+  size_t lds_cons, lds_fin;
+  int64_t fills_cap;
+  int n_frames;
+  dh::PhiloxKey key;  // seed and first subsequence of the call (ns_philox_key)
+};
+
+// the arrays of the state allocation that no kernel takes through NsArgs
+struct NsAux {
+  uint32_t* ent;     // the caller's entropy words
+  int8_t* bc;        // periodic / reflective coordinates (dh_ns_set_boundary), null: all hard
+  char* boot_ws;     // bootstrap_expand_launch
+  unsigned short* presort;
+  // friends bounds: the shapes' axes_inv (the metric am, cov, axes and ln V sit in b_ams, b_covs, b_axes, b_lv), the
+  // live sets in each shape's whitened frame, the batched update's workspace, bootstrap masks and their scratch
+  double *fai, *fct;
+  char* fr_ws;
+  unsigned char* fr_mask;
+  int* fr_scratch;
+  double* frr;
+  int* fnc;
+};
+
+int ns_plan(dh_ctx* ctx, const double* opt, size_t n_bc, int problem, int runs, int nlive, int ndim, int queue_size,
+            int sampler, int walks, int bound, int rebuild_sync, double dlogz, double enlarge, int64_t max_fills,
+            int64_t max_iter, const uint32_t* entropy_words, int n_words, uint32_t first_run, const double* records,
+            bool store_samples, int n_pt_out, int bootstrap, int rebuild_every, NsPlan* plan) {
+  NsPlan& p = *plan;
+  p.want_pt = n_pt_out > 0;
+  if (p.want_pt && n_pt_out != 4)
+    return fail(ctx, DH_ERR_ARG, "ns_ensemble: the per-point outputs (id, it, nc, live it) come together");
+  ProblemDev pd;
+  if (!get_problem(ctx, problem, &pd)) return DH_ERR_ARG;
+  if (pd.ndim != ndim) return fail(ctx, DH_ERR_ARG, "problem ndim %d != %d", pd.ndim, ndim);
+  p.problem = problem;
+  // sampler 3 / 4 / 5 = rwalk / rslice / slice with the unit-cube phase and the proposals drawn from hiprand
+  // Philox streams (throughput RNG mode, DESIGN.md section 2); start points and frames keep their PCG64 streams
+  // sampler 6 / 7 = the uniform sampler inside the bound (UniformBoundSampler) from PCG64 / Philox streams
+  p.philox = (sampler >= 3 && sampler <= 5) || sampler == 7;
+  // bound: 0 single ellipsoid, 1 multi-ellipsoid, 2 RadFriends (balls), 3 SupFriends (cubes); the friends bounds with
+  // the uniform sampler from PCG64 streams (sampler 6) at ndim <= 32 only
+  if (bound < 0 || bound > 3) return fail(ctx, DH_ERR_ARG, "ns_ensemble: bound code %d (0 single, 1 multi, 2 balls, 3 cubes)", bound);
+  if (bound >= 2 && (sampler != 6 || ndim > kMaxRegDim))
+    return fail(ctx, DH_ERR_ARG, "ns_ensemble: bound code %d (balls / cubes) needs sampler 6 (unif, PCG64) and ndim <= %d "
+                                 "(sampler %d, ndim %d)", bound, kMaxRegDim, sampler, ndim);
+  const int bound_multi = bound == 1 ? 1 : 0;
+  p.fr_kind = bound >= 2 ? bound - 2 : -1;
+  p.fr_reps = bootstrap > 0 ? bootstrap : 0;
+  if (sampler >= 6 && sampler <= 7)
+    sampler = 3;  // internal code of `unif`
+  else if (p.philox)
+    sampler -= 3;
+  else if (sampler > 2)
+    sampler = -1;
+  if (runs < 1 || nlive < 4 || queue_size < 1 || walks < 1 || sampler < 0 || sampler > 3 || !entropy_words ||
+      n_words < 1 || !records || bootstrap < 0 || bootstrap == 1)
+    return fail(ctx, DH_ERR_ARG, "ns_ensemble: bad arguments");
+  // Above the register-resident dimensions (and for slice samplers at dimensions without an instantiation) the
+  // walker launches go to the wave-per-walker kernels of wide.hip, which take the same per-run arrays; above
+  // d = 44 the bound is the multi-workgroup Ellipsoid.update with the run mask, or -- bound='multi' -- the wide
+  // MultiEllipsoid.update: a host recursion over device node work, so a rebuild fill there synchronises the stream
+  // and reads the run mask back (the loop is no longer launch-ahead on those fills; the tree is a handful of nodes).
+  const int N = nlive, D = ndim, K = queue_size, R = runs;
+  // the register sort of the live slots is built for at most 32 keys per thread (sort_slots<32>); the LDS bound of
+  // ns_finish below is tighter today, this one is the sort's own
+  if (N > 65535) return fail(ctx, DH_ERR_ARG, "ns_ensemble: nlive %d > 65535 (slots travel as 16-bit indices)", N);
+  if (n_bc && (int)n_bc != ndim)
+    return fail(ctx, DH_ERR_ARG, "ns_ensemble: %d boundary flags for ndim %d", (int)n_bc, ndim);
+  const int me = bound_multi ? (N / (2 * D) > 0 ? N / (2 * D) : 1) : 1;
+  NsArgs& a = p.a;
+  a = NsArgs{};
+  a.runs = R;
+  a.nlive = N;
+  a.ndim = D;
+  a.K = K;
+  a.walks = walks;
+  a.sampler = sampler;
+  a.bound_multi = bound_multi;
+  a.max_ells = me;
+  a.cap = max_iter > 0 ? max_iter : 400000;
+  a.dlogz = dlogz;
+  a.enlarge_log = log(enlarge);
+  a.facc = fmin(1.0, fmax(1.0 / (double)(walks > 2 ? walks : 2), 0.5));
+  a.first_eff = 10.0;
+  a.first_ncall = 2ll * N;
+  // update_bound_interval_ratio (internal_samplers.py:495-502, 581-588, 737-744) * nlive
+  // (UniformBoundSampler keeps the base class's ratio 1, internal_samplers.py:88-94)
+  a.update_interval = (long long)(sampler == 3 ? 1 : sampler == 2 ? walks * D : walks) * N;
+  // the sampler's / run_nested's options a caller has set (dh_ns_set_option; NaN = the reference's default)
+  if (!std::isnan(opt[DH_NS_OPT_UPDATE_INTERVAL])) {
+    // update_interval as dynesty takes it (dynesty.py:213-234): a float is a multiple of nlive, an int a number of calls
+    const double v = opt[DH_NS_OPT_UPDATE_INTERVAL];
+    // (a value below one call is one call: the reference's max(min(round(...), maxsize), 1), dynesty.py:646-649)
+    a.update_interval = v >= 1.0 ? (long long)llround(v) : 1;
+  }
+  if (!std::isnan(opt[DH_NS_OPT_FIRST_MIN_NCALL])) a.first_ncall = (long long)llround(opt[DH_NS_OPT_FIRST_MIN_NCALL]);
+  if (!std::isnan(opt[DH_NS_OPT_FIRST_MIN_EFF])) a.first_eff = opt[DH_NS_OPT_FIRST_MIN_EFF];
+  if (!std::isnan(opt[DH_NS_OPT_MAXITER])) a.maxiter = (long long)llround(opt[DH_NS_OPT_MAXITER]);
+  if (!std::isnan(opt[DH_NS_OPT_MAXCALL])) a.maxcall = (long long)llround(opt[DH_NS_OPT_MAXCALL]);
+  if (!std::isnan(opt[DH_NS_OPT_LOGL_MAX])) a.logl_max = opt[DH_NS_OPT_LOGL_MAX];
+  if (!std::isnan(opt[DH_NS_OPT_ADD_LIVE])) a.add_live = opt[DH_NS_OPT_ADD_LIVE] != 0.0 ? 1 : 0;
+  // default (round 5): the reference's protocol; 0 = the late form (opt-in fast mode)
+  // (the uniform sampler has no start points, hence no forced update: for it the option is the ordering of the
+  // regular update alone)
+  a.forced_exact = 1;
+  if (!std::isnan(opt[DH_NS_OPT_FORCED_EXACT])) a.forced_exact = opt[DH_NS_OPT_FORCED_EXACT] != 0.0 ? 1 : 0;
+  if (a.maxcall >= 0 && a.maxcall < N)
+    return fail(ctx, DH_ERR_ARG, "ns_ensemble: maxcall %lld below the %d calls of the initial live points", a.maxcall, N);
+  a.bootstrap = bootstrap;
+  a.store_samples = store_samples ? 1 : 0;
+  a.rebuild_sync = rebuild_sync ? 1 : 0;
+  a.serial_walk = ns_serial_walk();
+  a.fin_stride = ns_fin_stride(N);
+  a.presort_stride = 2048;
+  p.enlarged = enlarge != 1.0;
+  // Bounds are built every rebuild_every-th fill (runs that become due in between wait, see ns_prepare); 0 = chosen
+  // here.  Once the period reaches the number of fills a run needs to spend its update interval, EVERY run is due (and
+  // waiting) by the next rebuild fill: the ensemble rebuilds together and walks together, one latency chain per
+  // interval instead of one per fill, with each run's own sequence untouched.  Longer periods only add idle fills
+  // (a fill in which every run waits costs its launches, ~75 us), shorter ones lose the synchrony -- measured flat
+  // from the interval upwards (64 C2 runs: 0.335 s at 1, 0.246 at 2, 0.29 at 3, 0.20 at 4 ... 12).  The interval in
+  // fills is nlive / K for rwalk (every walker spends `walks` calls), about nlive / (4.4 K) for the slice samplers
+  // (4.4 evaluations per slice step measured) and nlive / (1.7 K) for the uniform sampler; rounded up generously.
+  // The choice is a function of the arguments only -- never of timings -- so a run's global fill indices, and with
+  // them its Philox offsets, are reproducible.
+  p.every = env_int("DH_NS_REBUILD_EVERY", rebuild_every);
+  if (p.every <= 0) {
+    const double I = sampler == 0 ? (double)N / K : 1.3 * (double)N / ((sampler == 3 ? 1.7 : 4.4) * K);
+    p.every = (int)ceil(I - 1e-9);
+  }
+  if (p.every < 1) p.every = 1;
+  if (p.every > 16) p.every = 16;
+  p.want_prof = env_int("DH_NS_PROF", 0) != 0;
+  p.force_check = env_int("DH_NS_FORCE", 1) != 0;  // diagnostic: 0 = no forced rebuilds
+  if (K > kEPTMax * kT) return fail(ctx, DH_ERR_ARG, "ns_ensemble: queue_size %d > %d", K, kEPTMax * kT);
+  p.lds_fin = 64;  // ns_finish: the keys by slot, the keys in order, the sorted slots (large sets: global memory)
+  if (!ns_finish_big(N)) {
+    size_t Pf = 1;
+    while (Pf < (size_t)N) Pf <<= 1;
+    p.lds_fin += (size_t)N * 16 + (Pf > 256 ? Pf : 256) * 2;
+  }
+  p.lds_cons = ns_consume_lds(N, K);
+  if ((p.lds_cons > p.lds_fin ? p.lds_cons : p.lds_fin) > kNsLdsMax)
+    return fail(ctx, DH_ERR_ARG, "ns_ensemble: nlive/queue too large for LDS");
+  if (me > kMaxCum) return fail(ctx, DH_ERR_ARG, "ns_ensemble: nlive/(2 ndim) = %d ellipsoids > %d", me, kMaxCum);
+  p.fills_cap = max_fills > 0 ? max_fills : 1000000;
+  p.n_frames = R * me * (a.forced_exact ? 2 : 1);
+  // the slot order ns_consume needs can be sorted in front of the generator pass's grid (beside the walk) where the
+  // whole live set is sorted (not the compact form) and fits the generator's LDS
+  p.presort_ok = sampler == 0 && N <= 2048 && !ns_consume_compact(N, K) && env_int("DH_NS_PRESORT", 1) != 0;
+  // Philox keys: seed from the entropy words, subsequence = global walker slot (first_run + run) * K + w (independent
+  // of the sharding)
+  p.key.seed = ((unsigned long long)entropy_words[0] << 32) ^ (n_words > 1 ? entropy_words[1] : 0u) ^ 0x9E3779B97F4A7C15ull;
+  p.key.seq0 = (unsigned long long)first_run * (unsigned long long)K;
+  p.key.offset = 0;
+  return DH_OK;
+}
+
+// The key of one stage's Philox streams in one fill.  Every stage has a seed of its own, so that the stages' offset
+// schemes cannot meet.  Stages whose consumption depends on the data (unit cube, slice samplers, uniform sampler) get
+// 2^24 draws per walker and fill.  rwalk consumes a fixed number of 32-bit draws per walker and fill: per step
+// hiprand_normal4 x ceil(D / 4) and one hiprand_uniform_double (2 draws; padded to 4 so that a fill's block stays
+// 4-aligned).
+enum NsStage { STAGE_CUBE, STAGE_RWALK, STAGE_SLICE, STAGE_UNIF };
+dh::PhiloxKey ns_philox_key(const NsPlan& p, NsStage stage, int64_t fill) {
+  dh::PhiloxKey key = p.key;
+  if (stage == STAGE_RWALK) {
+    key.offset = (unsigned long long)fill * (unsigned long long)p.a.walks * (unsigned long long)(4 * ((p.a.ndim + 3) / 4) + 4);
+    return key;
+  }
+  key.seed ^= stage == STAGE_CUBE ? 0x5BD1E995C0BEull : 0x27D4EB2F511CEull;
+  if (stage == STAGE_UNIF) key.seed ^= 0x3C6EF372FE94F82Bull;
+  key.offset = (unsigned long long)fill << 24;
+  return key;
+}
+
+// Walks the list of state arrays: without a base it adds up their sizes (256-byte aligned), with one it hands out the
+// pointers and enqueues the initial fills.  An array that is not wanted takes no room and stays null.
+struct NsCarver {
+  dh_ctx* ctx;
+  char* base;
+  size_t off = 0;
+  bool ok = true;
+  template <class T>
+  void operator()(T*& p, size_t count, bool wanted = true, int fill = -1) {
+    p = nullptr;
+    if (!wanted) return;
+    const size_t bytes = count * sizeof(T);
+    if (base) {
+      p = (T*)(base + off);
+      if (fill >= 0 && ok) ok = hip_ok(ctx, hipMemsetAsync(base + off, fill, bytes, ctx->stream), "memset");
+    }
+    off += (bytes + 255) & ~(size_t)255;
+  }
+};
+
+// THE list of the ensemble's device arrays: element type (the pointer's), element count, wanted or not, initial fill
+void ns_arrays(NsCarver& c, const NsPlan& p, NsArgs& a, NsAux& x, int n_words, bool have_bc) {
+  const size_t R = (size_t)a.runs, N = (size_t)a.nlive, D = (size_t)a.ndim, K = (size_t)a.K, me = (size_t)a.max_ells;
+  const size_t cap = (size_t)a.cap, dd = D * D;
+  const bool fx = a.forced_exact != 0, fr = p.fr_kind >= 0, frb = fr && p.fr_reps > 0;
+  c(a.st, R);
+  c(a.live_u, R * N * D);
+  c(a.live_v, R * N * D);
+  c(a.live_logl, R * N);
+  c(a.dead_logl, R * cap);
+  c(a.dead_u, R * cap * D, a.store_samples != 0);
+  c(a.q_u0, R * K * D);
+  c(a.q_frame, R * K);
+  c(a.q_rng, R * K * 4);
+  c(a.q_rng_out, R * K * 4);
+  c(a.r_u, R * K * D);
+  c(a.r_v, R * K * D);
+  c(a.r_logl, R * K);
+  c(a.r_a, R * K);
+  c(a.r_b, R * K);
+  c(a.r_c, R * K);
+  c(a.r_d, R * K);
+  c(a.run_doubling, R);
+  c(a.run_loglstar, R);
+  c(a.run_scale, R);
+  c(a.run_mode, R);
+  c(a.rebuild_mask, R);
+  c(a.force, R, true, 0);
+  c(a.ndone, 16, true, 0);
+  c(a.nells, R, true, 0);
+  c(a.bstatus, R, true, 0);
+  c(a.b_ctrs, R * me * D);
+  c(a.b_covs, R * me * dd);
+  c(a.b_ams, R * me * dd);
+  c(a.b_axes, R * me * dd * (fx ? 2 : 1));  // (forced_exact: and the frames a forced update keeps, ns_shadow_axes)
+  c(a.b_axl, R * me * D);
+  c(a.b_lv, R * me);
+  c(a.records, R * 8);
+  c(x.ent, (size_t)n_words);
+  c(a.fin_ws, R * a.fin_stride);
+  c(a.b_cum, R * me);
+  c(a.boot_ent, R * 4);
+  c(a.run_shift, R);
+  c(a.force_first, R, true, 0x7f);
+  c(a.sel_ent, R * 4, fx);
+  c(x.bc, D + 8, have_bc);
+  c(a.undo_u, R * D, fx);
+  c(a.undo_slot, R, fx, 0xff);
+  c(a.fx_kind, R, fx, 0);
+  c(a.pass_mode, R, fx, 0);
+  c(x.boot_ws, a.bootstrap > 0 ? bootstrap_ws_bytes(a.runs, a.nlive, a.ndim, a.max_ells, a.bootstrap) : 0, a.bootstrap > 0);
+  c(a.live_it, R * N, p.want_pt, 0);
+  c(a.dead_id, R * cap, p.want_pt);
+  c(a.dead_it, R * cap, p.want_pt);
+  c(a.dead_nc, R * cap, p.want_pt);
+  c(x.presort, R * 2048);
+  c(x.fai, R * dd, fr);
+  c(x.fct, R * N * D, fr);
+  c(x.fr_ws, fr ? friends_batch_ws_bytes(a.runs, a.nlive, a.ndim, p.fr_reps) : 0, fr);
+  c(x.fr_mask, R * p.fr_reps * N, frb);
+  c(x.fr_scratch, R * p.fr_reps * 2, frb);
+  c(x.frr, R);
+  c(x.fnc, R);
+  c(a.prof, 32, p.want_prof, 0);
+  a.presort = x.presort;
+}
+
+// bound.update of the runs in rebuild_mask (+ bootstrap expansion, + enlarge): sampler.py:492-508
+int build_bounds(dh_ctx* ctx, const NsPlan& p, const NsArgs& a, const NsAux& x) {
+  const int R = a.runs, N = a.nlive, D = a.ndim, me = a.max_ells;
+  if (p.fr_kind >= 0) {
+    // RadFriends.update / SupFriends.update of the masked runs in one launch sequence (friends.hip), clustering in
+    // each run's previous metric; the bootstrap replicas' in-sample masks from the words ns_prepare drew
+    int rc = DH_OK;
+    if (p.fr_reps) rc = boot_masks_launch(ctx, R, N, p.fr_reps, a.boot_ent, a.rebuild_mask, x.fr_mask, x.fr_scratch);
+    if (rc) return rc;
+    return friends_update_launch(ctx, R, a.live_u, N, D, p.fr_kind, a.b_ams, p.fr_reps, x.fr_mask, a.rebuild_mask,
+                                 p.enlarged ? a.enlarge_log : 0.0, x.fr_ws, a.b_covs, a.b_ams, a.b_axes, x.fai, a.b_lv,
+                                 x.frr, x.fnc, a.bstatus, a.run_mode);
+  }
+  int rc = rebuild_launch_masked(ctx, R, a.live_u, N, D, a.bound_multi ? 0 : 1, me, a.nells, a.bstatus, a.b_ctrs,
+                                 a.b_covs, a.b_ams, a.b_axes, a.b_axl, a.b_lv, a.rebuild_mask);
+  if (rc) return rc;
+  if (a.bootstrap > 0) {
+    // bound.update(points, bootstrap=B): the expansion factor from B resampled replicas per rebuilding run,
+    // then scale_to_logvol(logvol + ndim ln(expand)) where it exceeds 1 (bounding.py:381-400, 688-703)
+    rc = bootstrap_expand_launch(ctx, R, a.live_u, N, D, a.bound_multi, me, a.bootstrap, a.boot_ent, a.rebuild_mask,
+                                 x.boot_ws, a.run_shift, nullptr, a.bstatus);
+    if (rc) return rc;
+    rc = enlarge_launch_masked(ctx, R, me, a.nells, D, a.b_covs, a.b_ams, a.b_axes, a.b_axl, a.b_lv, 0.0,
+                               a.rebuild_mask, a.run_shift);
+    if (rc) return rc;
+  }
+  if (p.enlarged)  // sampler.py:506-508
+    rc = enlarge_launch_masked(ctx, R, me, a.nells, D, a.b_covs, a.b_ams, a.b_axes, a.b_axl, a.b_lv, a.enlarge_log,
+                               a.rebuild_mask);
+  return rc;
+}
+
+// ns_select, the start points' coordinates (ns_gather) and their membership test against the bounds of the runs that
+// `modes` marks MODE_BOUND; pass: NsArgs::fx_pass, 0 outside the forced-exact protocol.  The uniform sampler starts
+// nowhere: selection only.  (Above the register-resident dimensions the test takes one wavefront per start point.)
+int select_and_test(dh_ctx* ctx, const NsPlan& p, NsArgs& a, int pass, const int* modes, int* first) {
+  const int R = a.runs, K = a.K, D = a.ndim;
+  hipStream_t s = ctx->stream;
+  a.fx_pass = pass;
+  hipLaunchKernelGGL(ns_select, dim3(R), dim3(kT), 0, s, a);
+  if (a.sampler == 3) return DH_OK;
+  hipLaunchKernelGGL(ns_gather, dim3((unsigned)(((size_t)R * K * D + 255) / 256)), dim3(256), 0, s, a);
+  if (!p.force_check) return DH_OK;
+  if (pass) hipLaunchKernelGGL(ns_pass_mask, dim3(1), dim3(kT), 0, s, a, pass);
+  return contains_runs_launch(ctx, a.q_u0, R * K, D, K, a.b_ctrs, a.b_ams, a.bound_multi ? a.nells : nullptr, a.max_ells,
+                              a.bound_multi ? 1 : 0, modes, MODE_BOUND, a.bstatus, a.force, first);
+}
+
+// The late form of the forced update (DH_NS_OPT_FORCED_EXACT = 0, the opt-in fast one).  Sampler.propose_live rebuilds
+// the bound at once when a start point lies outside it (sampler.py:484-489: a point accepted since the last update,
+// beyond the enlarged ellipsoids).  Here the run is flagged and rebuilds before its NEXT fill: the walkers of this fill
+// are already chosen, and a queue of K proposals is as stale in the reference.
+int bounds_late(dh_ctx* ctx, const NsPlan& p, NsArgs& a, const NsAux& x) {
+  if (a.rebuild_fill) {
+    const int rc = build_bounds(ctx, p, a, x);
+    if (rc) return rc;
+  }
+  return select_and_test(ctx, p, a, 0, a.run_mode, nullptr);
+}
+
+// The reference's protocol (DH_NS_OPT_FORCED_EXACT, the default of the Python layer since round 5), with ONE
+// rebuild chain per fill that builds bounds.  Pass 1: every run but those of this fill's regular updates
+// selects its queue (a pending run keeps the one it has) and the membership test finds the first start point
+// outside (force_first).  ns_force_prepare: a flagged run takes its forced update with this fill's bounds, or
+// -- in a fill that builds none -- keeps its queue and waits for one that does (its own sequence is unchanged).
+// Then the masked rebuild of the regular AND the forced updates together (the regular ones see the live set
+// without the newest point: ns_swap_undo; the forced ones as it is, their old frames kept: ns_shadow_axes),
+// pass 2 (the regular updates' runs select from their new bounds; the membership test is the reference's check
+// that a forced update worked, and flags a regular update's run whose newest point lies outside its new
+// bound: pending), and ns_reselect (entries behind the first one outside redraw their frames from the new
+// volumes with the same variates).
+int bounds_exact(dh_ctx* ctx, const NsPlan& p, NsArgs& a, const NsAux& x) {
+  const int R = a.runs;
+  hipStream_t s = ctx->stream;
+  const bool starts = a.sampler != 3;  // (the uniform sampler starts nowhere: no membership test, no forced update)
+  int rc = select_and_test(ctx, p, a, 1, a.pass_mode, a.force_first);
+  if (rc) return rc;
+  if (p.force_check && starts) hipLaunchKernelGGL(ns_force_prepare, dim3(1), dim3(kT), 0, s, a);
+  if (a.rebuild_fill) {
+    if (starts) hipLaunchKernelGGL(ns_shadow_axes, dim3(R, 16), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(ns_swap_undo, dim3(R), dim3(64), 0, s, a);
+    rc = build_bounds(ctx, p, a, x);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ns_swap_undo, dim3(R), dim3(64), 0, s, a);
+    rc = select_and_test(ctx, p, a, 2, a.pass_mode, nullptr);
+    if (rc) return rc;
+    if (starts) hipLaunchKernelGGL(ns_reselect, dim3(R), dim3(kT), 0, s, a);
+  }
+  a.fx_pass = 0;
+  return DH_OK;
+}
+
+// The walkers of one fill: the unit-cube proposals of the runs without a bound yet, then the sampler's launch for the
+// runs with one.  Leaves a.presorted set where the rwalk generator pass sorted the slots for this fill's ns_consume.
+int walk_stage(dh_ctx* ctx, const NsPlan& p, NsArgs& a, const NsAux& x, int64_t fill, bool cube_phase) {
+  const int R = a.runs, N = a.nlive, D = a.ndim, K = a.K, me = a.max_ells;
+  int rc = DH_OK;
+  if (cube_phase) {
+    const dh::PhiloxKey key = ns_philox_key(p, STAGE_CUBE, fill);
+    rc = unif_launch_runs(ctx, p.problem, R * K, D, D, 0, nullptr, nullptr, nullptr, nullptr, 0.0, nullptr, a.q_rng, 0,
+                          a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out, a.run_loglstar, a.run_mode, K, MODE_CUBE,
+                          p.philox ? &key : nullptr);
+    if (rc) return rc;
+  }
+  if (a.sampler == 3) {
+    // UniformBoundSampler.sample (internal_samplers.py:243-340): draws from the run's bound until one beats
+    // the run's threshold; r_a = calls, r_b = flags
+    if (p.fr_kind >= 0) {
+      // the shapes sit on the runs' CURRENT live points (prepare_sampler: bound.ctrs = live_u every fill,
+      // internal_samplers.py:232-233): each walking run's live set in its whitened frame, one launch
+      rc = friends_whiten_runs_launch(ctx, R, a.live_u, x.fai, N, D, x.fct, a.run_mode, MODE_BOUND);
+      if (rc) return rc;
+      return unif_friends_launch_runs(ctx, p.problem, R * K, D, p.fr_kind, N, a.live_u, x.fct, a.b_axes, x.fai, x.bc,
+                                      a.q_rng, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out, a.run_loglstar,
+                                      a.run_mode, K, MODE_BOUND);
+    }
+    const dh::PhiloxKey key = ns_philox_key(p, STAGE_UNIF, fill);
+    return unif_launch_runs(ctx, p.problem, R * K, D, D, R * me, a.b_ctrs, a.b_axes, a.b_ams, a.b_cum, 0.0, x.bc, a.q_rng,
+                            0, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out, a.run_loglstar, a.run_mode, K,
+                            MODE_BOUND, p.philox ? &key : nullptr, a.bound_multi ? a.nells : nullptr, me);
+  }
+  if (a.sampler == 0) {
+    const dh::PhiloxKey key = ns_philox_key(p, STAGE_RWALK, fill);
+    if (p.presort_ok) {
+      ctx->presort.keys = a.live_logl;
+      ctx->presort.out = x.presort;
+      ctx->presort.n = N;
+      ctx->presort.runs = R;
+      ctx->presort.stride = a.presort_stride;
+      ctx->presort.done = 0;
+    }
+    rc = rwalk_launch_runs(ctx, p.problem, R * K, D, D, a.q_u0, a.b_axes, p.n_frames, a.q_frame, 1.0, 0.0, a.walks, x.bc,
+                           a.q_rng, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out, a.run_loglstar, a.run_scale,
+                           a.run_mode, K, MODE_BOUND, p.philox ? &key : nullptr);
+    a.presorted = p.presort_ok && ctx->presort.done ? 1 : 0;
+    ctx->presort = dh_ctx::PresortReq();
+    return rc;
+  }
+  const dh::PhiloxKey key = ns_philox_key(p, STAGE_SLICE, fill);
+  return slice_launch_runs(ctx, p.problem, R * K, D, a.sampler - 1, a.q_u0, a.b_axes, p.n_frames, a.q_frame, 1.0, 0.0,
+                           a.walks, 0, a.q_rng, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.r_c, a.r_d, a.q_rng_out,
+                           a.run_loglstar, a.run_scale, a.run_mode, a.run_doubling, K, MODE_BOUND,
+                           p.philox ? &key : nullptr);
+}
+
+// the read-back: records, final live points, and of the dead points' arrays what each run wrote
+bool download(dh_ctx* ctx, const NsArgs& a, double* records, double* dead_logl, double* live_logl, double* dead_u,
+              double* live_u, int32_t* dead_id, int32_t* dead_it, int32_t* dead_nc, int32_t* live_it) {
+  const size_t R = (size_t)a.runs, N = (size_t)a.nlive, D = (size_t)a.ndim;
+  hipStream_t s = ctx->stream;
+  // `count` elements from element `at` on, where the caller wants the array
+  auto get = [&](auto* host, const auto* dev, size_t at, size_t count, const char* what) {
+    static_assert(sizeof *host == sizeof *dev, "element sizes");
+    return !host || hip_ok(ctx, hipMemcpyAsync(host + at, dev + at, count * sizeof *host, hipMemcpyDeviceToHost, s), what);
+  };
+  if (!get(records, a.records, 0, R * 8, "D2H records") || !get(live_logl, a.live_logl, 0, R * N, "D2H live") ||
+      !get(live_u, a.live_u, 0, R * N * D, "D2H live u") || !get(live_it, a.live_it, 0, R * N, "D2H live it"))
+    return false;
+  if (!dead_u && !dead_id && !dead_logl) return true;
+  // only the niter rows each run produced (the caller's runs x max_iter (x ndim) buffers may be
+  // far larger than what is touched here: 64 runs x 400 000 would be 300 MB of pageable copies)
+  if (!hip_ok(ctx, hipStreamSynchronize(s), "sync")) return false;
+  for (size_t r = 0; r < R; ++r) {
+    long long nit = (long long)records[r * 8 + 2];
+    if (nit > a.cap) nit = a.cap;
+    if (nit <= 0) continue;
+    const size_t o = r * (size_t)a.cap, n = (size_t)nit;
+    if (!get(dead_logl, a.dead_logl, o, n, "D2H dead") || !get(dead_u, a.dead_u, o * D, n * D, "D2H dead u") ||
+        !get(dead_id, a.dead_id, o, n, "D2H id") || !get(dead_it, a.dead_it, o, n, "D2H it") ||
+        !get(dead_nc, a.dead_nc, o, n, "D2H nc"))
+      return false;
+  }
+  return true;
+}
+
+void ns_prof_print(dh_ctx* ctx, const long long* prof, long long fills) {
+  long long h[32];
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipMemcpy(h, prof, sizeof h, hipMemcpyDeviceToHost);
+  fprintf(stderr, "ns_consume cycles (run 0, %lld fills): load+sort %lld | walk %lld | scan %lld | replay+state %lld | dead %lld | live store %lld ; fills integrated serially (all runs): %lld new plateau + %lld carried ; queues of run 0 left to the serial walk: %lld ; parallel walk: ranks %lld | counts %lld | scan+pick %lld | low ranks %lld | merge %lld | slots %lld\n",
+          fills, h[0], h[1], h[2], h[3], h[4], h[5], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15], h[7]);
+  fprintf(stderr, "  load+sort = live keys %lld | sort %lld | queue + sums %lld ; scan = ties %lld | weights + ln Z scan %lld | stop %lld | information %lld | rest %lld\n", h[16], h[17], h[0], h[18], h[19], h[20], h[21], h[2]);
+}
 }  // namespace
 
 extern "C" {
@@ -2080,26 +2548,15 @@ int dh_ns_consume(dh_ctx* ctx, int runs, int nlive, int queue_size, double dlogz
   // the K + 1 smallest live points (ns_consume_compact)
   if (N > 65535) return fail(ctx, DH_ERR_ARG, "ns_consume: nlive %d > 65535", N);
   const size_t lds_max = ns_consume_lds(N, K);
-  if (lds_max > 150 * 1024) return fail(ctx, DH_ERR_ARG, "ns_consume: nlive/queue too large for LDS");
+  if (lds_max > kNsLdsMax) return fail(ctx, DH_ERR_ARG, "ns_consume: nlive/queue too large for LDS");
   NsArgs a{};
-  a.serial_walk = (getenv("DH_NS_SERIAL") && atoi(getenv("DH_NS_SERIAL")) != 0) ? 1 : 0;
+  a.serial_walk = ns_serial_walk();
   a.runs = R;
   a.nlive = N;
   a.ndim = 0;  // log-likelihoods only: no coordinates travel
   a.K = K;
   a.walks = 1;
   a.cap = K;
-  a.maxiter = a.maxcall = -1;
-  a.logl_max = INFINITY;
-  a.add_live = 1;
-  a.forced_exact = 0;
-  a.force_first = nullptr;
-  a.presort = nullptr;
-  a.presort_stride = 0;
-  a.presorted = 0;
-  a.sel_ent = nullptr;
-  a.undo_u = nullptr;
-  a.undo_slot = nullptr;
   a.dlogz = dlogz;
   a.dead_rel = 1;
   arena_reset(ctx);
@@ -2149,9 +2606,7 @@ int dh_ns_consume(dh_ctx* ctx, int runs, int nlive, int queue_size, double dlogz
       !hip_ok(ctx, hipMemsetAsync(a.bstatus, 0, (size_t)R * 4, s), "memset") ||
       !hip_ok(ctx, hipMemsetAsync(a.trace_n, 0, (size_t)R * 8, s), "memset"))
     return DH_ERR_HIP;
-  if (!hip_ok(ctx, hipFuncSetAttribute((const void*)ns_consume_for(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max), "hipFuncSetAttribute(ns_consume)") ||
-      !hip_ok(ctx, hipFuncSetAttribute((const void*)ns_start, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max), "hipFuncSetAttribute(ns_start)"))
-    return DH_ERR_HIP;
+  if (!ns_set_lds(ctx, K, lds_max, false)) return DH_ERR_HIP;
   hipLaunchKernelGGL(ns_start, dim3(R), dim3(kT), 0, s, a);  // loglstar = min, lmax = max of live_logl
   hipLaunchKernelGGL(ns_consume_for(K), dim3(R), dim3(kT), lds_max, s, a);
   if (!hip_ok(ctx, hipGetLastError(), "ns_consume launch")) return DH_ERR_HIP;
@@ -2229,542 +2684,67 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
       bc.swap(c->ns_bc);
     }
   } shot(ctx);
-  const bool want_pt = dead_id_out || dead_it_out || dead_nc_out || live_it_out;
-  if (want_pt && !(dead_id_out && dead_it_out && dead_nc_out && live_it_out))
-    return fail(ctx, DH_ERR_ARG, "ns_ensemble: the per-point outputs (id, it, nc, live it) come together");
-  ProblemDev pd;
-  if (!get_problem(ctx, problem, &pd)) return DH_ERR_ARG;
-  if (pd.ndim != ndim) return fail(ctx, DH_ERR_ARG, "problem ndim %d != %d", pd.ndim, ndim);
-  // sampler 3 / 4 / 5 = rwalk / rslice / slice with the unit-cube phase and the proposals drawn from hiprand
-  // Philox streams (throughput RNG mode, DESIGN.md section 2); start points and frames keep their PCG64 streams
-  // sampler 6 / 7 = the uniform sampler inside the bound (UniformBoundSampler) from PCG64 / Philox streams
-  const bool philox = (sampler >= 3 && sampler <= 5) || sampler == 7;
-  // bound: 0 single ellipsoid, 1 multi-ellipsoid, 2 RadFriends (balls), 3 SupFriends (cubes); the friends bounds with
-  // the uniform sampler from PCG64 streams (sampler 6) at ndim <= 32 only
-  if (bound < 0 || bound > 3) return fail(ctx, DH_ERR_ARG, "ns_ensemble: bound code %d (0 single, 1 multi, 2 balls, 3 cubes)", bound);
-  if (bound >= 2 && (sampler != 6 || ndim > kMaxRegDim))
-    return fail(ctx, DH_ERR_ARG, "ns_ensemble: bound code %d (balls / cubes) needs sampler 6 (unif, PCG64) and ndim <= %d "
-                                 "(sampler %d, ndim %d)", bound, kMaxRegDim, sampler, ndim);
-  const int bound_multi = bound == 1 ? 1 : 0;
-  const int fr_kind = bound >= 2 ? bound - 2 : -1;  // friends.hip KIND_BALLS / KIND_CUBES
-  if (sampler >= 6 && sampler <= 7)
-    sampler = 3;  // internal code of `unif`
-  else if (philox)
-    sampler -= 3;
-  else if (sampler > 2)
-    sampler = -1;
-  if (runs < 1 || nlive < 4 || queue_size < 1 || walks < 1 || sampler < 0 || sampler > 3 || !entropy_words ||
-      n_words < 1 || !records || bootstrap < 0 || bootstrap == 1)
-    return fail(ctx, DH_ERR_ARG, "ns_ensemble: bad arguments");
-  // Above the register-resident dimensions (and for slice samplers at dimensions without an instantiation) the
-  // walker launches go to the wave-per-walker kernels of wide.hip, which take the same per-run arrays; above
-  // d = 44 the bound is the multi-workgroup Ellipsoid.update with the run mask, or -- bound='multi' -- the wide
-  // MultiEllipsoid.update: a host recursion over device node work, so a rebuild fill there synchronises the stream
-  // and reads the run mask back (the loop is no longer launch-ahead on those fills; the tree is a handful of nodes).
-  const int N = nlive, D = ndim, K = queue_size, R = runs;
-  // the register sort of the live slots is built for at most 32 keys per thread (sort_slots<32>); the LDS bound of
-  // ns_finish below is tighter today, this one is the sort's own
-  if (N > 65535) return fail(ctx, DH_ERR_ARG, "ns_ensemble: nlive %d > 65535 (slots travel as 16-bit indices)", N);
-  if (!shot.bc.empty() && (int)shot.bc.size() != ndim)
-    return fail(ctx, DH_ERR_ARG, "ns_ensemble: %d boundary flags for ndim %d", (int)shot.bc.size(), ndim);
-  const int me = bound_multi ? (N / (2 * D) > 0 ? N / (2 * D) : 1) : 1;
-  NsArgs a{};
-  a.runs = R;
-  a.nlive = N;
-  a.ndim = D;
-  a.K = K;
-  a.walks = walks;
-  a.sampler = sampler;
-  a.bound_multi = bound_multi;
-  a.max_ells = me;
-  a.cap = max_iter > 0 ? max_iter : 400000;
-  a.dlogz = dlogz;
-  a.enlarge_log = log(enlarge);
-  a.facc = fmin(1.0, fmax(1.0 / (double)(walks > 2 ? walks : 2), 0.5));
-  a.first_eff = 10.0;
-  a.first_ncall = 2ll * N;
-  // update_bound_interval_ratio (internal_samplers.py:495-502, 581-588, 737-744) * nlive
-  // (UniformBoundSampler keeps the base class's ratio 1, internal_samplers.py:88-94)
-  a.update_interval = (long long)(sampler == 3 ? 1 : sampler == 2 ? walks * D : walks) * N;
-  // the sampler's / run_nested's options a caller has set (dh_ns_set_option; NaN = the reference's default above)
-  a.maxiter = a.maxcall = -1;
-  a.logl_max = INFINITY;
-  a.add_live = 1;
-  a.forced_exact = 0;
-  a.force_first = nullptr;
-  a.presort = nullptr;
-  a.presort_stride = 0;
-  a.presorted = 0;
-  a.sel_ent = nullptr;
-  a.undo_u = nullptr;
-  a.undo_slot = nullptr;
-  {
-    const double* o = shot.opt;
-    if (!std::isnan(o[DH_NS_OPT_UPDATE_INTERVAL])) {
-      // update_interval as dynesty takes it (dynesty.py:213-234): a float is a multiple of nlive, an int a number of calls
-      const double v = o[DH_NS_OPT_UPDATE_INTERVAL];
-      // (a value below one call is one call: the reference's max(min(round(...), maxsize), 1), dynesty.py:646-649)
-      a.update_interval = v >= 1.0 ? (long long)llround(v) : 1;
-    }
-    if (!std::isnan(o[DH_NS_OPT_FIRST_MIN_NCALL])) a.first_ncall = (long long)llround(o[DH_NS_OPT_FIRST_MIN_NCALL]);
-    if (!std::isnan(o[DH_NS_OPT_FIRST_MIN_EFF])) a.first_eff = o[DH_NS_OPT_FIRST_MIN_EFF];
-    if (!std::isnan(o[DH_NS_OPT_MAXITER])) a.maxiter = (long long)llround(o[DH_NS_OPT_MAXITER]);
-    if (!std::isnan(o[DH_NS_OPT_MAXCALL])) a.maxcall = (long long)llround(o[DH_NS_OPT_MAXCALL]);
-    if (!std::isnan(o[DH_NS_OPT_LOGL_MAX])) a.logl_max = o[DH_NS_OPT_LOGL_MAX];
-    if (!std::isnan(o[DH_NS_OPT_ADD_LIVE])) a.add_live = o[DH_NS_OPT_ADD_LIVE] != 0.0 ? 1 : 0;
-    // default (round 5): the reference's protocol; 0 = the late form (opt-in fast mode)
-    // (the uniform sampler has no start points, hence no forced update: for it the option is the ordering of the
-    // regular update alone)
-    a.forced_exact = 1;
-    if (!std::isnan(o[DH_NS_OPT_FORCED_EXACT])) a.forced_exact = o[DH_NS_OPT_FORCED_EXACT] != 0.0 ? 1 : 0;
-    if (a.maxcall >= 0 && a.maxcall < N)
-      return fail(ctx, DH_ERR_ARG, "ns_ensemble: maxcall %lld below the %d calls of the initial live points", a.maxcall, N);
-  }
-  a.bootstrap = bootstrap;
-  a.store_samples = dead_u_out ? 1 : 0;
-  a.rebuild_sync = rebuild_sync ? 1 : 0;
-  a.serial_walk = (getenv("DH_NS_SERIAL") && atoi(getenv("DH_NS_SERIAL")) != 0) ? 1 : 0;
-  // Runs are independent, so WHEN a run's bound is rebuilt relative to the other runs' walks is free: a run that is
-  // due sits the fill out (run_mode MODE_WAIT) while its rebuild -- a latency chain that leaves most of the chip idle
-  // -- runs on a second stream beside the other runs' walkers, and walks from the new bound in the next fill.  Its own
-  // sequence (rebuild, then walk from the same live set with the same generator state) is unchanged: with PCG64
-  // streams every run's result is bit-identical to the serial schedule's (tests).  MEASURED, AND OFF BY DEFAULT
-  // (DH_NS_OVERLAP=1 switches it on): a rebuild beside a walk slows both (77 KB of LDS and 256 VGPRs per rebuild
-  // workgroup against two 230-VGPR walk workgroups per CU), and every run spends one more fill per bound update --
-  // 64 C2 runs 0.336 -> 0.328 s, 16 eggbox runs 0.127 -> 0.160 s, 16 C4 runs 11.1 -> 11.3 s.
-  const bool want_overlap = getenv("DH_NS_OVERLAP") && atoi(getenv("DH_NS_OVERLAP")) != 0;
-  if (want_overlap && a.forced_exact) {
-    // (the reference's protocol builds bounds inside the fill that needs them: nothing to overlap.  Said once, not
-    // silently ignored -- the protocol is the default since round 5, also for C callers that never set the option)
-    static bool warned = false;
-    if (!warned) {
-      fprintf(stderr, "dynhip: DH_NS_OVERLAP=1 has no effect while DH_NS_OPT_FORCED_EXACT is on (the default); "
-                      "set the option to 0 for the late form\n");
-      warned = true;
-    }
-  }
-  a.overlap = (want_overlap && !a.forced_exact) ? 1 : 0;
-  // Bounds are built every rebuild_every-th fill (runs that become due in between wait, see ns_prepare); 0 = chosen
-  // here.  Once the period reaches the number of fills a run needs to spend its update interval, EVERY run is due (and
-  // waiting) by the next rebuild fill: the ensemble rebuilds together and walks together, one latency chain per
-  // interval instead of one per fill, with each run's own sequence untouched.  Longer periods only add idle fills
-  // (a fill in which every run waits costs its launches, ~75 us), shorter ones lose the synchrony -- measured flat
-  // from the interval upwards (64 C2 runs: 0.335 s at 1, 0.246 at 2, 0.29 at 3, 0.20 at 4 ... 12).  The interval in
-  // fills is nlive / K for rwalk (every walker spends `walks` calls), about nlive / (4.4 K) for the slice samplers
-  // (4.4 evaluations per slice step measured) and nlive / (1.7 K) for the uniform sampler; rounded up generously.
-  // The choice is a function of the arguments only -- never of timings -- so a run's global fill indices, and with
-  // them its Philox offsets, are reproducible.
-  int every = rebuild_every;
-  if (const char* e = getenv("DH_NS_REBUILD_EVERY")) every = atoi(e);
-  if (every <= 0) {
-    const double I = sampler == 0 ? (double)N / K : 1.3 * (double)N / ((sampler == 3 ? 1.7 : 4.4) * K);
-    every = (int)ceil(I - 1e-9);
-  }
-  if (every < 1) every = 1;
-  if (every > 16) every = 16;
-  if (a.overlap) every = 1;
-  a.prof = nullptr;
-  if (getenv("DH_NS_PROF")) {
-    if (hipMalloc((void**)&a.prof, 32 * sizeof(long long)) != hipSuccess) a.prof = nullptr;
-    if (a.prof) (void)hipMemset(a.prof, 0, 32 * sizeof(long long));
-  }
+  NsPlan p;
+  int rc = ns_plan(ctx, shot.opt, shot.bc.size(), problem, runs, nlive, ndim, queue_size, sampler, walks, bound,
+                   rebuild_sync, dlogz, enlarge, max_fills, max_iter, entropy_words, n_words, first_run, records,
+                   dead_u_out != nullptr, !!dead_id_out + !!dead_it_out + !!dead_nc_out + !!live_it_out, bootstrap,
+                   rebuild_every, &p);
+  if (rc) return rc;
+  NsArgs a = p.a;
+  NsAux x;
+  const int R = a.runs, N = a.nlive, D = a.ndim, K = a.K;
   // ---- one allocation for all state ----
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t dd = (size_t)D * D;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += al(bytes);
-    return o;
-  };
-  const size_t o_st = take(sizeof(NsRun) * R), o_lu = take((size_t)R * N * D * 8), o_lv = take((size_t)R * N * D * 8),
-               o_ll = take((size_t)R * N * 8),
-               o_dl = take((size_t)R * a.cap * 8), o_du = take(dead_u_out ? (size_t)R * a.cap * D * 8 : 8), o_qu = take((size_t)R * K * D * 8),
-               o_qf = take((size_t)R * K * 4), o_qr = take((size_t)R * K * 32), o_qo = take((size_t)R * K * 32),
-               o_ru = take((size_t)R * K * D * 8), o_rv = take((size_t)R * K * D * 8),
-               o_rl = take((size_t)R * K * 8), o_ra = take((size_t)R * K * 4), o_rb = take((size_t)R * K * 4),
-               o_rc = take((size_t)R * K * 4), o_rd = take((size_t)R * K * 4), o_dbl = take((size_t)R * 4),
-               o_pl = take((size_t)R * 8), o_ps = take((size_t)R * 8), o_pm = take((size_t)R * 4),
-               o_rm = take((size_t)R * 4), o_fo = take((size_t)R * 4), o_nd = take(64), o_ne = take((size_t)R * 4),
-               o_bs = take((size_t)R * 4), o_bc = take((size_t)R * me * D * 8), o_bv = take((size_t)R * me * dd * 8),
-               o_ba = take((size_t)R * me * dd * 8), o_bx = take((size_t)R * me * dd * 8 * (a.forced_exact ? 2 : 1)),
-               o_bl = take((size_t)R * me * D * 8), o_bg = take((size_t)R * me * 8),
-               o_rec = take((size_t)R * 8 * 8), o_ent = take((size_t)n_words * 4),
-               o_fw = take((size_t)R * ns_fin_stride(N) * 8), o_cum = take((size_t)R * me * 8), o_be = take((size_t)R * 32),
-               o_rs = take((size_t)R * 8), o_ff = take((size_t)R * 4), o_se = take((size_t)R * 32),
-               o_bcf = take((size_t)D + 8), o_uu = take((size_t)R * D * 8), o_us = take((size_t)R * 4),
-               o_fk = take((size_t)R * 4), o_pmk = take((size_t)R * 4),
-               o_boot = take(bootstrap > 0 ? bootstrap_ws_bytes(R, N, D, me, bootstrap) : 8),
-               o_lit = take(want_pt ? (size_t)R * N * 4 : 8), o_pid = take(want_pt ? (size_t)R * a.cap * 4 : 8),
-               o_pit = take(want_pt ? (size_t)R * a.cap * 4 : 8), o_pnc = take(want_pt ? (size_t)R * a.cap * 4 : 8),
-               o_pso = take((size_t)R * 2048 * 2);
-  // friends bounds: the shapes' axes_inv (the metric am, cov, axes and ln V sit in b_ams, b_covs, b_axes, b_lv), the
-  // live sets in each shape's whitened frame, the batched update's workspace, bootstrap masks and their scratch
-  const bool fr = fr_kind >= 0;
-  const int fr_reps = bootstrap > 0 ? bootstrap : 0;
-  const size_t o_fai = take(fr ? (size_t)R * dd * 8 : 8), o_fct = take(fr ? (size_t)R * N * D * 8 : 8),
-               o_fws = take(fr ? friends_batch_ws_bytes(R, N, D, fr_reps) : 8),
-               o_fmk = take(fr && fr_reps ? (size_t)R * fr_reps * N : 8),
-               o_fsc = take(fr && fr_reps ? (size_t)R * fr_reps * 8 : 8), o_frr = take((size_t)R * 8),
-               o_fnc = take((size_t)R * 4);
+  NsCarver sizes{ctx, nullptr};
+  ns_arrays(sizes, p, a, x, n_words, !shot.bc.empty());
   char* base = nullptr;
   (void)hipSetDevice(ctx->device);
-  if (!hip_ok(ctx, hipMalloc((void**)&base, off), "hipMalloc(ns state)")) return DH_ERR_NOMEM;
-  hipStream_t main_stream = ctx->stream, rb_stream = nullptr;
-  hipEvent_t ev_prep = nullptr, ev_rb = nullptr;
+  if (!hip_ok(ctx, hipMalloc((void**)&base, sizes.off), "hipMalloc(ns state)")) return DH_ERR_NOMEM;
+  hipStream_t s = ctx->stream;
   auto cleanup = [&](int rc) {
-    ctx->stream = main_stream;
-    if (rb_stream) (void)hipStreamSynchronize(rb_stream);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ev_prep) (void)hipEventDestroy(ev_prep);
-    if (ev_rb) (void)hipEventDestroy(ev_rb);
-    if (rb_stream) (void)hipStreamDestroy(rb_stream);
     (void)hipFree(base);
     return rc;
   };
-  if (a.overlap &&
-      (!hip_ok(ctx, hipStreamCreateWithFlags(&rb_stream, hipStreamNonBlocking), "hipStreamCreate(rebuild)") ||
-       !hip_ok(ctx, hipEventCreateWithFlags(&ev_prep, hipEventDisableTiming), "hipEventCreate") ||
-       !hip_ok(ctx, hipEventCreateWithFlags(&ev_rb, hipEventDisableTiming), "hipEventCreate")))
+  NsCarver carve{ctx, base};
+  ns_arrays(carve, p, a, x, n_words, !shot.bc.empty());
+  if (!carve.ok ||
+      (x.bc && !hip_ok(ctx, hipMemcpyAsync(x.bc, shot.bc.data(), (size_t)D, hipMemcpyHostToDevice, s), "H2D bc")) ||
+      !hip_ok(ctx, hipMemcpyAsync(x.ent, entropy_words, (size_t)n_words * 4, hipMemcpyHostToDevice, s), "H2D"))
     return cleanup(DH_ERR_HIP);
-  a.st = (NsRun*)(base + o_st);
-  a.live_u = (double*)(base + o_lu);
-  a.live_v = (double*)(base + o_lv);
-  a.live_logl = (double*)(base + o_ll);
-  a.dead_logl = (double*)(base + o_dl);
-  a.dead_u = dead_u_out ? (double*)(base + o_du) : nullptr;
-  a.q_u0 = (double*)(base + o_qu);
-  a.q_frame = (int*)(base + o_qf);
-  a.q_rng = (uint64_t*)(base + o_qr);
-  a.q_rng_out = (uint64_t*)(base + o_qo);
-  a.r_u = (double*)(base + o_ru);
-  a.r_v = (double*)(base + o_rv);
-  a.r_logl = (double*)(base + o_rl);
-  a.r_a = (int*)(base + o_ra);
-  a.r_b = (int*)(base + o_rb);
-  a.r_c = (int*)(base + o_rc);
-  a.r_d = (int*)(base + o_rd);
-  a.run_doubling = (int*)(base + o_dbl);
-  a.run_loglstar = (double*)(base + o_pl);
-  a.run_scale = (double*)(base + o_ps);
-  a.run_mode = (int*)(base + o_pm);
-  a.rebuild_mask = (int*)(base + o_rm);
-  a.force = (int*)(base + o_fo);
-  a.ndone = (int*)(base + o_nd);
-  a.nells = (int*)(base + o_ne);
-  a.bstatus = (int*)(base + o_bs);
-  a.b_ctrs = (double*)(base + o_bc);
-  a.b_covs = (double*)(base + o_bv);
-  a.b_ams = (double*)(base + o_ba);
-  a.b_axes = (double*)(base + o_bx);
-  a.b_axl = (double*)(base + o_bl);
-  a.b_lv = (double*)(base + o_bg);
-  a.records = (double*)(base + o_rec);
-  a.fin_ws = (double*)(base + o_fw);
-  a.fin_stride = ns_fin_stride(N);
-  a.b_cum = (double*)(base + o_cum);
-  a.boot_ent = (uint64_t*)(base + o_be);
-  a.run_shift = (double*)(base + o_rs);
-  a.force_first = (int*)(base + o_ff);
-  a.presort = (const unsigned short*)(base + o_pso);
-  a.presort_stride = 2048;
-  a.presorted = 0;
-  a.sel_ent = a.forced_exact ? (uint64_t*)(base + o_se) : nullptr;
-  a.undo_u = a.forced_exact ? (double*)(base + o_uu) : nullptr;
-  a.undo_slot = a.forced_exact ? (int*)(base + o_us) : nullptr;
-  a.fx_kind = a.forced_exact ? (int*)(base + o_fk) : nullptr;
-  a.pass_mode = a.forced_exact ? (int*)(base + o_pmk) : nullptr;
-  a.fx_pass = 0;
-  if (want_pt) {
-    a.live_it = (int*)(base + o_lit);
-    a.dead_id = (int*)(base + o_pid);
-    a.dead_it = (int*)(base + o_pit);
-    a.dead_nc = (int*)(base + o_pnc);
-  }
-  uint32_t* d_ent = (uint32_t*)(base + o_ent);
-  hipStream_t s = ctx->stream;
-  const int8_t* d_bc = nullptr;  // periodic / reflective coordinates (dh_ns_set_boundary)
-  if (!shot.bc.empty()) {
-    if (!hip_ok(ctx, hipMemcpyAsync(base + o_bcf, shot.bc.data(), (size_t)D, hipMemcpyHostToDevice, s), "H2D bc"))
-      return cleanup(DH_ERR_HIP);
-    d_bc = (const int8_t*)(base + o_bcf);
-  }
-  if (want_pt && !hip_ok(ctx, hipMemsetAsync(base + o_lit, 0, (size_t)R * N * 4, s), "memset")) return cleanup(DH_ERR_HIP);
-  if (!hip_ok(ctx, hipMemsetAsync(base + o_nd, 0, 64, s), "memset") ||
-      !hip_ok(ctx, hipMemsetAsync(base + o_bs, 0, (size_t)R * 4, s), "memset") ||
-      !hip_ok(ctx, hipMemsetAsync(base + o_fo, 0, (size_t)R * 4, s), "memset") ||
-      !hip_ok(ctx, hipMemsetAsync(base + o_ff, 0x7f, (size_t)R * 4, s), "memset") ||
-      !hip_ok(ctx, hipMemsetAsync(base + o_us, 0xff, (size_t)R * 4, s), "memset") ||
-      !hip_ok(ctx, hipMemsetAsync(base + o_fk, 0, (size_t)R * 4, s), "memset") ||   // fx_kind
-      !hip_ok(ctx, hipMemsetAsync(base + o_pmk, 0, (size_t)R * 4, s), "memset") ||  // pass_mode (its own padded block)
-      !hip_ok(ctx, hipMemsetAsync(base + o_ne, 0, (size_t)R * 4, s), "memset") ||
-      !hip_ok(ctx, hipMemcpyAsync(d_ent, entropy_words, (size_t)n_words * 4, hipMemcpyHostToDevice, s), "H2D"))
-    return cleanup(DH_ERR_HIP);
-
-  hipLaunchKernelGGL(ns_init, dim3(R), dim3(kT), 0, s, a, d_ent, n_words, first_run);
+  hipLaunchKernelGGL(ns_init, dim3(R), dim3(kT), 0, s, a, x.ent, n_words, first_run);
   // (friends) the metric before the first update: RadFriends(ndim) / SupFriends(ndim) with cov=None, the identity
-  if (fr) hipLaunchKernelGGL(ns_fr_eye, dim3((unsigned)(((size_t)R * dd + 255) / 256)), dim3(256), 0, s, a.b_ams, R, D);
-  int rc = eval_launch_dev(ctx, problem, R * N, a.live_u, a.live_v, a.live_logl);
+  if (p.fr_kind >= 0)
+    hipLaunchKernelGGL(ns_fr_eye, dim3((unsigned)(((size_t)R * D * D + 255) / 256)), dim3(256), 0, s, a.b_ams, R, D);
+  rc = eval_launch_dev(ctx, problem, R * N, a.live_u, a.live_v, a.live_logl);
   if (rc) return cleanup(rc);
-  size_t lds_fin = 64;  // ns_finish: the keys by slot, the keys in order, the sorted slots (large sets: global memory)
-  if (!ns_finish_big(N)) {
-    size_t Pf = 1;
-    while (Pf < (size_t)N) Pf <<= 1;
-    lds_fin += (size_t)N * 16 + (Pf > 256 ? Pf : 256) * 2;
-  }
-  const size_t lds_cons = ns_consume_lds(N, K);
-  if (K > kEPTMax * kT) return cleanup(fail(ctx, DH_ERR_ARG, "ns_ensemble: queue_size %d > %d", K, kEPTMax * kT));
-  if (lds_cons > 150 * 1024) return cleanup(fail(ctx, DH_ERR_ARG, "ns_ensemble: nlive/queue too large for LDS"));
-  const size_t lds_max = lds_cons > lds_fin ? lds_cons : lds_fin;
-  if (lds_max > 150 * 1024) return cleanup(fail(ctx, DH_ERR_ARG, "ns_ensemble: nlive/queue too large for LDS"));
-  if (me > kMaxCum) return cleanup(fail(ctx, DH_ERR_ARG, "ns_ensemble: nlive/(2 ndim) = %d ellipsoids > %d", me, kMaxCum));
-  // the attribute is per device (and the call is cheap): set it on every call, on this context's device
-  if (!hip_ok(ctx, hipFuncSetAttribute((const void*)ns_consume_for(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max), "hipFuncSetAttribute(ns_consume)") ||
-      !hip_ok(ctx, hipFuncSetAttribute((const void*)ns_start, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max), "hipFuncSetAttribute(ns_start)") ||
-      !hip_ok(ctx, hipFuncSetAttribute((const void*)ns_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max), "hipFuncSetAttribute(ns_finish)"))
-    return cleanup(DH_ERR_HIP);
+  if (!ns_set_lds(ctx, K, p.lds_cons > p.lds_fin ? p.lds_cons : p.lds_fin, true)) return cleanup(DH_ERR_HIP);
   hipLaunchKernelGGL(ns_start, dim3(R), dim3(kT), 0, s, a);
   if (!hip_ok(ctx, hipGetLastError(), "ns_start launch")) return cleanup(DH_ERR_HIP);
-  const int64_t fills_cap = max_fills > 0 ? max_fills : 1000000;
   int64_t fill = 0;
-  int ndone = 0;
   int h_state[2] = {0, 1};  // [runs done, any run still in the unit-cube phase]
   bool cube_phase = true;
-  const bool force_check = !(getenv("DH_NS_FORCE") && atoi(getenv("DH_NS_FORCE")) == 0);  // diagnostic: 0 = no forced rebuilds
-  // bound.update of the runs in rebuild_mask (+ bootstrap expansion, + enlarge): sampler.py:492-508
-  auto build_bounds = [&]() -> int {
-    if (fr) {
-      // RadFriends.update / SupFriends.update of the masked runs in one launch sequence (friends.hip), clustering in
-      // each run's previous metric; the bootstrap replicas' in-sample masks from the words ns_prepare drew
-      int rc = DH_OK;
-      unsigned char* mk = fr_reps ? (unsigned char*)(base + o_fmk) : nullptr;
-      if (fr_reps)
-        rc = boot_masks_launch(ctx, R, N, fr_reps, a.boot_ent, a.rebuild_mask, mk, (int*)(base + o_fsc));
-      if (rc) return rc;
-      return friends_update_launch(ctx, R, a.live_u, N, D, fr_kind, a.b_ams, fr_reps, mk, a.rebuild_mask,
-                                   enlarge != 1.0 ? a.enlarge_log : 0.0, base + o_fws, a.b_covs, a.b_ams, a.b_axes,
-                                   (double*)(base + o_fai), a.b_lv, (double*)(base + o_frr), (int*)(base + o_fnc),
-                                   a.bstatus, a.run_mode);
-    }
-    int rc = rebuild_launch_masked(ctx, R, a.live_u, N, D, bound_multi ? 0 : 1, me, a.nells, a.bstatus, a.b_ctrs,
-                                   a.b_covs, a.b_ams, a.b_axes, a.b_axl, a.b_lv, a.rebuild_mask);
-    if (rc) return rc;
-    if (bootstrap > 0) {
-      // bound.update(points, bootstrap=B): the expansion factor from B resampled replicas per rebuilding run,
-      // then scale_to_logvol(logvol + ndim ln(expand)) where it exceeds 1 (bounding.py:381-400, 688-703)
-      rc = bootstrap_expand_launch(ctx, R, a.live_u, N, D, bound_multi, me, bootstrap, a.boot_ent, a.rebuild_mask,
-                                   base + o_boot, a.run_shift, nullptr, a.bstatus);
-      if (rc) return rc;
-      rc = enlarge_launch_masked(ctx, R, me, a.nells, D, a.b_covs, a.b_ams, a.b_axes, a.b_axl, a.b_lv, 0.0,
-                                 a.rebuild_mask, a.run_shift);
-      if (rc) return rc;
-    }
-    if (enlarge != 1.0)  // sampler.py:506-508
-      rc = enlarge_launch_masked(ctx, R, me, a.nells, D, a.b_covs, a.b_ams, a.b_axes, a.b_axl, a.b_lv,
-                                 a.enlarge_log, a.rebuild_mask);
-    return rc;
-  };
-  const int n_frames = R * me * (a.forced_exact ? 2 : 1);
-  const bool presort_ok = sampler == 0 && N <= 2048 && !ns_consume_compact(N, K) && !a.overlap &&
-                          !(getenv("DH_NS_PRESORT") && atoi(getenv("DH_NS_PRESORT")) == 0);
-  while (fill < fills_cap && ndone < R) {
-    for (int burst = 0; burst < 8 && fill < fills_cap; ++burst, ++fill) {
-      if (a.overlap && fill > 0 && !hip_ok(ctx, hipStreamWaitEvent(s, ev_rb, 0), "hipStreamWaitEvent(rebuild)"))
-        return cleanup(DH_ERR_HIP);
-      a.rebuild_fill = fill % every == 0 ? 1 : 0;
+  while (fill < p.fills_cap && h_state[0] < R) {
+    for (int burst = 0; burst < 8 && fill < p.fills_cap; ++burst, ++fill) {
+      a.rebuild_fill = fill % p.every == 0 ? 1 : 0;
       hipLaunchKernelGGL(ns_prepare, dim3(1), dim3(kT), 0, s, a);
-      if (a.overlap) {
-        // the bound work of this fill goes to the second stream (everything below enqueues on ctx->stream)
-        if (!hip_ok(ctx, hipEventRecord(ev_prep, s), "hipEventRecord") ||
-            !hip_ok(ctx, hipStreamWaitEvent(rb_stream, ev_prep, 0), "hipStreamWaitEvent(prepare)"))
-          return cleanup(DH_ERR_HIP);
-        ctx->stream = rb_stream;
-      }
-      if (!a.forced_exact) {
-        if (a.rebuild_fill) {
-          rc = build_bounds();
-          if (rc) return cleanup(rc);
-        }
-        if (a.overlap) {
-          ctx->stream = main_stream;
-          if (!hip_ok(ctx, hipEventRecord(ev_rb, rb_stream), "hipEventRecord")) return cleanup(DH_ERR_HIP);
-        }
-        hipLaunchKernelGGL(ns_select, dim3(R), dim3(kT), 0, s, a);
-        if (sampler != 3)
-          hipLaunchKernelGGL(ns_gather, dim3((unsigned)(((size_t)R * K * D + 255) / 256)), dim3(256), 0, s, a);
-        // Sampler.propose_live rebuilds the bound at once when a start point lies outside it (sampler.py:484-489:
-        // a point accepted since the last update, beyond the enlarged ellipsoids).  In this form (the opt-in fast one)
-        // the run is flagged and rebuilds before its NEXT fill: the walkers of this fill are already chosen, and a
-        // queue of K proposals is as stale in the reference.  (Above the register-resident dimensions: one wavefront
-        // per start point.)
-        if (force_check && sampler != 3) {
-          rc = contains_runs_launch(ctx, a.q_u0, R * K, D, K, a.b_ctrs, a.b_ams, bound_multi ? a.nells : nullptr, me,
-                                    bound_multi ? 1 : 0, a.run_mode, MODE_BOUND, a.bstatus, a.force, nullptr);
-          if (rc) return cleanup(rc);
-        }
-      } else {
-        // The reference's protocol (DH_NS_OPT_FORCED_EXACT, the default of the Python layer since round 5), with ONE
-        // rebuild chain per fill that builds bounds.  Pass 1: every run but those of this fill's regular updates
-        // selects its queue (a pending run keeps the one it has) and the membership test finds the first start point
-        // outside (force_first).  ns_force_prepare: a flagged run takes its forced update with this fill's bounds, or
-        // -- in a fill that builds none -- keeps its queue and waits for one that does (its own sequence is unchanged).
-        // Then the masked rebuild of the regular AND the forced updates together (the regular ones see the live set
-        // without the newest point: ns_swap_undo; the forced ones as it is, their old frames kept: ns_shadow_axes),
-        // pass 2 (the regular updates' runs select from their new bounds; the membership test is the reference's check
-        // that a forced update worked, and flags a regular update's run whose newest point lies outside its new
-        // bound: pending), and ns_reselect (entries behind the first one outside redraw their frames from the new
-        // volumes with the same variates).
-        const dim3 ggrid((unsigned)(((size_t)R * K * D + 255) / 256));
-        const bool starts = sampler != 3;  // (the uniform sampler starts nowhere: no membership test, no forced update)
-        a.fx_pass = 1;
-        hipLaunchKernelGGL(ns_select, dim3(R), dim3(kT), 0, s, a);
-        if (starts) hipLaunchKernelGGL(ns_gather, ggrid, dim3(256), 0, s, a);
-        if (force_check && starts) {
-          hipLaunchKernelGGL(ns_pass_mask, dim3(1), dim3(kT), 0, s, a, 1);
-          rc = contains_runs_launch(ctx, a.q_u0, R * K, D, K, a.b_ctrs, a.b_ams, bound_multi ? a.nells : nullptr, me,
-                                    bound_multi ? 1 : 0, a.pass_mode, MODE_BOUND, a.bstatus, a.force, a.force_first);
-          if (rc) return cleanup(rc);
-          hipLaunchKernelGGL(ns_force_prepare, dim3(1), dim3(kT), 0, s, a);
-        }
-        if (a.rebuild_fill) {
-          if (starts) hipLaunchKernelGGL(ns_shadow_axes, dim3(R, 16), dim3(256), 0, s, a);
-          hipLaunchKernelGGL(ns_swap_undo, dim3(R), dim3(64), 0, s, a);
-          rc = build_bounds();
-          if (rc) return cleanup(rc);
-          hipLaunchKernelGGL(ns_swap_undo, dim3(R), dim3(64), 0, s, a);
-          a.fx_pass = 2;
-          hipLaunchKernelGGL(ns_select, dim3(R), dim3(kT), 0, s, a);
-          if (starts) hipLaunchKernelGGL(ns_gather, ggrid, dim3(256), 0, s, a);
-          if (force_check && starts) {
-            hipLaunchKernelGGL(ns_pass_mask, dim3(1), dim3(kT), 0, s, a, 2);
-            rc = contains_runs_launch(ctx, a.q_u0, R * K, D, K, a.b_ctrs, a.b_ams, bound_multi ? a.nells : nullptr, me,
-                                      bound_multi ? 1 : 0, a.pass_mode, MODE_BOUND, a.bstatus, a.force, nullptr);
-            if (rc) return cleanup(rc);
-          }
-          if (starts) hipLaunchKernelGGL(ns_reselect, dim3(R), dim3(kT), 0, s, a);
-        }
-        a.fx_pass = 0;
-      }
-      // Philox keys: seed from the entropy words (one per stage, so that the stages' offset schemes cannot
-      // meet), subsequence = global walker slot (first_run + run) * K + w (independent of the sharding)
-      dh::PhiloxKey key;
-      key.seed = ((unsigned long long)entropy_words[0] << 32) ^ (n_words > 1 ? entropy_words[1] : 0u) ^ 0x9E3779B97F4A7C15ull;
-      key.seq0 = (unsigned long long)first_run * (unsigned long long)K;
-      // stages whose consumption depends on the data (unit cube, slice samplers): 2^24 draws per walker and fill
-      dh::PhiloxKey key_cube = key, key_slice = key;
-      key_cube.seed ^= 0x5BD1E995C0BEull;
-      key_slice.seed ^= 0x27D4EB2F511CEull;
-      key_cube.offset = key_slice.offset = (unsigned long long)fill << 24;
-      if (cube_phase) {
-        rc = unif_launch_runs(ctx, problem, R * K, D, D, 0, nullptr, nullptr, nullptr, nullptr, 0.0, nullptr,
-                              a.q_rng, 0, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out, a.run_loglstar,
-                              a.run_mode, K, MODE_CUBE, philox ? &key_cube : nullptr);
-        if (rc) return cleanup(rc);
-      }
-      if (sampler == 3) {
-        // UniformBoundSampler.sample (internal_samplers.py:243-340): draws from the run's bound until one beats
-        // the run's threshold; r_a = calls, r_b = flags
-        dh::PhiloxKey key_unif = key_slice;
-        key_unif.seed ^= 0x3C6EF372FE94F82Bull;
-        if (fr) {
-          // the shapes sit on the runs' CURRENT live points (prepare_sampler: bound.ctrs = live_u every fill,
-          // internal_samplers.py:232-233): each walking run's live set in its whitened frame, one launch
-          double* fai = (double*)(base + o_fai);
-          double* fct = (double*)(base + o_fct);
-          rc = friends_whiten_runs_launch(ctx, R, a.live_u, fai, N, D, fct, a.run_mode, MODE_BOUND);
-          if (!rc)
-            rc = unif_friends_launch_runs(ctx, problem, R * K, D, fr_kind, N, a.live_u, fct, a.b_axes, fai, d_bc,
-                                          a.q_rng, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out, a.run_loglstar,
-                                          a.run_mode, K, MODE_BOUND);
-        } else
-        rc = unif_launch_runs(ctx, problem, R * K, D, D, R * me, a.b_ctrs, a.b_axes, a.b_ams, a.b_cum, 0.0, d_bc,
-                              a.q_rng, 0, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out, a.run_loglstar,
-                              a.run_mode, K, MODE_BOUND, philox ? &key_unif : nullptr, bound_multi ? a.nells : nullptr,
-                              me);
-      } else if (sampler == 0) {
-        // 32-bit draws one walker consumes per fill: per step hiprand_normal4 x ceil(D / 4) and one
-        // hiprand_uniform_double (2 draws; padded to 4 so that a fill's block stays 4-aligned)
-        key.offset = (unsigned long long)fill * (unsigned long long)walks * (unsigned long long)(4 * ((D + 3) / 4) + 4);
-        // the slot order ns_consume needs, sorted in front of the generator pass's grid (beside the walk) where the
-        // whole live set is sorted (not the compact form) and fits the generator's LDS
-        if (presort_ok) {
-          ctx->presort.keys = a.live_logl;
-          ctx->presort.out = (unsigned short*)(base + o_pso);
-          ctx->presort.n = N;
-          ctx->presort.runs = R;
-          ctx->presort.stride = a.presort_stride;
-          ctx->presort.done = 0;
-        }
-        rc = rwalk_launch_runs(ctx, problem, R * K, D, D, a.q_u0, a.b_axes, n_frames, a.q_frame, 1.0, 0.0, walks,
-                               d_bc, a.q_rng, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.q_rng_out,
-                               a.run_loglstar, a.run_scale, a.run_mode, K, MODE_BOUND, philox ? &key : nullptr);
-        a.presorted = presort_ok && ctx->presort.done ? 1 : 0;
-        ctx->presort = dh_ctx::PresortReq();
-      }
-      else
-        rc = slice_launch_runs(ctx, problem, R * K, D, sampler - 1, a.q_u0, a.b_axes, n_frames, a.q_frame, 1.0,
-                               0.0, walks, 0, a.q_rng, a.r_u, a.r_v, a.r_logl, a.r_a, a.r_b, a.r_c, a.r_d,
-                               a.q_rng_out, a.run_loglstar, a.run_scale, a.run_mode, a.run_doubling, K,
-                               MODE_BOUND, philox ? &key_slice : nullptr);
+      rc = a.forced_exact ? bounds_exact(ctx, p, a, x) : bounds_late(ctx, p, a, x);
+      if (!rc) rc = walk_stage(ctx, p, a, x, fill, cube_phase);
       if (rc) return cleanup(rc);
-      hipLaunchKernelGGL(ns_consume_for(K), dim3(R), dim3(kT), lds_cons, s, a);
+      hipLaunchKernelGGL(ns_consume_for(K), dim3(R), dim3(kT), p.lds_cons, s, a);
       a.presorted = 0;
     }
     if (!hip_ok(ctx, hipMemcpyAsync(h_state, a.ndone, 8, hipMemcpyDeviceToHost, s), "D2H ndone") ||
         !hip_ok(ctx, hipStreamSynchronize(s), "sync"))
       return cleanup(DH_ERR_HIP);
-    ndone = h_state[0];
     if (!h_state[1]) cube_phase = false;  // (as of the last ns_prepare: every run has its first bound)
   }
-  if (a.overlap && fill > 0 && !hip_ok(ctx, hipStreamWaitEvent(s, ev_rb, 0), "hipStreamWaitEvent(rebuild)"))
-    return cleanup(DH_ERR_HIP);
-  hipLaunchKernelGGL(ns_finish, dim3(R), dim3(kT), lds_fin, s, a);
+  hipLaunchKernelGGL(ns_finish, dim3(R), dim3(kT), p.lds_fin, s, a);
   if (!hip_ok(ctx, hipGetLastError(), "ns launch") ||
-      !hip_ok(ctx, hipMemcpyAsync(records, a.records, (size_t)R * 64, hipMemcpyDeviceToHost, s), "D2H records"))
+      !download(ctx, a, records, dead_logl_out, live_logl_out, dead_u_out, live_u_out, dead_id_out, dead_it_out,
+                dead_nc_out, live_it_out))
     return cleanup(DH_ERR_HIP);
-  if (live_logl_out &&
-      !hip_ok(ctx, hipMemcpyAsync(live_logl_out, a.live_logl, (size_t)R * N * 8, hipMemcpyDeviceToHost, s),
-              "D2H live"))
-    return cleanup(DH_ERR_HIP);
-  if (live_u_out &&
-      !hip_ok(ctx, hipMemcpyAsync(live_u_out, a.live_u, (size_t)R * N * D * 8, hipMemcpyDeviceToHost, s),
-              "D2H live u"))
-    return cleanup(DH_ERR_HIP);
-  if (want_pt &&
-      !hip_ok(ctx, hipMemcpyAsync(live_it_out, a.live_it, (size_t)R * N * 4, hipMemcpyDeviceToHost, s), "D2H live it"))
-    return cleanup(DH_ERR_HIP);
-  if (dead_u_out || want_pt || dead_logl_out) {
-    // only the niter rows each run produced (the caller's runs x max_iter (x ndim) buffers may be
-    // far larger than what is touched here: 64 runs x 400 000 would be 300 MB of pageable copies)
-    if (!hip_ok(ctx, hipStreamSynchronize(s), "sync")) return cleanup(DH_ERR_HIP);
-    for (int r = 0; r < R; ++r) {
-      long long nit = (long long)records[(size_t)r * 8 + 2];
-      if (nit > a.cap) nit = a.cap;
-      if (nit <= 0) continue;
-      const size_t o = (size_t)r * a.cap;
-      if (dead_logl_out && !hip_ok(ctx, hipMemcpyAsync(dead_logl_out + o, a.dead_logl + o, (size_t)nit * 8,
-                                                       hipMemcpyDeviceToHost, s), "D2H dead"))
-        return cleanup(DH_ERR_HIP);
-      if (dead_u_out && !hip_ok(ctx, hipMemcpyAsync(dead_u_out + o * D, a.dead_u + o * D, (size_t)nit * D * 8,
-                                                    hipMemcpyDeviceToHost, s), "D2H dead u"))
-        return cleanup(DH_ERR_HIP);
-      if (want_pt &&
-          (!hip_ok(ctx, hipMemcpyAsync(dead_id_out + o, a.dead_id + o, (size_t)nit * 4, hipMemcpyDeviceToHost, s), "D2H id") ||
-           !hip_ok(ctx, hipMemcpyAsync(dead_it_out + o, a.dead_it + o, (size_t)nit * 4, hipMemcpyDeviceToHost, s), "D2H it") ||
-           !hip_ok(ctx, hipMemcpyAsync(dead_nc_out + o, a.dead_nc + o, (size_t)nit * 4, hipMemcpyDeviceToHost, s), "D2H nc")))
-        return cleanup(DH_ERR_HIP);
-    }
-  }
   if (n_fills_out) *n_fills_out = fill;
-  if (a.prof) {
-    long long h[32];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h, a.prof, sizeof h, hipMemcpyDeviceToHost);
-    fprintf(stderr, "ns_consume cycles (run 0, %lld fills): load+sort %lld | walk %lld | scan %lld | replay+state %lld | dead %lld | live store %lld ; fills integrated serially (all runs): %lld new plateau + %lld carried ; queues of run 0 left to the serial walk: %lld ; parallel walk: ranks %lld | counts %lld | scan+pick %lld | low ranks %lld | merge %lld | slots %lld\n",
-            (long long)fill, h[0], h[1], h[2], h[3], h[4], h[5], h[8], h[9], h[10], h[11], h[12], h[13], h[14], h[15], h[7]);
-    fprintf(stderr, "  load+sort = live keys %lld | sort %lld | queue + sums %lld ; scan = ties %lld | weights + ln Z scan %lld | stop %lld | information %lld | rest %lld\n", h[16], h[17], h[0], h[18], h[19], h[20], h[21], h[2]);
-    (void)hipFree(a.prof);
-  }
+  if (a.prof) ns_prof_print(ctx, a.prof, (long long)fill);
   return cleanup(DH_OK);
 }
 

@@ -472,8 +472,8 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim,
                    int rebuild_every /* bounds are built every n-th fill, runs due in between wait; 0: chosen from the shape */);
 
 /* Options of the resident run loop that the reference takes in NestedSampler(...) / run_nested(...) and that
- * dh_ns_ensemble otherwise fixes at the reference's defaults.  They are context state: set before a
- * dh_ns_ensemble call, they hold until set again; value NaN restores the default.
+ * dh_ns_ensemble otherwise fixes at the reference's defaults.  Set before a dh_ns_ensemble call, they
+ * apply to that call alone (see below); value NaN restores the default.
  *   DH_NS_OPT_UPDATE_INTERVAL   calls between bound updates (dynesty.py:213-234 `update_interval` as a number of calls;
  *                               a caller holding the ratio form multiplies by nlive); default: the sampler's ratio
  *                               (1 unif, walks rwalk, slices rslice, slices * ndim slice) * nlive
@@ -499,7 +499,7 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim,
  *                               0 = the late form: the run is flagged, walks this fill from the old bound and rebuilds
  *                               before its next fill; the regular bound includes the newest point (9-20 % fewer bound
  *                               updates than the reference; a few per cent faster).  The uniform sampler has no start
- *                               points: the option does not apply.  1 switches DH_NS_OVERLAP off.
+ *                               points: the option does not apply.
  * A run ended by maxiter / maxcall / logl_max ends normally (status 0), as the reference's does.
  * Options (and dh_ns_set_boundary's flags) apply to the NEXT dh_ns_ensemble call only: that call takes them and the
  * context forgets them, however the call ends. */
