@@ -251,6 +251,26 @@ int dh_problem_create(dh_ctx* ctx, int ndim, int like_id, const double* like_par
   if (prior_id < 0 || prior_id > DH_PRIOR_NORMAL || n_prior_par < need_prior)
     return fail(ctx, DH_ERR_ARG, "prior id %d needs %d parameters, got %d", prior_id, need_prior,
                 n_prior_par);
+  if (!like_par || (n_prior_par > 0 && !prior_par))
+    return fail(ctx, DH_ERR_ARG, "problem_create: null pointer");
+  // GAUSS_PREC: v^T P v only sees the symmetric part of P, and the evaluators read different triangles
+  // of it (upper, lower, all of it), so every copy holds (P + P^T) / 2.  (a + a) / 2 == a: a symmetric
+  // P is stored as given.
+  std::vector<double> lp(like_par, like_par + n_like_par);
+  if (like_id == DH_LIKE_GAUSS_PREC)
+    for (int i = 0; i < ndim; ++i)
+      for (int j = 0; j < ndim; ++j) {
+        const size_t ij = 1 + (size_t)i * ndim + j, ji = 1 + (size_t)j * ndim + i;
+        lp[ij] = 0.5 * (like_par[ij] + like_par[ji]);
+      }
+  // transposed + zero-padded copy for the column-sweep mat-vec of the walk kernels (of the
+  // symmetrised P: its transpose is itself, bit for bit)
+  const bool want_t = like_id == DH_LIKE_GAUSS_PREC && ndim <= kMaxRegDim;
+  const int N = want_t ? pad_dim(ndim) : 0;
+  std::vector<double> pt((size_t)N * N, 0.0);
+  if (want_t)
+    for (int i = 0; i < ndim; ++i)
+      for (int j = 0; j < ndim; ++j) pt[(size_t)j * N + i] = lp[1 + (size_t)i * ndim + j];
   dh_problem_rec r;
   r.live = true;
   r.ndim = ndim;
@@ -259,28 +279,27 @@ int dh_problem_create(dh_ctx* ctx, int ndim, int like_id, const double* like_par
   r.n_like = n_like_par;
   r.n_prior = n_prior_par;
   (void)hipSetDevice(ctx->device);
+  // an error below gives back what was allocated so far (hipFree(nullptr) does nothing)
+  auto give_up = [&r](int code) {
+    (void)hipFree(r.like_par);
+    (void)hipFree(r.prior_par);
+    (void)hipFree(r.prec_t);
+    return code;
+  };
   if (!hip_ok(ctx, hipMalloc((void**)&r.like_par, sizeof(double) * (n_like_par + 1)), "hipMalloc") ||
-      !hip_ok(ctx, hipMalloc((void**)&r.prior_par, sizeof(double) * (n_prior_par + 2)), "hipMalloc"))
-    return DH_ERR_NOMEM;
-  if (!hip_ok(ctx, hipMemcpy(r.like_par, like_par, sizeof(double) * n_like_par, hipMemcpyHostToDevice),
+      !hip_ok(ctx, hipMalloc((void**)&r.prior_par, sizeof(double) * (n_prior_par + 2)), "hipMalloc") ||
+      (want_t && !hip_ok(ctx, hipMalloc((void**)&r.prec_t, sizeof(double) * N * N), "hipMalloc")))
+    return give_up(DH_ERR_NOMEM);
+  if (!hip_ok(ctx, hipMemcpy(r.like_par, lp.data(), sizeof(double) * n_like_par, hipMemcpyHostToDevice),
               "H2D like_par"))
-    return DH_ERR_HIP;
+    return give_up(DH_ERR_HIP);
   if (n_prior_par &&
       !hip_ok(ctx, hipMemcpy(r.prior_par, prior_par, sizeof(double) * n_prior_par, hipMemcpyHostToDevice),
               "H2D prior_par"))
-    return DH_ERR_HIP;
-  if (like_id == DH_LIKE_GAUSS_PREC && ndim <= kMaxRegDim) {
-    // transposed + zero-padded copy for the column-sweep mat-vec of the walk
-    // kernels (P is symmetric in exact arithmetic; transpose anyway)
-    const int N = pad_dim(ndim);
-    std::vector<double> pt((size_t)N * N, 0.0);
-    for (int i = 0; i < ndim; ++i)
-      for (int j = 0; j < ndim; ++j) pt[(size_t)j * N + i] = like_par[1 + (size_t)i * ndim + j];
-    if (!hip_ok(ctx, hipMalloc((void**)&r.prec_t, sizeof(double) * N * N), "hipMalloc") ||
-        !hip_ok(ctx, hipMemcpy(r.prec_t, pt.data(), sizeof(double) * N * N, hipMemcpyHostToDevice),
-                "H2D prec_t"))
-      return DH_ERR_HIP;
-  }
+    return give_up(DH_ERR_HIP);
+  if (want_t && !hip_ok(ctx, hipMemcpy(r.prec_t, pt.data(), sizeof(double) * N * N, hipMemcpyHostToDevice),
+                        "H2D prec_t"))
+    return give_up(DH_ERR_HIP);
   for (size_t i = 0; i < ctx->problems.size(); ++i)
     if (!ctx->problems[i].live) {
       ctx->problems[i] = r;

@@ -30,6 +30,8 @@ from scipy.special import ndtri
 # ids shared with include/dynhip.h
 LIKE_GAUSS_IID = 0  # logl = -0.5 * sum(v^2) + c                par = [c]
 LIKE_GAUSS_PREC = 1  # logl = -0.5 * v^T P v + c                 par = [c, P row-major]
+#   (P may be asymmetric: the host forms the full v^T P v, the device stores (P + P^T) / 2 -- the same
+#   quadratic form -- because its evaluators read different triangles of the matrix)
 LIKE_EGGBOX = 2  # logl = (2 + prod cos((2 tmax v - tmax)/2))^5  par = [tmax]
 
 PRIOR_IDENTITY = 0  # v = u

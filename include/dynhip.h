@@ -45,6 +45,9 @@ extern "C" {
 /* likelihood / prior ids -- twins of dynesty_amd/problems.py */
 #define DH_LIKE_GAUSS_IID 0  /* -0.5 sum v^2 + c                par = [c]        */
 #define DH_LIKE_GAUSS_PREC 1 /* -0.5 v^T P v + c                par = [c, P]     */
+/* (P need not be symmetric: v^T P v only sees (P + P^T) / 2, and that is what dh_problem_create stores -- every
+ * evaluator, whichever triangle of the matrix it reads, computes the full quadratic form.  A symmetric P is stored bit
+ * for bit as given.) */
 #define DH_LIKE_EGGBOX 2     /* (2 + prod cos((2 tmax v - tmax)/2))^5  par = [tmax] */
 #define DH_PRIOR_IDENTITY 0  /* v = u                                            */
 #define DH_PRIOR_AFFINE 1    /* v = a (2u - 1) + b              par = [a, b]     */

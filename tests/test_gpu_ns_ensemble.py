@@ -4,6 +4,7 @@ and independence of the way the ensemble is sharded."""
 import numpy as np
 import pytest
 
+import hp_ref
 import inputs
 
 pytestmark = pytest.mark.gpu
@@ -124,6 +125,8 @@ def test_samples_and_merged_run(ctx):
         np.testing.assert_allclose(ll, r["dead_logl"][run, :k], rtol=0, atol=1e-10)
         _, ll = ctx.problem_eval(prob, r["live_u"][run])
         np.testing.assert_allclose(ll, r["live_logl"][run], rtol=0, atol=1e-10)
+        hp_ref.check_from_u(prob, r["dead_u"][run, :k], r["dead_logl"][run, :k], what=f"ns_ensemble dead, run {run}")
+        hp_ref.check_from_u(prob, r["live_u"][run], r["live_logl"][run], what=f"ns_ensemble live, run {run}")
         assert (np.diff(r["dead_logl"][run, :k]) >= 0).all()
         # the reference's per-point bookkeeping (sampler.py:1165-1182): 'id' = live slot, 'it' = iteration
         # (from 1) at which the point was proposed, 'nc' = calls spent on its replacement.  Exact chain

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import scipy.stats
 
+import hp_ref
 import inputs
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +85,9 @@ def test_chain_statistics_match_the_parity_mode(ctx):
     v, ll = ctx.problem_eval(prob, out["u"])
     np.testing.assert_allclose(out["v"], v, rtol=0, atol=1e-13)
     np.testing.assert_allclose(out["logl"], ll, rtol=1e-12)
+    # ... and both are the problem's own functions, not merely the device agreeing with itself
+    hp_ref.check(prob, out["u"][:512], out["v"][:512], out["logl"][:512], what="rwalk philox C2")
+    hp_ref.check(prob, out["u"][:512], v[:512], ll[:512], what="problem_eval C2")
 
 
 def test_keyed_reproducibility(ctx):
@@ -164,6 +168,8 @@ def test_slice_chains_sample_the_contour_uniformly(ctx, ndim, principal, slices,
     # v and logl belong to the returned u
     v, ll = ctx.problem_eval(prob, out["u"][:512])
     np.testing.assert_allclose(out["logl"][:512], ll, rtol=1e-12, atol=1e-12)
+    hp_ref.check(prob, out["u"][:512], out["v"][:512], out["logl"][:512], what=f"slice philox ball{ndim}")
+    hp_ref.check(prob, out["u"][:512], v, ll, what=f"problem_eval ball{ndim}")
     # work per chain: the same as the parity mode's on the same start points (call counts within 3 %)
     st = ctx.seed_children([5, ndim], 0, min(k, 4000))
     par = ctx.slice_batch(prob, u0[:len(st)], axes, 1.0, loglstar, slices, st, principal=principal)

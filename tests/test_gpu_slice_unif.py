@@ -5,6 +5,7 @@ n_contract) must match exactly."""
 import numpy as np
 import pytest
 
+import hp_ref
 import inputs
 from oracle import bounding_ref as B
 
@@ -182,7 +183,8 @@ def test_unif_lockstep_equals_fused(ctx, kind):
     prob = inputs.problem("G5")
     rng = np.random.default_rng(4)
     live = 0.5 + 0.05 * rng.standard_normal((400, 5))
-    _, ll = ctx.problem_eval(prob, live)
+    v, ll = ctx.problem_eval(prob, live)
+    hp_ref.check(prob, live, v, ll, what="problem_eval G5 (unif lock-step)")
     loglstar = float(np.sort(ll)[80])
     backend.set_backend(ctx)
     try:
@@ -280,7 +282,8 @@ def test_slice_lockstep_on_device_feed(ctx, which):
     prob = inputs.problem("G5")
     rng = np.random.default_rng(8)
     us = 0.5 + 0.04 * rng.standard_normal((12, 5))
-    _, ll = ctx.problem_eval(prob, us)
+    v, ll = ctx.problem_eval(prob, us)
+    hp_ref.check(prob, us, v, ll, what="problem_eval G5 (slice lock-step)")
     loglstar = float(np.min(ll)) - 1.0
     axes = 0.1 * (np.eye(5) + 0.2 * rng.standard_normal((5, 5)))
 

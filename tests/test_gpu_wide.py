@@ -5,6 +5,7 @@ instantiation, against the oracle on the same seeds."""
 import numpy as np
 import pytest
 
+import hp_ref
 import inputs
 from oracle import bounding_ref as B
 from oracle import proposals_ref as P
@@ -206,7 +207,10 @@ def test_unif_wide_vs_oracle(ctx, case):
     p2 = 0.5 + 0.012 + 0.02 * rng.standard_normal((600, nc))
     e1, e2 = B.bounding_ellipsoid(p1), B.bounding_ellipsoid(p2)
     # threshold from points distributed like the proposals (the last d - nc coordinates are U(0, 1))
-    _, ll = ctx.problem_eval(prob, np.hstack([p1, rng.random((600, d - nc))]))
+    uu = np.hstack([p1, rng.random((600, d - nc))])
+    vv, ll = ctx.problem_eval(prob, uu)
+    # (a stride of the points: the reference's ndtri is a 50-digit Newton iteration per coordinate)
+    hp_ref.check(prob, uu, vv, ll, rows=np.arange(0, 600, 40), what=f"problem_eval C4/48 ({case})")
     # (uniform draws in a 48-D ellipsoid sit near its surface: a threshold inside the cloud would
     # never be met -- take one below the cloud, 1/q and unitcheck still decide what is evaluated)
     loglstar = float(np.min(ll)) - 3.0
