@@ -119,6 +119,15 @@ SIGNATURES = {
     "dh_set_rwalk_form": (_i, [_vp, _i]),
     "dh_ns_set_option": (_i, [_vp, _i, _dbl]),
     "dh_ns_set_boundary": (_i, [_vp, _i, _vp]),
+    "dh_ns_keep": (_i, [_vp, _i]),
+    "dh_ns_release": (_i, [_vp]),
+    "dh_merge_runs": (_i, [_vp, _i, _i, _i, _i, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dh_merge_kept": (_i, [_vp, _i, _vp, _vp]),
+    "dh_merged_fetch": (_i, [_vp, _i, C.c_int64, C.c_int64, _vp]),
+    "dh_merged_moments": (_i, [_vp, _vp, _vp]),
+    "dh_merged_resample": (_i, [_vp, _dbl, C.c_int64, _vp]),
+    "dh_merged_gather": (_i, [_vp, C.c_int64, _vp, _vp]),
+    "dh_merged_release": (_i, [_vp]),
     "dh_set_rwalk_items": (_i, [_vp, _i, C.c_longlong]),
     "dh_slice_batch_philox": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _dbl, _dbl, _i, _i, _u64, _u64, _u64,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -235,6 +244,111 @@ def enlarge_bootstrap_defaults(sample, enlarge, bootstrap):
     raise ValueError('Enlarge and bootstrap together do not make sense unless bootstrap=0 or enlarge = 1')
 
 
+# dh_merged_fetch: field name -> (DH_MERGED_* code, dtype, per-point row of ndim values)
+MERGED_FIELDS = dict(logl=(0, np.float64, False), logvol=(1, np.float64, False), logwt=(2, np.float64, False),
+                     logz=(3, np.float64, False), logzerr=(4, np.float64, False), information=(5, np.float64, False),
+                     weights=(6, np.float64, False), samples_u=(7, np.float64, True), samples=(8, np.float64, True),
+                     samples_run=(9, np.int32, False), samples_seq=(10, np.int32, False),
+                     samples_n=(11, np.int32, False), final=(12, np.int32, False), samples_id=(13, np.int32, False),
+                     samples_it=(14, np.int32, False), ncall=(15, np.int32, False))
+SUMMARY_FIELDS = ("niter", "logz", "logzerr", "h", "ess", "ncall")
+
+
+class DeviceMergedRun(dict):
+    """The merged run of Context.merge_runs / merge_kept: it lives on the device (one per context, replaced by the
+    context's next merge); only what is asked for comes to the host.  `summary`: niter (points), logz, logzerr, h,
+    ess, ncall (sum over the points; 0 without per-point bookkeeping)."""
+
+    def __init__(self, ctx, summary, ndim, have_pt):
+        super().__init__()
+        self.ctx, self.ndim, self.have_pt = ctx, int(ndim), bool(have_pt)
+        self.summary = dict(zip(SUMMARY_FIELDS, [float(x) for x in summary]))
+        self.summary["niter"] = int(self.summary["niter"])
+        self.summary["ncall"] = int(self.summary["ncall"])
+        self.niter = self.summary["niter"]
+        self._serial = ctx._merge_serial
+
+    def _live(self):
+        if self.ctx is None or self._serial != self.ctx._merge_serial:
+            raise ValueError("this merged run is no longer on the device (released, or replaced by a later merge)")
+        return self.ctx
+
+    def field(self, name, first=0, count=None):
+        """`count` points of one per-point field from point `first` on (MERGED_FIELDS names)."""
+        ctx = self._live()
+        if name not in MERGED_FIELDS:
+            raise ValueError(f"merged field {name!r}: one of {sorted(MERGED_FIELDS)}")
+        code, dtype, row = MERGED_FIELDS[name]
+        if code >= 13 and not self.have_pt:
+            raise ValueError(f"merged field {name!r}: the merge was not given id / it / nc")
+        first = int(first)
+        count = self.niter - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > self.niter:
+            raise ValueError(f"merged field {name!r}: [{first}, {first + count}) of {self.niter} points")
+        out = np.empty((count, self.ndim) if row else (count,), dtype=dtype)
+        ctx._check_merge(ctx.lib.dh_merged_fetch(ctx.handle, code, first, count, _ptr(out)))
+        return out
+
+    def mean_and_cov(self):
+        """utils.mean_and_cov(samples, importance_weights) computed on the device."""
+        ctx = self._live()
+        mean, cov = np.empty(self.ndim), np.empty((self.ndim, self.ndim))
+        ctx._check_merge(ctx.lib.dh_merged_moments(ctx.handle, _ptr(mean), _ptr(cov)))
+        return mean, cov
+
+    def importance_weights(self):
+        return self.field("weights")
+
+    def resample_equal(self, n=None, rstate=None):
+        """utils.resample_equal(samples, importance_weights, rstate): systematic resampling on the device, the
+        shuffle (rstate.permutation) on the host applied to the indices, then a gather of the chosen rows.  With
+        n = None (all points) the result equals the reference's row for row."""
+        ctx = self._live()
+        if rstate is None:
+            rstate = np.random.default_rng()
+        n = self.niter if n is None else int(n)
+        if n < 1:
+            raise ValueError("resample_equal: n must be positive")
+        idx = np.empty(n, dtype=np.int64)
+        ctx._check_merge(ctx.lib.dh_merged_resample(ctx.handle, float(rstate.random()), n, _ptr(idx)))
+        return self.gather(idx[rstate.permutation(n)])
+
+    def resample_indices(self, u0, n):
+        """idx[i] = #{j : C_j <= (u0 + i) / n} over the normalised cumulative weights (no shuffle)."""
+        ctx = self._live()
+        idx = np.empty(int(n), dtype=np.int64)
+        ctx._check_merge(ctx.lib.dh_merged_resample(ctx.handle, float(u0), int(n), _ptr(idx)))
+        return idx
+
+    def gather(self, idx):
+        """Parameter rows of the points `idx`."""
+        ctx = self._live()
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        out = np.empty((len(idx), self.ndim))
+        if len(idx):
+            ctx._check_merge(ctx.lib.dh_merged_gather(ctx.handle, len(idx), _ptr(idx), _ptr(out)))
+        return out
+
+    def to_merged_run(self):
+        """Everything downloaded into ensemble.MergedRun (merge_static_runs' field names)."""
+        from .ensemble import MergedRun
+        names = ["logl", "logvol", "logwt", "logz", "logzerr", "information", "samples_n", "samples_run",
+                 "samples_seq", "samples_u", "samples"] + (["samples_id", "samples_it", "ncall"] if self.have_pt else [])
+        out = MergedRun(niter=self.niter)
+        for k in names:
+            a = self.field(k)
+            out[k] = a.astype(np.int64) if a.dtype == np.int32 else a
+        if self.have_pt:
+            out["eff"] = 100. * self.niter / float(out["ncall"].sum())
+        return out
+
+    def release(self):
+        if self.ctx is not None and self._serial == self.ctx._merge_serial:
+            self.ctx._merge_serial += 1
+            self.ctx._check(self.ctx.lib.dh_merged_release(self.ctx.handle))
+        self.ctx = None
+
+
 class Context:
     """One device + stream (dh_ctx).  Methods take/return NumPy arrays."""
 
@@ -246,6 +360,7 @@ class Context:
             raise DynHipError(f"dh_create({device}) failed: {msg}")
         self.device = int(device)
         self._problems = {}
+        self._merge_serial = 0  # which merge the context's merged run is (DeviceMergedRun)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -268,6 +383,72 @@ class Context:
         if rc in (ERR_CONTAIN, ERR_REGION, ERR_SLICE, ERR_QZERO):
             raise RuntimeError(msg)
         raise DynHipError(f"libdynhip error {rc}: {msg}")
+
+    def _check_merge(self, rc):
+        """Argument errors of the merge calls (shapes, no kept ensemble, a released run) are ValueError."""
+        if rc == ERR_ARG:
+            raise ValueError(self.lib.dh_last_error(self.handle).decode())
+        return self._check(rc)
+
+    # -- the combiner on the device (csrc/merge.hip) ---------------------------
+    def _merged(self, rc):
+        """After a merge call: an argument error touched nothing (an earlier DeviceMergedRun stays valid); anything
+        else, success included, replaced or dropped the context's merged run."""
+        if rc != ERR_ARG:
+            self._merge_serial += 1
+        return self._check_merge(rc)
+
+    def merge_runs(self, prob, niter, dead_logl, live_logl, dead_u, live_u, dead_id=None, dead_it=None,
+                   dead_nc=None, live_it=None):
+        """dh_merge_runs: ensemble.merge_static_runs on the device.  dead_*: (R, >= max niter [, D]) arrays or
+        per-run lists, live_*: (R, N [, D]) in slot order; dead_id / dead_it / dead_nc / live_it together or not
+        at all.  Returns a DeviceMergedRun."""
+        nd = prob.ndim
+        niter = np.ascontiguousarray(niter, dtype=np.int64).reshape(-1)
+        R = len(niter)
+        live_logl = _f64(live_logl)
+        if live_logl.ndim != 2 or live_logl.shape[0] != R:
+            raise ValueError(f"merge_runs: live_logl of shape {live_logl.shape} for {R} runs")
+        N = live_logl.shape[1]
+        live_u = _f64(live_u)
+        if live_u.shape != (R, N, nd):
+            raise ValueError(f"merge_runs: live_u of shape {live_u.shape}, expected {(R, N, nd)}")
+        stride = int(niter.max()) if R else 0
+        if R and int(niter.min()) < 0:
+            raise ValueError("merge_runs: negative niter")
+
+        def rows(a, dtype, tail=()):
+            out = np.zeros((R, max(stride, 1)) + tail, dtype=dtype)
+            for r in range(R):
+                row = np.asarray(a[r])
+                if len(row) < niter[r]:
+                    raise ValueError(f"merge_runs: run {r} has {len(row)} dead rows for niter {niter[r]}")
+                out[r, :niter[r]] = row[:niter[r]]
+            return out
+        info = [dead_id, dead_it, dead_nc, live_it]
+        if any(x is None for x in info) and not all(x is None for x in info):
+            raise ValueError("merge_runs: dead_id, dead_it, dead_nc and live_it come together")
+        have_pt = dead_id is not None
+        dl, du = rows(dead_logl, np.float64), rows(dead_u, np.float64, (nd,))
+        pid = rows(dead_id, np.int32) if have_pt else None
+        pit = rows(dead_it, np.int32) if have_pt else None
+        pnc = rows(dead_nc, np.int32) if have_pt else None
+        lit = np.ascontiguousarray(live_it, dtype=np.int32).reshape(R, N) if have_pt else None
+        summ = np.empty(6)
+        self._merged(self.lib.dh_merge_runs(
+            self.handle, self.problem(prob), R, N, nd, max(stride, 1) if stride else 0, _ptr(niter), _ptr(dl),
+            _ptr(live_logl), _ptr(du), _ptr(live_u), _ptr(pid), _ptr(pit), _ptr(pnc), _ptr(lit), _ptr(summ)))
+        return DeviceMergedRun(self, summ, nd, have_pt)
+
+    def merge_kept(self, prob, niter=None):
+        """dh_merge_kept: the merged run of the ensemble the last ns_ensemble(keep=True) left on the device."""
+        nit = None if niter is None else np.ascontiguousarray(niter, dtype=np.int64)
+        summ = np.empty(6)
+        self._merged(self.lib.dh_merge_kept(self.handle, self.problem(prob), _ptr(nit), _ptr(summ)))
+        return DeviceMergedRun(self, summ, prob.ndim, True)
+
+    def release_kept(self):
+        self._check(self.lib.dh_ns_release(self.handle))
 
     def set_rwalk_form(self, form):
         """0 (default) / 2: four lanes per walker + matrix cores (csrc/walkq.hip) wherever that kernel is
@@ -803,8 +984,11 @@ class Context:
                     want_dead_logl=False, sample='rwalk', slices=None,
                     rebuild_sync=False, want_samples=False, rng='pcg64', bootstrap=None, rebuild_every=0,
                     update_interval=None, first_update=None, maxiter=None, maxcall=None, logl_max=None,
-                    add_live=True, forced_exact=True, periodic=None, reflective=None):
+                    add_live=True, forced_exact=True, periodic=None, reflective=None, keep=False):
         """Device-resident ensemble of static NS runs (dh_ns_ensemble).
+
+        keep=True: the finished ensemble stays on the device for merge_kept (dh_ns_keep); with want_samples=False
+        the returned dict then has the records and no per-point arrays.
 
         periodic / reflective: lists of coordinate indices as NestedSampler takes them (dynesty.py:297-310); they reach
         the rwalk and uniform samplers (dh_ns_set_boundary), the slice samplers ignore them as the reference's do.
@@ -904,6 +1088,8 @@ class Context:
             if reflective is not None:
                 bc[np.asarray(reflective, dtype=int)] = BC_REFLECT
         self._check(self.lib.dh_ns_set_boundary(self.handle, nd if bc is not None else 0, _ptr(bc)))
+        if keep:
+            self._check(self.lib.dh_ns_keep(self.handle, 1))
         self._check(self.lib.dh_ns_ensemble(
             self.handle, self.problem(prob), int(runs), int(nlive), nd,
             int(queue_size), kind + ((1 if kind == 6 else 3) if rng == 'philox' else 0), int(walks),

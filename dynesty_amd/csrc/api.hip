@@ -153,6 +153,8 @@ void dh_destroy(dh_ctx* ctx) {
     if (p.prior_par) (void)hipFree(p.prior_par);
     if (p.prec_t) (void)hipFree(p.prec_t);
   }
+  kept_free(ctx);
+  merged_free(ctx);
   if (ctx->zig) (void)hipFree(ctx->zig);
   if (ctx->items) (void)hipFree(ctx->items);
   if (ctx->arena) (void)hipFree(ctx->arena);

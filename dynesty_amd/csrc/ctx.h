@@ -38,6 +38,31 @@ struct dh_problem_rec {
   int n_like = 0, n_prior = 0;
 };
 
+// A finished ensemble left on the device by dh_ns_ensemble after dh_ns_keep (ns.hip): `base` is that call's single
+// allocation, the pointers below lie inside it.  Rows of the dead arrays are `cap` apart.
+struct dh_kept {
+  char* base = nullptr;
+  int problem = -1, runs = 0, nlive = 0, ndim = 0;
+  long long cap = 0;
+  const double *dead_logl = nullptr, *live_logl = nullptr, *dead_u = nullptr, *live_u = nullptr;
+  const int *dead_id = nullptr, *dead_it = nullptr, *dead_nc = nullptr, *live_it = nullptr;
+  std::vector<long long> niter;  // per run, from the records
+};
+
+// The merged run of the last dh_merge_runs / dh_merge_kept (merge.hip): one allocation, M points in merged order.
+struct dh_merged {
+  char* base = nullptr;
+  long long M = 0;
+  int ndim = 0, runs = 0, nlive = 0;
+  bool have_pt = false;  // id / it / nc were given
+  double *logl = nullptr, *logvol = nullptr, *logwt = nullptr, *logz = nullptr, *logzerr = nullptr, *h = nullptr;
+  double *w = nullptr, *cw = nullptr, *u = nullptr, *v = nullptr;
+  double* mom = nullptr;  // [sum w, sum w^2, ESS, sum w v_0 .. sum w v_{D-1}]
+  int *run = nullptr, *seq = nullptr, *id = nullptr, *it = nullptr, *nc = nullptr, *n = nullptr, *fin = nullptr;
+  long long* idx = nullptr;  // indices of the last dh_merged_resample (an allocation of its own, grow-only)
+  long long idx_cap = 0, idx_n = 0;
+};
+
 struct dh_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -94,6 +119,10 @@ struct dh_ctx {
     unsigned short* out = nullptr;
     int n = 0, runs = 0, stride = 0, done = 0;
   } presort;
+  // dh_ns_keep: the next dh_ns_ensemble leaves its arrays on the device (one-shot); what it left; the merged run
+  int ns_keep = 0;
+  dh_kept kept;
+  dh_merged merged;
   double* items = nullptr;
   size_t items_cap = 0;
   size_t items_budget = (size_t)1 << 30;
@@ -219,6 +248,9 @@ int bootstrap_expand_launch(dh_ctx* ctx, int runs, const double* pts, int n, int
                             const uint64_t* ent, const int* active, void* ws, double* run_shift, double* expand,
                             int* bstatus);
 int eval_launch_dev(dh_ctx* ctx, int problem, int k, const double* u, double* v, double* logl);
+// merge.hip: give back the kept ensemble / the merged run (after the stream has drained)
+void kept_free(dh_ctx* ctx);
+void merged_free(dh_ctx* ctx);
 // bound.hip: start-point membership per run (candidate w -> run w / wpr); flag[run] |= 1 if one lies outside
 int contains_runs_launch(dh_ctx* ctx, const double* x, int k, int d, int wpr, const double* ctrs, const double* ams,
                          const int* nells, int max_ells, int strict, const int* run_mode, int my_mode,

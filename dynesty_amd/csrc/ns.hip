@@ -2518,6 +2518,33 @@ bool download(dh_ctx* ctx, const NsArgs& a, double* records, double* dead_logl, 
   return true;
 }
 
+// dh_ns_keep: a kept ensemble stores the samples and all four per-point arrays whether or not the caller downloads them
+int ns_point_outputs(bool keep, int given) { return keep && given == 0 ? 4 : given; }
+
+// the context takes over the call's allocation as "the kept ensemble" (merge.hip reads it through dh_kept)
+void ns_keep_arrays(dh_ctx* ctx, const NsArgs& a, int problem, char* base, const double* records) {
+  dh_kept& k = ctx->kept;
+  k.base = base;
+  k.problem = problem;
+  k.runs = a.runs;
+  k.nlive = a.nlive;
+  k.ndim = a.ndim;
+  k.cap = a.cap;
+  k.dead_logl = a.dead_logl;
+  k.live_logl = a.live_logl;
+  k.dead_u = a.dead_u;
+  k.live_u = a.live_u;
+  k.dead_id = a.dead_id;
+  k.dead_it = a.dead_it;
+  k.dead_nc = a.dead_nc;
+  k.live_it = a.live_it;
+  k.niter.resize((size_t)a.runs);
+  for (int r = 0; r < a.runs; ++r) {
+    long long nit = (long long)records[(size_t)r * 8 + 2];
+    k.niter[(size_t)r] = nit < 0 ? 0 : nit > a.cap ? a.cap : nit;
+  }
+}
+
 void ns_prof_print(dh_ctx* ctx, const long long* prof, long long fills) {
   long long h[32];
   (void)hipStreamSynchronize(ctx->stream);
@@ -2647,6 +2674,19 @@ int dh_ns_set_option(dh_ctx* ctx, int key, double value) {
   return DH_OK;
 }
 
+int dh_ns_keep(dh_ctx* ctx, int on) {
+  DH_CHECK_CTX(ctx);
+  ctx->ns_keep = on ? 1 : 0;
+  return DH_OK;
+}
+
+int dh_ns_release(dh_ctx* ctx) {
+  DH_CHECK_CTX(ctx);
+  (void)hipStreamSynchronize(ctx->stream);
+  kept_free(ctx);
+  return DH_OK;
+}
+
 int dh_ns_set_boundary(dh_ctx* ctx, int ndim, const int8_t* bc) {
   DH_CHECK_CTX(ctx);
   // validate first: a rejected call leaves the installed flags as they were
@@ -2676,7 +2716,9 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
     dh_ctx* c;
     double opt[DH_NS_OPT_COUNT];
     std::vector<int8_t> bc;
-    explicit NsOneShot(dh_ctx* cc) : c(cc) {
+    int keep;
+    explicit NsOneShot(dh_ctx* cc) : c(cc), keep(cc->ns_keep) {
+      c->ns_keep = 0;
       for (int i = 0; i < DH_NS_OPT_COUNT; ++i) {
         opt[i] = c->ns_opt[i];
         c->ns_opt[i] = __builtin_nan("");
@@ -2687,9 +2729,10 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
   NsPlan p;
   int rc = ns_plan(ctx, shot.opt, shot.bc.size(), problem, runs, nlive, ndim, queue_size, sampler, walks, bound,
                    rebuild_sync, dlogz, enlarge, max_fills, max_iter, entropy_words, n_words, first_run, records,
-                   dead_u_out != nullptr, !!dead_id_out + !!dead_it_out + !!dead_nc_out + !!live_it_out, bootstrap,
-                   rebuild_every, &p);
+                   dead_u_out != nullptr || shot.keep, ns_point_outputs(shot.keep != 0, !!dead_id_out + !!dead_it_out + !!dead_nc_out + !!live_it_out),
+                   bootstrap, rebuild_every, &p);
   if (rc) return rc;
+  if (shot.keep) kept_free(ctx);  // a later keep replaces the earlier one (before this call's allocation)
   NsArgs a = p.a;
   NsAux x;
   const int R = a.runs, N = a.nlive, D = a.ndim, K = a.K;
@@ -2702,6 +2745,10 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
   hipStream_t s = ctx->stream;
   auto cleanup = [&](int rc) {
     (void)hipStreamSynchronize(ctx->stream);
+    if (shot.keep && rc == DH_OK) {
+      ns_keep_arrays(ctx, a, problem, base, records);
+      return rc;
+    }
     (void)hipFree(base);
     return rc;
   };

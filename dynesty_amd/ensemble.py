@@ -306,14 +306,37 @@ def merge_logz(dead_logl, niter, live_logl):
 
 
 def run_ensemble_merged(prob, runs, nlive=2000, queue_size=512, entropy=(21,),
-                        max_iter=None, **kw):
-    """`runs` static runs on the device (dh_ns_ensemble) merged into one
-    MergedRun with posterior samples: the single-process form of BASELINE C5's
-    "gather of logZ / posterior samples"."""
+                        max_iter=None, merge='host', **kw):
+    """`runs` static runs on the device (dh_ns_ensemble) merged into one run
+    with posterior samples: the single-process form of BASELINE C5's
+    "gather of logZ / posterior samples".
+
+    merge='host' (default): every run's points come to the host and
+    `merge_static_runs` combines them; returns a MergedRun.
+    merge='device': the ensemble stays on the device (ns_ensemble(keep=True))
+    and the device combiner merges it there (Context.merge_kept); returns the
+    DeviceMergedRun -- summary, field(), mean_and_cov(), resample_equal(),
+    to_merged_run() -- with only what is asked for crossing to the host.
+    The kept ensemble is released once merged; the merged run stays on the
+    device until its release() or the context's next merge.
+    Either way the per-run records are under ["runs"]."""
+    if merge not in ('host', 'device'):
+        raise ValueError(f"run_ensemble_merged: merge={merge!r} (one of 'host', 'device')")
     from .backend import get_backend
     be = get_backend()
     if max_iter is None:
         max_iter = 80 * nlive  # > nlive * (H + ln(1/dlogz)) for the benchmark problems
+    if merge == 'device':
+        r = be.ns_ensemble(prob, runs, nlive, queue_size, entropy=entropy,
+                           max_iter=max_iter, want_samples=False, keep=True, **kw)
+        if (r["status"] != 0).any():
+            raise RuntimeError(f"ns_ensemble: runs failed, status {r['status']}")
+        try:
+            m = be.merge_kept(prob)
+        finally:
+            be.release_kept()  # the merged run stands alone: the ensemble's own allocation goes back at once
+        m["runs"] = r
+        return m
     r = be.ns_ensemble(prob, runs, nlive, queue_size, entropy=entropy,
                        max_iter=max_iter, want_samples=True, **kw)
     if (r["status"] != 0).any():

@@ -601,6 +601,64 @@ int dh_unif_friends_batch(dh_ctx* ctx, int problem, int k, int ndim, int kind, c
                           double* v, double* logl, int32_t* ncalls, uint64_t* rng_out,
                           const uint64_t* rng32, uint64_t* rng32_out);
 
+/* ---- the combiner on the device (csrc/merge.hip) ---------------------------------------
+ * dh_ns_keep(ctx, 1): the NEXT dh_ns_ensemble call (one-shot, like the options) stores the samples and the per-point
+ * id / it / nc on the device whether or not their host pointers are given, downloads only what the host pointers ask
+ * for, and leaves its allocation with the context as "the kept ensemble" (one per context).  A later keep,
+ * dh_ns_release or dh_destroy frees it.  Without the switch dh_ns_ensemble is unchanged. */
+int dh_ns_keep(dh_ctx* ctx, int on);
+int dh_ns_release(dh_ctx* ctx);
+
+/* Per-point fields of the merged run (dh_merged_fetch).  LOGL .. WEIGHT: one double per point; SAMPLES_U / SAMPLES:
+ * ndim doubles per point; RUN .. NCALL: one int32 per point (ID / IT / NCALL only where the merge was given them). */
+enum {
+  DH_MERGED_LOGL = 0,
+  DH_MERGED_LOGVOL = 1,
+  DH_MERGED_LOGWT = 2,
+  DH_MERGED_LOGZ = 3,
+  DH_MERGED_LOGZERR = 4,
+  DH_MERGED_INFORMATION = 5,
+  DH_MERGED_WEIGHT = 6,    /* exp(logwt - ln Z) / sum */
+  DH_MERGED_SAMPLES_U = 7,
+  DH_MERGED_SAMPLES = 8,
+  DH_MERGED_RUN = 9,       /* run the point came from */
+  DH_MERGED_SEQ = 10,      /* its index in that run's own sequence (dead points, then final live points ascending) */
+  DH_MERGED_SAMPLES_N = 11,
+  DH_MERGED_FINAL = 12,    /* 1: a final live point */
+  DH_MERGED_ID = 13,
+  DH_MERGED_IT = 14,
+  DH_MERGED_NCALL = 15
+};
+
+/* `runs` static runs of equal nlive merged into one run that stays on the device -- ensemble.merge_static_runs, i.e.
+ * the reference's utils.merge_runs for such runs.  Host pointers: niter (runs), dead_logl / dead_id / dead_it / dead_nc
+ * (runs x stride, the first niter[r] of a row are read), dead_u (runs x stride x ndim), live_logl / live_it
+ * (runs x nlive, slot order), live_u (runs x nlive x ndim).  dead_id, dead_it, dead_nc and live_it may be NULL
+ * together.  The merged order is the stable order of the concatenated sequences (exact, ties included); parameters
+ * are dh_problem_eval's of the same rows, bit for bit.  summary_out: 6 doubles {M, ln Z, its error, H, ESS,
+ * sum ncall}.  The merged run (one per context) is replaced by the next merge.
+ * DH_ERR_ARG: shapes and sizes (M < 2^31 points, M x ndim < 2^32 elements); nothing was touched, an earlier merged
+ * run is still there.  Every other error leaves the context without a merged run: DH_ERR_VALUE: a NaN
+ * log-likelihood, or a run whose sequence decreases; DH_ERR_NOMEM. */
+int dh_merge_runs(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int64_t stride, const int64_t* niter,
+                  const double* dead_logl, const double* live_logl, const double* dead_u, const double* live_u,
+                  const int32_t* dead_id, const int32_t* dead_it, const int32_t* dead_nc, const int32_t* live_it,
+                  double* summary_out);
+/* The same from the kept ensemble, with no upload.  niter: NULL = the kept records'.  DH_ERR_ARG: no kept ensemble,
+ * or `problem` is not the one it ran. */
+int dh_merge_kept(dh_ctx* ctx, int problem, const int64_t* niter, double* summary_out);
+/* `count` points of one field from point `first` on, to the host. */
+int dh_merged_fetch(dh_ctx* ctx, int field, int64_t first, int64_t count, void* out);
+/* utils.mean_and_cov of (samples, weights): mean ndim, cov ndim x ndim (either may be NULL). */
+int dh_merged_moments(dh_ctx* ctx, double* mean, double* cov);
+/* Systematic resampling (utils.resample_equal before its shuffle): idx[i] = #{j : C_j <= (u0 + i) / n_out} over the
+ * normalised cumulative weights.  idx_out (n_out int64) may be NULL: the indices stay on the device.  n_out < 2^32. */
+int dh_merged_resample(dh_ctx* ctx, double u0, int64_t n_out, int64_t* idx_out);
+/* Parameter rows of n points: out_v n x ndim (n x ndim < 2^32 per call).  idx NULL = the first n indices of the last
+ * dh_merged_resample. */
+int dh_merged_gather(dh_ctx* ctx, int64_t n, const int64_t* idx_or_null, double* out_v);
+int dh_merged_release(dh_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -653,6 +653,22 @@ def gen_merge(out):
     print("wrote", out, len(g), "arrays")
 
 
+def gen_merge_device(out, merge_npz):
+    """Moments and equal-weight samples of the merged run merge.npz already holds (tests/test_merge_hp_cpu.py,
+    tests/test_gpu_merge.py): utils.mean_and_cov and utils.resample_equal of (ref/samples, ref/importance_weights)
+    for the generators default_rng(0..3), and the u0 each of them draws first."""
+    from dynesty import utils as dyu
+    m = np.load(merge_npz)
+    samples, w = m["ref/samples"], m["ref/importance_weights"]
+    g = {}
+    g["mean"], g["cov"] = dyu.mean_and_cov(samples, w)
+    for s in range(4):
+        g[f"resample/{s}"] = dyu.resample_equal(samples, w, rstate=np.random.default_rng(s))
+        g[f"u0/{s}"] = np.float64(np.random.default_rng(s).random())
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(g), "arrays")
+
+
 if __name__ == "__main__":
     import_reference()
     gdir = os.path.join(ROOT, "tests", "golden")
@@ -674,5 +690,7 @@ if __name__ == "__main__":
         gen_nsloop(os.path.join(gdir, "nsloop.npz"))
     if "merge" in which:  # not in the default list: tests/test_merge_cpu.py
         gen_merge(os.path.join(gdir, "merge.npz"))
+    if "merge_device" in which:  # not in the default list; reads merge.npz, which stays as it is
+        gen_merge_device(os.path.join(gdir, "merge_device.npz"), os.path.join(gdir, "merge.npz"))
     if "livesets" in which:  # not in the default list: two partial reference runs (minutes)
         gen_livesets(os.path.join(gdir, "livesets.npz"))
