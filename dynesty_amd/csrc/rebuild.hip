@@ -1838,6 +1838,87 @@ __device__ __forceinline__ void kmeans_label_sums(const Lds& L, unsigned long lo
   o2 = a2 + b2;
 }
 
+// One of the two chains alone, for a 128-point part (node_kmeans_part's WIDE form): wave w takes the 64-point group
+// w & 1; waves 0 and 1 run that group's chain `a`, waves 2 and 3 its chain `b` (the groups of four points that start
+// at row 4 of every eight).  Same operands in the same order as the chain above; `a + b` is formed where the waves'
+// partials are folded.
+template <bool NB3>
+__device__ __forceinline__ void kmeans_label_sums_chain(const Lds& L, unsigned long long sel, double& o0, double& o1, double& o2) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, LD = L.LD;
+  const int lj = lane & 15, lk = lane >> 4, cb = (w >> 1) * 4;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  const unsigned long long mine = sel >> (lk + cb);
+  const double* base = L.tile + ((w & 1) * 64 + cb + lk) * LD + lj;
+#pragma unroll 4
+  for (int g8 = 0; g8 < 8; ++g8) {
+    const double ind = ((mine >> (8 * g8)) & 1ull) ? 1.0 : 0.0;
+    const double* row = base + g8 * 8 * LD;
+    a0 = DH_MFMA_F64_4X4(ind, row[0], a0);
+    a1 = DH_MFMA_F64_4X4(ind, row[16], a1);
+    if constexpr (NB3) a2 = DH_MFMA_F64_4X4(ind, row[32], a2);
+  }
+  o0 = a0;
+  o1 = a1;
+  o2 = a2;
+}
+
+// ---- the WIDE distance phase: one lane per (point, centroid) pair ---------------------------------------------------
+// Lane i of a row of 16 hands its value to the whole row: the DPP control row_newbcast:i (gfx90a and later) on a 64-bit
+// move.  With coordinates 16 b + i of centroid (lane >> 5) in lane i's register C[b], coordinate j of THIS lane's
+// centroid is row_bcast_f64<j & 15>(C[j >> 4]) -- one vector move, no scalar register in between and no LDS access.
+template <int I>
+__device__ __forceinline__ double row_bcast_f64(double v) {
+  static_assert(I >= 0 && I < 16, "a lane of the row");
+  return __builtin_amdgcn_mov_dpp(v, 0x150 + I, 0xF, 0xF, false);
+}
+// step j of the chain: d = fma(x_j - c_j, x_j - c_j, d), the centroid's coordinate j from lane j & 15 of the row
+template <int J>
+__device__ __forceinline__ double sqdist_step(double d, double x, double c0, double c1, double c2) {
+  const double e = x - row_bcast_f64<(J & 15)>(J < 16 ? c0 : J < 32 ? c1 : c2);
+  return fma(e, e, d);
+}
+// Coordinates J0 .. ND - 1 of the chain in blocks of eight, xv = the block at J0 (already requested): the next block's
+// loads are issued before this block's steps.  ND is a compile-time constant: straight-line code, every LDS offset and
+// every broadcast lane an immediate -- no branch, no address arithmetic and no scalar operand between the first and
+// the last step of a point's chain.
+template <int J0, int ND>
+__device__ __forceinline__ double sqdist_blocks(const double* x, double d, const double (&xv)[8], double c0, double c1, double c2) {
+  constexpr int N = ND - J0 < 8 ? ND - J0 : 8, NN = ND - J0 - 8 < 8 ? ND - J0 - 8 : 8;
+  double xn[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if constexpr (NN > 0) {
+#pragma unroll
+    for (int u = 0; u < NN; ++u) xn[u] = x[J0 + 8 + u];
+  }
+  if constexpr (N > 0) d = sqdist_step<J0 + 0>(d, xv[0], c0, c1, c2);
+  if constexpr (N > 1) d = sqdist_step<J0 + 1>(d, xv[1], c0, c1, c2);
+  if constexpr (N > 2) d = sqdist_step<J0 + 2>(d, xv[2], c0, c1, c2);
+  if constexpr (N > 3) d = sqdist_step<J0 + 3>(d, xv[3], c0, c1, c2);
+  if constexpr (N > 4) d = sqdist_step<J0 + 4>(d, xv[4], c0, c1, c2);
+  if constexpr (N > 5) d = sqdist_step<J0 + 5>(d, xv[5], c0, c1, c2);
+  if constexpr (N > 6) d = sqdist_step<J0 + 6>(d, xv[6], c0, c1, c2);
+  if constexpr (N > 7) d = sqdist_step<J0 + 7>(d, xv[7], c0, c1, c2);
+  if constexpr (NN > 0)
+    return sqdist_blocks<J0 + 8, ND>(x, d, xn, c0, c1, c2);
+  else
+    return d;
+}
+// d = sum over j = 0 .. ND - 1, in this order, of fma(x_j - c_j, x_j - c_j, d)
+template <int ND>
+__device__ __forceinline__ double sqdist_chain(const double* x, double c0, double c1, double c2) {
+  static_assert(ND >= 1 && ND <= 48, "three registers of sixteen coordinates");
+  double xv[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int u = 0; u < (ND < 8 ? ND : 8); ++u) xv[u] = x[u];
+  double d = sqdist_blocks<0, ND>(x, 0.0, xv, c0, c1, c2);
+  asm volatile("" : "+v"(d));  // (keeps the last step in this instance: the instances' common tail is otherwise merged behind their join)
+  return d;
+}
+// (the dimensions the WIDE form is built for: one instance of the chain each)
+#define DH_WIDE_DIMS(X)                                                                                               \
+  X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) \
+  X(28) X(29) X(30) X(31) X(32) X(33) X(34) X(35) X(36) X(37) X(38) X(39) X(40) X(41) X(42) X(43) X(44) X(45) X(46)   \
+  X(47) X(48)
+
 // lane l's value of a double, to every lane (l uniform): two v_readlane_b32 -- no LDS round trip
 __device__ __forceinline__ double readlane_f64(double v, int l) {
   const long long b = __double_as_longlong(v);
@@ -1845,6 +1926,10 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
   const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)b >> 32), l);
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
+
+// the WIDE form of node_kmeans_part: a 128-point part, and a dimension the chain instances cover (DH_WIDE_DIMS: three
+// registers of sixteen centroid coordinates)
+__device__ __forceinline__ bool kmeans_wide_form(const Lds& L, int D) { return L.TP == 128 && D >= 8 && D <= 48; }
 
 // Lloyd iterations of a split (the reference's kmeans2(iter=10)).  Iteration it publishes its partials with the tag
 // tag0 + it + 1, whose low 8 bits are the iteration's (split_body's tag0).
@@ -1855,6 +1940,22 @@ static_assert(kLloydIters + 1 <= 0xff, "the iteration tag has 8 bits");
 // index, np = number of parts, kp = this node's partial-sum slots (2 parities x np x KP),
 // bar = its barrier counter.  Returns n0 (size of cluster 0) or -1 on a barrier timeout;
 // on return perm[start + q TP ...] holds the partitioned order if the split is viable.
+//
+// Two forms of the Lloyd iteration, one instance each (the caller chooses by kmeans_wide_form):
+//   * WIDE = false, a 256-point part (D <= 13) or any other shape: one point per thread, both centroids' chains in the
+//     thread, centroid coordinates through v_readlane.  On a 128-point part this left waves 2 and 3 idle in the distance
+//     and label-sum phases, and its distance loop is 145 instructions per eight dimensions with 16 scalar branches
+//     among them (32 v_readlane, the run-time test `j < D` per dimension as a branch, an address clamp per dimension).
+//   * WIDE = true, a 128-point part: one lane per (point, centroid) pair, the two accumulator chains of a 64-point
+//     group's label sums on two waves.  The distance chain is an instance per dimension (DH_WIDE_DIMS): per coordinate
+//     one v_mov_b64_dpp row_newbcast, one v_add_f64, one v_fmac_f64 and half a ds_read2_b64 -- 211 instructions for 48
+//     dimensions, no branch and no scalar operand between the first step and the last.
+// Both forms compute every distance, label, count, sum and centroid with the same operations in the same order: the
+// bench outputs and the trees of tests/test_gpu_split_lloyd.py do not change by a bit.  Measured on one MI355X against
+// the one-point-per-thread form (profiles/lloyd/): per iteration of a 128-point part at 64 runs vq 4 300 -> 2 000-2 300
+// ticks, sums 2 500 -> 1 300, a single-part iteration 11 400 -> 8 400; k_split 65.0 -> 49.3 us per launch; the bench
+// step 2.044 -> 1.945 ms.  What is left of an iteration is barriers, the fold and the tagged exchange.
+template <bool WIDE>
 __device__ int node_kmeans_part(const Lds& L, const double* pts, int* perm, int* perm2, int start, int count,
                                 int D, const double* es, int q, int np, double* kp0, double* kp1, int* bar,
                                 int min_size, unsigned long long tag0, int lvl = 0) {
@@ -1900,14 +2001,48 @@ __device__ int node_kmeans_part(const Lds& L, const double* pts, int* perm, int*
       for (int pz = pz0; pz < rup; pz += pzs) L.tile[pz * LD + jz] = 0.0;
     __syncthreads();
   }
-  unsigned long long m0 = 0ull, m1 = 0ull;  // this wave's label ballots (valid points only)
+  unsigned long long m0 = 0ull, m1 = 0ull;  // label ballots of a 64-point group (valid points only)
+  // WIDE: a 128-point part on 256 threads.  The one-point-per-thread form below leaves waves 2 and 3 without work in
+  // the two longest phases of an iteration (distances, label sums), and a part is bound by how fast one wave issues.
+  //   * distances: lane (p & 31) + 32 c of wave p >> 5 runs the chain of point p against centroid c; the partner's
+  //     result arrives by v_permlane32_swap.  The centroid reaches the chain through row broadcasts (sqdist_chain).
+  //   * ballots: wave w knows the labels of points 32 w .. 32 w + 31; the 32-bit masks meet in L.ri at the barrier
+  //     that was there, and every wave reads the two words of its 64-point group w & 1 -- the masks of before.
+  //   * label sums: wave g runs chain `a` of group g, wave g + 2 chain `b` (kmeans_label_sums_chain).
+  // Every chain keeps its operands and their order: labels, counts, sums and centroids are what they were, bit for bit.
+  // (an instance of its own, chosen by the caller: L.TP == 128 and 8 <= D <= 48 -- kmeans_wide_form -- so that neither
+  // form carries the other's loop invariants through the iterations: k_split has no register to spare)
+  constexpr bool wide = WIDE;
+  const int half = lane >> 5, pw = (w << 5) | (lane & 31);  // WIDE: this lane's centroid and point
+  const int wu = __builtin_amdgcn_readfirstlane(w);         // (the wave index as a scalar: what depends on it alone stays out of the vector registers)
+  const int cg = cnt - (wu & 1) * 64;                       // WIDE: valid points of this wave's 64-point group
   for (int it = 0; it < kLloydIters; ++it) {
     // vq: nearest centroid, strict '<' so the lower index wins ties.  (round 6) The centroids ride in the lanes of two
     // registers (lane j: coordinate j) and reach the distance loop through v_readlane: two LDS loads per wave and
     // iteration instead of two per dimension and point -- with four to five parts per CU the LDS pipe was half of
     // an iteration's time at 64 runs.  Same differences, same fma chains: the same bits.
-    const bool has = t < cnt;
-    if (w * 64 < cnt) {  // (uniform per wave)
+    const bool has = wide ? pw < cnt : t < cnt;
+    if (wide) {
+      if (w * 32 < cnt) {  // (uniform per wave)
+        // (lanes whose coordinate is beyond D read what follows the centroids in LDS -- the sums, the partial-sum
+        // scratch: inside the carve-up -- and are never broadcast)
+        const double* cn = L.cen + half * D + (lane & 15);
+        const double c0r = cn[0], c1r = cn[16], c2r = cn[32];
+        const double* x = L.tile + (has ? pw : 0) * LD;
+        double d = 0.0;
+        switch (D) {  // (uniform: one dispatch in front of the chain)
+#define DH_SQD_CASE(N) \
+  case N:              \
+    d = sqdist_chain<N>(x, c0r, c1r, c2r); \
+    break;
+          DH_WIDE_DIMS(DH_SQD_CASE)
+#undef DH_SQD_CASE
+          default: break;
+        }
+        const double dp = xor_lane<32>(d);  // the same point against the other centroid
+        lb = (half ? d < dp : dp < d) ? 1 : 0;  // d1 < d0
+      }
+    } else if (w * 64 < cnt) {  // (uniform per wave)
       const double c0l = L.cen[lane < D ? lane : 0], c1l = L.cen[D + (lane < D ? lane : 0)];
       const double* x = L.tile + (has ? t : 0) * LD;
       double d0 = 0.0, d1 = 0.0;
@@ -1934,16 +2069,31 @@ __device__ int node_kmeans_part(const Lds& L, const double* pts, int* perm, int*
       // = a fixed point of the Lloyd iteration, the remaining iterations would reproduce this one bit for bit
       const unsigned long long mv = __ballot(has && lb != lb_prev);
       m1 = __ballot(has && lb == 1);
-      m0 = __ballot(has && lb == 0);
-      if (lane == 0) {
-        L.ri[260 + w] = __popcll(mv);
-        L.ri[264 + w] = __popcll(m0);
+      if (wide) {
+        // (both halves of the wave carry the same 32 points: the low words count; label 0 = valid and not label 1)
+        const int nv = __popc((unsigned)__ballot(has));  // (a ballot of the whole wave: not under `lane == 0`)
+        if (lane == 0) {
+          L.ri[260 + w] = __popc((unsigned)mv);
+          L.ri[264 + w] = nv - __popc((unsigned)m1);
+          L.ri[268 + w] = (int)(unsigned)m1;
+        }
+      } else {
+        m0 = __ballot(has && lb == 0);
+        if (lane == 0) {
+          L.ri[260 + w] = __popcll(mv);
+          L.ri[264 + w] = __popcll(m0);
+        }
       }
       lb_prev = lb;
     }
     __syncthreads();  // (one barrier: __syncthreads_count is three)
     c0_tile = L.ri[264] + L.ri[265] + L.ri[266] + L.ri[267];
     const int ch_tile = L.ri[260] + L.ri[261] + L.ri[262] + L.ri[263];
+    if (wide) {
+      const int g2 = (wu & 1) * 2;
+      m1 = (unsigned long long)(unsigned)L.ri[268 + g2] | ((unsigned long long)(unsigned)L.ri[269 + g2] << 32);
+      m0 = ~m1 & (cg >= 64 ? ~0ull : cg > 0 ? (1ull << cg) - 1ull : 0ull);
+    }
     PH_ADD(10);
     LV_ADD(lvl, 9);
     // update_cluster_means: per-cluster sums = Labels^T X on the matrix cores; wave w
@@ -1956,7 +2106,16 @@ __device__ int node_kmeans_part(const Lds& L, const double* pts, int* perm, int*
     // two independent accumulator chains (groups of 4 points alternate between them): a dependent
     // chain of 16 x 3 matrix instructions per wave was most of this phase
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    if (w * 64 < cnt) {
+    if (wide) {
+      if (cg > 0) {
+        const int li = lane & 3;
+        const unsigned long long sel = li == 0 ? m0 : li == 1 ? m1 : 0ull;
+        if (nb > 2)
+          kmeans_label_sums_chain<true>(L, sel, a0, a1, a2);
+        else
+          kmeans_label_sums_chain<false>(L, sel, a0, a1, a2);
+      }
+    } else if (w * 64 < cnt) {
       const int li = lane & 3;
       const unsigned long long sel = li == 0 ? m0 : li == 1 ? m1 : 0ull;
       if (nb > 2)
@@ -1981,10 +2140,19 @@ __device__ int node_kmeans_part(const Lds& L, const double* pts, int* perm, int*
       // (grouped like the parts of the level kernels when one 256-point tile stands in for two 128-point
       // parts -- L.KG < 4 -- so that a node's sums do not depend on the tile that held it)
       double sum = 0.0;
-      for (int g0 = 0; g0 < kThreads / 64; g0 += L.KG) {
+      if (wide) {
+        // a group's chain `a` (wave g) + its chain `b` (wave g + 2) is what its wave summed before; the two groups
+        // then add up in wave order as below (the waves without points added + 0.0 to a sum that is never - 0.0)
         double gs = 0.0;
-        for (int wv = g0; wv < g0 + L.KG; ++wv) gs += L.kred[(wv * 2 + c) * 48 + j];
+        gs += L.kred[(0 * 2 + c) * 48 + j] + L.kred[(2 * 2 + c) * 48 + j];
+        gs += L.kred[(1 * 2 + c) * 48 + j] + L.kred[(3 * 2 + c) * 48 + j];
         sum += gs;
+      } else {
+        for (int g0 = 0; g0 < kThreads / 64; g0 += L.KG) {
+          double gs = 0.0;
+          for (int wv = g0; wv < g0 + L.KG; ++wv) gs += L.kred[(wv * 2 + c) * 48 + j];
+          sum += gs;
+        }
       }
       L.sums[c * D + j] = sum;
       if (np == 1) {
@@ -2054,6 +2222,7 @@ __device__ int node_kmeans_part(const Lds& L, const double* pts, int* perm, int*
   if (min(n0, count - n0) < min_size) return n0;  // split rejected (:1521-1522): no partition needed
   // ---- stable partition by label (label 0 first) ----
   // ranks inside the tile from wave ballots; offsets of this part from the partners' counts
+  if (wide) lb = (L.ri[268 + (t >> 5)] >> (t & 31)) & 1;  // back to one point per thread (t < 128: the last iteration's mask words)
   const bool valid = t < cnt;
   const unsigned long long pm0 = __ballot(valid && lb == 0);
   const unsigned long long lt = (1ull << lane) - 1ull;
@@ -2612,8 +2781,11 @@ __device__ __forceinline__ void split_body(const RebuildArgs& a, const Lds& L, c
   const unsigned long long tag0 = ((unsigned long long)a.epoch << 24) | ((unsigned long long)(level & 0xffff) << 8);
   int* bar = a.tree ? nb : a.kbar + (((size_t)level * a.runs + run) * a.maxw + slot) * kBarStride;
   PH_T0();
-  const int n0 = node_kmeans_part(L, a.pts_scaled + (size_t)run * a.n * D, v.perm, v.perm2, start, count, D,
-                                  v.estore + (size_t)cur * v.NS, q, np, kp0, kp1, bar, min_size, tag0, level);
+  const double* kpts = a.pts_scaled + (size_t)run * a.n * D;
+  const double* kes = v.estore + (size_t)cur * v.NS;
+  const int n0 = kmeans_wide_form(L, D)
+                     ? node_kmeans_part<true>(L, kpts, v.perm, v.perm2, start, count, D, kes, q, np, kp0, kp1, bar, min_size, tag0, level)
+                     : node_kmeans_part<false>(L, kpts, v.perm, v.perm2, start, count, D, kes, q, np, kp0, kp1, bar, min_size, tag0, level);
   PH_ADD(4);
   LV_T0();
   if (n0 < 0) {
