@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from .marginals import Marginals
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_ENV = "DYNHIP_LIB"
 
@@ -128,6 +130,9 @@ SIGNATURES = {
     "dh_merged_resample": (_i, [_vp, _dbl, C.c_int64, _vp]),
     "dh_merged_gather": (_i, [_vp, C.c_int64, _vp, _vp]),
     "dh_merged_release": (_i, [_vp]),
+    "dh_merged_quantile": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "dh_merged_hist1d": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp]),
+    "dh_merged_hist2d": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "dh_set_rwalk_items": (_i, [_vp, _i, C.c_longlong]),
     "dh_slice_batch_philox": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _dbl, _dbl, _i, _i, _u64, _u64, _u64,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -254,10 +259,11 @@ MERGED_FIELDS = dict(logl=(0, np.float64, False), logvol=(1, np.float64, False),
 SUMMARY_FIELDS = ("niter", "logz", "logzerr", "h", "ess", "ncall")
 
 
-class DeviceMergedRun(dict):
+class DeviceMergedRun(dict, Marginals):
     """The merged run of Context.merge_runs / merge_kept: it lives on the device (one per context, replaced by the
     context's next merge); only what is asked for comes to the host.  `summary`: niter (points), logz, logzerr, h,
-    ess, ncall (sum over the points; 0 without per-point bookkeeping)."""
+    ess, ncall (sum over the points; 0 without per-point bookkeeping).  quantile / histogram / histogram2d /
+    corner_data (marginals.Marginals) are computed on the device too: dh_merged_quantile, _hist1d, _hist2d."""
 
     def __init__(self, ctx, summary, ndim, have_pt):
         super().__init__()
@@ -327,6 +333,37 @@ class DeviceMergedRun(dict):
         out = np.empty((len(idx), self.ndim))
         if len(idx):
             ctx._check_merge(ctx.lib.dh_merged_gather(ctx.handle, len(idx), _ptr(idx), _ptr(out)))
+        return out
+
+    def _cols_ptr(self, cols):
+        """NULL for all columns in order (the C calls' own default), else the list."""
+        return None if np.array_equal(cols, np.arange(self.ndim)) else _ptr(cols)
+
+    def _quantile(self, q, cols):
+        ctx = self._live()
+        q, cols = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(cols, dtype=np.int32)
+        out = np.empty((len(cols), len(q)))
+        ctx._check_merge(ctx.lib.dh_merged_quantile(ctx.handle, len(q), _ptr(q), len(cols), self._cols_ptr(cols),
+                                                    _ptr(out)))
+        return out
+
+    def _hist1d(self, cols, edges, weighted, ranges=None):
+        ctx = self._live()
+        cols, edges = np.ascontiguousarray(cols, dtype=np.int32), np.ascontiguousarray(edges, dtype=np.float64)
+        nb = edges.shape[1] - 1
+        out = np.empty((len(cols), nb))
+        ctx._check_merge(ctx.lib.dh_merged_hist1d(ctx.handle, len(cols), self._cols_ptr(cols), nb, _ptr(edges),
+                                                  int(weighted), _ptr(out)))
+        return out
+
+    def _hist2d(self, pairs, xedges, yedges, weighted):
+        ctx = self._live()
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        xedges, yedges = np.ascontiguousarray(xedges, dtype=np.float64), np.ascontiguousarray(yedges, dtype=np.float64)
+        nbx, nby = xedges.shape[1] - 1, yedges.shape[1] - 1
+        out = np.empty((len(pairs), nbx, nby))
+        ctx._check_merge(ctx.lib.dh_merged_hist2d(ctx.handle, len(pairs), _ptr(pairs), nbx, nby, _ptr(xedges),
+                                                  _ptr(yedges), int(weighted), _ptr(out)))
         return out
 
     def to_merged_run(self):

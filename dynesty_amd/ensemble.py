@@ -13,6 +13,8 @@ is asked for them.
 """
 import numpy as np
 
+from .marginals import Marginals
+
 RECORD_FIELDS = ("run", "logz", "logzerr", "niter", "ncall", "h")
 
 
@@ -200,16 +202,59 @@ def combine_logz(table):
     return float(lz[ok].mean()), se, n
 
 
-class MergedRun(dict):
+class MergedRun(dict, Marginals):
     """Result of `merge_static_runs`: the fields of the reference's merged
     `Results` (utils.merge_runs) that are defined for an ensemble of static
-    runs, with attribute access."""
+    runs, with attribute access.  quantile / histogram / histogram2d /
+    corner_data (marginals.Marginals) are NumPy here; the device's merged run
+    (_lib.DeviceMergedRun) offers the same four computed where it lives."""
     __getattr__ = dict.get
 
     def importance_weights(self):
         """Normalised posterior weights exp(logwt - logz[-1])."""
         w = np.exp(self["logwt"] - self["logz"][-1])
         return w / w.sum()
+
+    @property
+    def ndim(self):
+        return self["samples"].shape[1]
+
+    def _column(self, c):
+        if not 0 <= c < self.ndim:
+            raise ValueError(f"column {c} outside [0, {self.ndim})")
+        return self["samples"][:, c]
+
+    def _quantile(self, q, cols):
+        """utils.quantile (utils.py:1190-1234) with a stable argsort; q = 0 and q = 1 are the column's minimum and
+        maximum exactly (np.interp's ends wherever the first weight of the order is positive)."""
+        if not len(q) or not ((q >= 0.0) & (q <= 1.0)).all():  # (NaN fails both)
+            raise ValueError("Quantiles must be between 0. and 1.")
+        w = self.importance_weights()
+        out = np.empty((len(cols), len(q)))
+        for i, c in enumerate(cols):
+            x = self._column(c)
+            idx = np.argsort(x, kind="stable")
+            cdf = np.cumsum(w[idx])[:-1]
+            cdf /= cdf[-1]
+            out[i] = np.interp(q, np.append(0, cdf), x[idx])
+            # the ends as the device gives them: np.interp returns the LAST point of cdf 0 at q = 0, which is not the
+            # minimum where the first weights of the order are 0.0 (a run that spans thousands of nats)
+            out[i, q == 0.0], out[i, q == 1.0] = x[idx[0]], x[idx[-1]]
+        return out
+
+    def _hist1d(self, cols, edges, weighted, ranges=None):
+        w = self.importance_weights() if weighted else None
+        if ranges is None:
+            return np.array([np.histogram(self._column(c), bins=e, weights=w)[0] for c, e in zip(cols, edges)],
+                            dtype=np.float64)
+        # equal-width bins: NumPy sums each bin on its own there (its explicit-edge form differences a cumulative sum)
+        return np.array([np.histogram(self._column(c), bins=edges.shape[1] - 1, range=tuple(r), weights=w)[0]
+                         for c, r in zip(cols, ranges)], dtype=np.float64)
+
+    def _hist2d(self, pairs, xedges, yedges, weighted):
+        w = self.importance_weights() if weighted else None
+        return np.array([np.histogram2d(self._column(i), self._column(j), bins=(xe, ye), weights=w)[0]
+                         for (i, j), xe, ye in zip(pairs, xedges, yedges)], dtype=np.float64)
 
 
 def merge_static_runs(dead_logl, niter, live_logl, dead_u=None, live_u=None,

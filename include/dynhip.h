@@ -659,6 +659,37 @@ int dh_merged_resample(dh_ctx* ctx, double u0, int64_t n_out, int64_t* idx_out);
 int dh_merged_gather(dh_ctx* ctx, int64_t n, const int64_t* idx_or_null, double* out_v);
 int dh_merged_release(dh_ctx* ctx);
 
+/* ---- marginals of the merged run --------------------------------------------------------
+ * All three work on the merged run's parameter rows (the SAMPLES field) and normalised weights (the WEIGHT field)
+ * where they live; only the results come to the host.  Every sum of weights is a sum of the integers
+ * W_i = llrint(w_i 2^62): exact and independent of order, so the results are bitwise reproducible.  cols_or_null:
+ * ncol column indices (repeats allowed, at most 512), or NULL with ncol = ndim for all columns in order.
+ * DH_ERR_ARG (the merged run stays in place): no merged run, a column outside [0, ndim), a size cap, and what each
+ * call names below.
+ *
+ * Weighted quantiles -- utils.quantile(x, q, weights) (utils.py:1190-1234), which plotting._make_subplots's spans
+ * are too (plotting.py:80-93).  The order of a column is (value, point index) ascending = np.argsort(kind="stable");
+ * C_k = the sum of W over its first k points, Norm = C_{M-1} (the reference's cumsum(sw)[:-1]).  q = 0: the column
+ * minimum; q = 1 or q Norm >= Norm: the maximum (np.interp's ends); otherwise with T = q Norm and k the largest with
+ * C_k <= T: x_(k) + (T - C_k) / W_(k) (x_(k+1) - x_(k)).  out: ncol x nq.  DH_ERR_ARG: nq outside [1, 16], a q
+ * outside [0, 1] or NaN.  DH_ERR_VALUE: Norm = 0 for a column and a q inside (0, 1) (the reference divides by zero;
+ * q = 0 and q = 1, the extremes, do not depend on Norm and are returned for such a column too). */
+int dh_merged_quantile(dh_ctx* ctx, int nq, const double* q, int ncol, const int32_t* cols_or_null, double* out);
+/* 1-D weighted histograms -- np.histogram(x, bins, weights=weights) as plotting.py:1356 calls it.  edges: per column
+ * nbins + 1 non-decreasing finite values.  A point falls in bin i = the largest i with edges[i] <= x;
+ * x == edges[nbins] belongs to the last bin; points outside are dropped (np.histogram's membership, bin for bin).
+ * out (ncol x nbins): the bins' sums of W scaled by 2^-62, or with weighted = 0 the counts.  DH_ERR_ARG: nbins outside
+ * [1, 4096], decreasing or non-finite edges. */
+int dh_merged_hist1d(dh_ctx* ctx, int ncol, const int32_t* cols_or_null, int nbins, const double* edges, int weighted,
+                     double* out);
+/* 2-D weighted histograms -- np.histogram2d(x, y, bins, weights=weights) as plotting.py:2159-2294 calls it.  pairs:
+ * npair x 2 columns (x, y); xedges npair x (nbx + 1), yedges npair x (nby + 1); the membership rule of
+ * dh_merged_hist1d per axis, a point counts where both axes are inside.  out: npair x nbx x nby.  DH_ERR_ARG:
+ * nbx x nby above 16384 (one pair's table of 64-bit sums in a workgroup's LDS), npair outside [1, 65536], decreasing
+ * or non-finite edges. */
+int dh_merged_hist2d(dh_ctx* ctx, int npair, const int32_t* pairs, int nbx, int nby, const double* xedges,
+                     const double* yedges, int weighted, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -669,6 +669,22 @@ def gen_merge_device(out, merge_npz):
     print("wrote", out, len(g), "arrays")
 
 
+MARGINAL_Q = [0, 0.001, 0.025, 0.16, 0.5, 0.84, 0.975, 0.999, 1]
+
+
+def gen_merge_marginals(out, merge_npz):
+    """Credible intervals of the merged run merge.npz already holds (tests/test_merge_marginals_cpu.py,
+    tests/test_gpu_merge_marginals.py): utils.quantile(ref/samples[:, c], q, weights=ref/importance_weights) for
+    c = 0..2 at MARGINAL_Q."""
+    from dynesty import utils as dyu
+    m = np.load(merge_npz)
+    samples, w = m["ref/samples"], m["ref/importance_weights"]
+    q = np.array(MARGINAL_Q, dtype=np.float64)
+    g = dict(q=q, quantile=np.array([dyu.quantile(samples[:, c], q, weights=w) for c in range(3)], dtype=np.float64))
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(g), "arrays")
+
+
 if __name__ == "__main__":
     import_reference()
     gdir = os.path.join(ROOT, "tests", "golden")
@@ -692,5 +708,7 @@ if __name__ == "__main__":
         gen_merge(os.path.join(gdir, "merge.npz"))
     if "merge_device" in which:  # not in the default list; reads merge.npz, which stays as it is
         gen_merge_device(os.path.join(gdir, "merge_device.npz"), os.path.join(gdir, "merge.npz"))
+    if "merge_marginals" in which:  # not in the default list; reads merge.npz, which stays as it is
+        gen_merge_marginals(os.path.join(gdir, "merge_marginals.npz"), os.path.join(gdir, "merge.npz"))
     if "livesets" in which:  # not in the default list: two partial reference runs (minutes)
         gen_livesets(os.path.join(gdir, "livesets.npz"))
