@@ -685,11 +685,36 @@ def gen_merge_marginals(out, merge_npz):
     print("wrote", out, len(g), "arrays")
 
 
+def _ell_hp_one(key):
+    import ell_hp_ref
+    return key, ell_hp_ref.case_record(key)
+
+
+def gen_ell_hp(out):
+    """High-precision results (mpmath, 50 digits) of the ellipsoid linear algebra on the seeded cases of
+    tests/ell_cases.py (tests/test_ell_hp_cpu.py, tests/test_gpu_ell_hp.py).  Nothing of the reference project is
+    involved: the reference here is tests/ell_hp_ref.py.  Outputs only -- the inputs are regenerated from their seeds.
+    A quarter of an hour of mpmath, spread over the processors."""
+    import multiprocessing
+    import ell_hp_ref
+    keys = ell_hp_ref.all_case_keys()
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        records = dict(pool.imap_unordered(_ell_hp_one, keys, chunksize=1))
+    g = ell_hp_ref.pack_fixture(records)
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(keys), "cases,", len(g), "arrays")
+
+
 if __name__ == "__main__":
-    import_reference()
     gdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(gdir, exist_ok=True)
     which = sys.argv[1:] or ["bounding", "proposals", "rng", "runs", "friends", "wide", "nsloop"]
+    if "ell_hp" in which:  # not in the default list; needs no reference project (tests/ell_hp_ref.py is the reference)
+        gen_ell_hp(os.path.join(gdir, "ell_hp.npz"))
+        which = [w for w in which if w != "ell_hp"]
+        if not which:
+            sys.exit(0)
+    import_reference()
     if "bounding" in which:
         gen_bounding(os.path.join(gdir, "bounding.npz"))
     if "proposals" in which:
