@@ -1,11 +1,12 @@
 // MultiEllipsoid / Ellipsoid rebuild on the device (kernels K1-K4 of SURVEY.md).
 //
-// One workgroup owns one live set ("run") and executes the whole rebuild --
-// bounding ellipsoid of the root, the recursive k=2 split
-// (reference bounding.py:1464-1563) as a level-ordered worklist, the bottom-up
-// BIC-style accept test, and the coverage check of MultiEllipsoid.update
-// (bounding.py:632-686) -- in ONE launch: no host round trips, no inter-
-// workgroup synchronisation.  An ensemble of runs is a grid of workgroups.
+// The bounding ellipsoid of the root, the recursive k=2 split (reference bounding.py:1464-1563), the bottom-up
+// BIC-style accept test and the coverage check of MultiEllipsoid.update (bounding.py:632-686) of a whole ensemble of
+// live sets ("runs"), as a fixed sequence of launches with no host round trip: k_root_parts, per tree level k_split
+// and k_ell, k_tree for what is deeper, k_finish, k_out_eig (the sequence: the pipeline comment in front of carve; the grids and
+// where the scratch lies: rebuild_plan.h).  All nodes of a level -- of every run -- are worked on concurrently; the
+// workgroups that share one node or one root exchange tagged words and meet at spin waits, so they are launched in
+// groups that are resident together.
 //
 // Data layout: points stay row-major (N x D, fp64) in HBM/L2; a permutation
 // array keeps every tree node a contiguous segment (stable partition = the
@@ -21,15 +22,16 @@
 #include <type_traits>
 #include <vector>
 #include "eig_wave.h"
+#include "rebuild_plan.h"
 
 using namespace dh;
+using namespace dh_plan;
 using dh_eig::jacobi_wave;
 using dh_eig::sort_eigs_wave;
 using dh_eig::wave_sync;
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr double kRoundDelta = 1e-3;  // bounding.py:1420
 constexpr double kMaxCond = 1e12;     // bounding.py:1311
 constexpr double kEigMult = 10.0;     // bounding.py:1326
@@ -643,7 +645,6 @@ __device__ void node_std(const Lds& L, const double* pts, const int* perm, int s
 // of these loops read two LDS operands per FMA (~1250 ds_reads per point for the quadratic
 // form), the MFMA forms read one operand pair per 1024 FMAs.
 typedef double mfma_acc __attribute__((ext_vector_type(4)));
-constexpr int kBarStride = 16;  // ints between part-barrier counters (one per 64-byte line)
 constexpr int kMfmaMinDim = 10;  // below this the quadratic form stays on the VALU
 #define DH_MFMA_F64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 #define DH_MFMA_F64_4X4(a, b, c) __builtin_amdgcn_mfma_f64_4x4x4f64((a), (b), (c), 0, 0, 0)
@@ -2283,27 +2284,18 @@ __device__ __forceinline__ double logaddexp_d(double x, double y) {
   return x + y;  // NaN
 }
 
-// ---- the rebuild as a level-synchronous kernel pipeline ----------------------
-//   k_root_parts (grid = runs x ceil(n/TP))  root ellipsoid by cooperating resident parts, per-run scale, worklist seed
-//   k_split  (grid = runs * maxw)     one workgroup per splittable node of the
-//                                     level: k-means (k=2) + stable partition
-//   k_ell    (grid = runs * 2 maxw)   one workgroup per new child: bounding
-//                                     ellipsoid; queues it for the next level
-//   ... repeated for `levels` levels (idle workgroups exit immediately) ...
-//   k_finish (grid = runs)            bottom-up accept test, emit, coverage check
-// All nodes of a level -- of every run -- are processed concurrently, so a
-// single run is no longer confined to one CU and nothing returns to the host.
-
-// LDS without the Jacobi work buffers (16-byte multiple); they follow at this offset
-// when everything fits kLdsLimit, else they overlay the point tile.
-constexpr size_t kLdsLimit = 159 * 1024;
-// separate Jacobi buffers only while two workgroups still fit one CU's 160 KB
-constexpr size_t kLdsSeparate = 79 * 1024;
-__host__ __device__ inline size_t rebuild_lds_base_bytes(int D, int TP) {
-  const int LD = D | 1;
-  const size_t dbl = (size_t)TP * LD + 4 * (size_t)D * LD + 7 * (size_t)D + 2 + kThreads + 128;
-  return (dbl * 8 + (320 + (size_t)D + 8) * 4 + 15) & ~(size_t)15;
-}
+// ---- the rebuild as a kernel pipeline (grids and chunks: rebuild_plan.h) ----------------------
+//   k_root_parts (runs x ceil(n/256), in co-resident chunks of runs)  root ellipsoid by cooperating parts, per-run
+//                                     scale, worklist seed; k_root_eig solves the root's eigen-system on a side stream
+//   per level L of a balanced tree's depth:
+//   k_split  (runs x parts of level L, in co-resident chunks of runs)  one workgroup per tps-point part of a splittable
+//                                     node: k-means (k=2) + stable partition
+//   k_ell_wave (runs x <= 2^(L+1), D <= 13)  one wavefront per small new child
+//   k_ell    (runs x <= 2^(L+1))      the other children: bounding ellipsoid; queues them for the next level
+//   k_tree   (persistent workers)     whatever is deeper, and what k_ell declined, from a work queue
+//   k_finish (runs)                   bottom-up accept test, emit, coverage check
+//   k_out_eig (runs x <= 8)           eigen-systems of the emitted ellipsoids
+// Idle workgroups exit immediately; nothing returns to the host.
 
 __device__ __forceinline__ void carve(Lds& L, unsigned char* smem, int D, int TP = kThreads) {
   L.LD = D | 1;  // odd leading dimension: conflict-free column walks
@@ -2361,15 +2353,7 @@ __device__ __forceinline__ void carve(Lds& L, unsigned char* smem, int D, int TP
   L.JV[1] = jb + 3 * (size_t)P * L.JLD;
 }
 
-// k_split's own, smaller layout: the resident tile of tps points and what the k-means touches (scale, centroids,
-// sums, the partial-sum scratch, the integer scratch) -- 31 KB at D = 25, tps = 128, so that five workgroups share a
-// CU.  (With the common layout's 77 KB two did, and a level of the 64-run bench rebuild has 512-1 000 busy parts:
-// every level took two rounds of workgroups, 135 us instead of the 65-70 us it takes alone.)
-__host__ __device__ inline size_t split_lds_bytes(int D, int TP) {
-  const int LD = D | 1;
-  return ((((size_t)TP * LD + 5 * (size_t)D + 2 + kThreads + 128) * 8 + (320 + (size_t)D + 8) * 4) + 15) & ~(size_t)15;
-}
-
+// k_split's own, smaller layout (split_lds_bytes)
 __device__ __forceinline__ void carve_split(Lds& L, unsigned char* smem, int D, int TP) {
   L.LD = D | 1;
   L.TP = TP;
@@ -3020,12 +3004,6 @@ __device__ __forceinline__ void k_ell_impl(const RebuildArgs& a, int level, int 
 // the nodes that fit, marks them by their finite fmax, and k_ell skips those.  A node whose eigen-free path does not
 // apply (spd_fast false) is left untouched for k_ell.
 constexpr int kWaveDeclined = 2;
-constexpr int kWaveCap = 128;
-
-__host__ __device__ inline size_t wave_lds_bytes(int D) {
-  const int LD = D | 1;
-  return ((((size_t)kWaveCap * LD + 4 * (size_t)D * LD + 2 * (size_t)D + 64) * 8) + 15) & ~(size_t)15;
-}
 
 __device__ __forceinline__ void carve_wave(Lds& L, unsigned char* smem, int D) {
   L.LD = D | 1;
@@ -3766,13 +3744,6 @@ __global__ void __launch_bounds__(1024)
   }
 }
 
-size_t rebuild_lds_bytes(int D, int TP = kThreads) {
-  const size_t base = rebuild_lds_base_bytes(D, TP);
-  const int P = (D + 1) & ~1;
-  const size_t jb = 4 * (size_t)P * (P | 1) * 8;
-  return base + jb > kLdsSeparate ? base : base + jb;  // else the Jacobi buffers overlay the tile
-}
-
 }  // namespace
 
 extern "C" {
@@ -3841,285 +3812,260 @@ int dh::enlarge_launch_masked(dh_ctx* ctx, int runs, int max_ells, const int32_t
   return hip_ok(ctx, hipGetLastError(), "enlarge launch") ? DH_OK : DH_ERR_HIP;
 }
 
+namespace {
+
+// D > 44 (the common LDS layout does not fit): the wide constructions of wide.hip
+int wide_dispatch(dh_ctx* ctx, int runs, const double* pts, int n, int d, int mode, int max_ells, int32_t* nells,
+                  int32_t* status, double* ctrs, double* covs, double* ams, double* axes, double* axlens, double* logvols,
+                  int32_t* leaf_of_point, int32_t* nnodes, const int* active, const int* n_arr) {
+  if (mode == 1 && !active && !n_arr)
+    return wide_single_launch(ctx, runs, pts, n, d, nells, status, ctrs, covs, ams, axes, axlens, logvols);
+  if (mode == 0 && !n_arr)  // (with a run mask: the device-resident loop's MultiEllipsoid.update, host-driven)
+    return wide_multi_launch(ctx, runs, pts, n, d, max_ells, nells, status, ctrs, covs, ams, axes, axlens, logvols,
+                             leaf_of_point, nnodes, active);
+  if (mode == 1 && active && !n_arr)  // the device-resident loop's masked Ellipsoid.update
+    return wide_single_launch_masked(ctx, runs, pts, n, d, nells, status, ctrs, covs, ams, axes, axlens, logvols, active);
+  // ragged batch above d = 44 (the bootstrap replicas of a wide bound): the wide constructions take one point
+  // set per call, so the sizes (and the mask) come to the host and the sets go through one after the other
+  std::vector<int32_t> h_n((size_t)runs), h_act;
+  if (!hip_ok(ctx, hipMemcpyAsync(h_n.data(), n_arr, (size_t)runs * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H ragged sizes"))
+    return DH_ERR_HIP;
+  if (active) {
+    h_act.resize((size_t)runs);
+    if (!hip_ok(ctx, hipMemcpyAsync(h_act.data(), active, (size_t)runs * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H run mask"))
+      return DH_ERR_HIP;
+  }
+  if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync")) return DH_ERR_HIP;
+  const size_t dd = (size_t)d * d;
+  for (int s = 0; s < runs; ++s) {
+    if (active && !h_act[(size_t)s]) continue;
+    const int cnt = h_n[(size_t)s];
+    if (cnt < 0 || cnt > n) return fail(ctx, DH_ERR_ARG, "rebuild: ragged size %d of set %d outside [0, %d]", cnt, s, n);
+    const size_t o = (size_t)s * max_ells;
+    int rc;
+    if (cnt < 2) {  // bounding_ellipsoid of a single point raises (bounding.py:1383-1385)
+      const int32_t st = DH_ERR_VALUE, one = 1;
+      rc = hip_ok(ctx, hipMemcpyAsync(status + s, &st, 4, hipMemcpyHostToDevice, ctx->stream), "H2D") &&
+                   hip_ok(ctx, hipMemcpyAsync(nells + s, &one, 4, hipMemcpyHostToDevice, ctx->stream), "H2D") &&
+                   hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync")
+               ? DH_OK
+               : DH_ERR_HIP;
+    } else if (mode == 1) {
+      rc = wide_single_launch(ctx, 1, pts + (size_t)s * n * d, cnt, d, nells + s, status + s, ctrs + o * d, covs + o * dd,
+                              ams + o * dd, axes + o * dd, axlens + o * d, logvols + o);
+    } else {
+      rc = wide_multi_launch(ctx, 1, pts + (size_t)s * n * d, cnt, d, max_ells, nells + s, status + s, ctrs + o * d,
+                             covs + o * dd, ams + o * dd, axes + o * dd, axlens + o * d, logvols + o,
+                             leaf_of_point ? leaf_of_point + (size_t)s * n : nullptr, nnodes ? nnodes + s : nullptr);
+    }
+    if (rc) return rc;
+  }
+  return DH_OK;
+}
+
+// Every kernel's limit of dynamic LDS is at least what it is launched with, and what its occupancy is asked with (the
+// query counts the dynamic allocation only up to the limit).  The limit is a per-device attribute, raised when a
+// call needs more than any before it on that device.
+int ensure_lds_attributes(dh_ctx* ctx, const RebuildPlan& p) {
+  DH_DEV_MEMO(attr_lds);
+  DH_DEV_MEMO(attr_top);
+  DH_DEV_MEMO(attr_fin);
+  auto raise = [&](const void* kf, size_t bytes, const char* what) {
+    return hip_ok(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), what);
+  };
+  if (p.lds > attr_lds) {
+    const void* ks[8] = {(const void*)k_root_parts, (const void*)k_split, (const void*)k_ell<false>,
+                         (const void*)k_ell<true>, (const void*)k_out_eig, (const void*)k_root_eig,
+                         (const void*)k_tree, (const void*)k_ell<false, true>};
+    for (const void* kf : ks)
+      if (!raise(kf, p.lds, "hipFuncSetAttribute(rebuild LDS)")) return DH_ERR_HIP;
+    attr_lds = p.lds;
+    attr_top = 0;  // (k_ell's limit was just lowered to lds)
+  }
+  if (p.lds_top > attr_top) {  // (after the common one, which would lower it)
+    if (!raise((const void*)k_ell<false>, p.lds_top, "hipFuncSetAttribute(k_ell LDS)") ||
+        !raise((const void*)k_ell<false, true>, p.lds_top, "hipFuncSetAttribute(k_ell LDS)") ||
+        !raise((const void*)k_ell<true>, p.lds_top, "hipFuncSetAttribute(k_ell LDS)"))
+      return DH_ERR_HIP;
+    attr_top = p.lds_top;
+  }
+  if (p.lds_fin > attr_fin) {
+    if (!raise((const void*)k_finish, p.lds_fin, "hipFuncSetAttribute(k_finish LDS)")) return DH_ERR_HIP;
+    attr_fin = p.lds_fin;
+  }
+  return DH_OK;
+}
+
+// How many workgroups of the kernels that meet at spin waits a CU holds: asked of the runtime, not assumed.
+RebuildCaps query_caps(dh_ctx* ctx, const RebuildPlan& p) {
+  RebuildCaps c = {ctx->num_cu, 0, 0, 0, ctx->split_resident_pct, ctx->coop_launch};
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&c.occ_root, (const void*)k_root_parts, kThreads, p.lds) != hipSuccess)
+    c.occ_root = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&c.occ_split, (const void*)k_split, kThreads, p.lds_split) != hipSuccess)
+    c.occ_split = 1;
+  if (p.tail && hipOccupancyMaxActiveBlocksPerMultiprocessor(&c.occ_tree, (const void*)k_tree, kThreads, p.lds) != hipSuccess)
+    c.occ_tree = 1;
+  return c;
+}
+
+// The context's scratch buffer, grown on demand, with the arrays of rebuild_layout handed to `a` (and the queue
+// form's partial-sum slots to kpart_tail) and the counters zeroed.
+int ensure_workspace(dh_ctx* ctx, const RebuildPlan& p, RebuildArgs& a, double*& kpart_tail) {
+  RebuildLayout l;
+  rebuild_layout(p, l);
+  if (l.total > ctx->rebuild_ws_cap) {
+    if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync")) return DH_ERR_HIP;
+    if (ctx->rebuild_ws) (void)hipFree(ctx->rebuild_ws);
+    ctx->rebuild_ws = nullptr;
+    ctx->rebuild_ws_cap = 0;
+    if (!hip_ok(ctx, hipMalloc((void**)&ctx->rebuild_ws, l.total), "hipMalloc(rebuild scratch)")) return DH_ERR_NOMEM;
+    ctx->rebuild_ws_cap = l.total;
+    // (the k-means partials are recognised by their tags: no stale word of a fresh allocation may pass for one)
+    if (!hip_ok(ctx, hipMemsetAsync(ctx->rebuild_ws, 0, l.total, ctx->stream), "memset(rebuild scratch)")) return DH_ERR_HIP;
+  }
+  auto at = [&](auto*& ptr, RebuildArray id) {
+    const RebuildSlot& s = l.slot[id];
+    ptr = s.bytes ? (std::remove_reference_t<decltype(ptr)>)(ctx->rebuild_ws + s.off) : nullptr;
+  };
+  at(a.perm, kWsPerm);
+  at(a.perm2, kWsPerm2);
+  at(a.lab, kWsLab);
+  at(a.nodes, kWsNodes);
+  at(a.estore, kWsEstore);
+  at(a.reslist, kWsReslist);
+  at(a.split_list, kWsSplitList);
+  at(a.ell_list, kWsEllList);
+  at(a.scale_g, kWsScaleG);
+  at(a.pts_scaled, kWsPtsScaled);
+  at(a.part_list, kWsPartList);
+  at(a.part_base, kWsPartBase);
+  at(a.kpart, kWsKpart);
+  at(kpart_tail, kWsKpartTail);
+  at(a.rootbuf, kWsRootbuf);
+  at(a.fin_lse, kWsFinLse);
+  at(a.fin_int, kWsFinInt);
+  at(a.out_node, kWsOutNode);
+  at(a.out_fast, kWsOutFast);
+  at(a.root_eig, kWsRootEig);
+  int* cnt;
+  at(cnt, kWsCounters);
+  const RebuildCounters& c = l.cnt;
+  a.nnodes_dev = cnt + c.nnodes;
+  a.nsplit = cnt + c.nsplit;
+  a.nell = cnt + c.nell;
+  a.nparts = cnt + c.nparts;
+  a.kerr = cnt + c.kerr;
+  a.kbar = cnt + c.kbar;
+  a.kp_top = p.tail ? cnt + c.kp_top : nullptr;
+  a.tq_ctl = p.tail ? cnt + c.tq_ctl : nullptr;
+  a.nbar = p.tail ? cnt + c.nbar : nullptr;
+  a.tq_items = p.tail ? (unsigned long long*)(cnt + c.tq_items) : nullptr;
+  return hip_ok(ctx, hipMemsetAsync(cnt, 0, c.ints * 4, ctx->stream), "memset(rebuild counters)") ? DH_OK : DH_ERR_HIP;
+}
+
+// k_root_parts, in chunks of runs whose parts are resident together
+int launch_root(dh_ctx* ctx, const RebuildPlan& p, RebuildArgs& a) {
+  for (int r0 = 0; r0 < p.runs; r0 += p.root_chunk) {
+    a.root_run0 = r0;
+    const int cr = p.runs - r0 < p.root_chunk ? p.runs - r0 : p.root_chunk;
+    if (!hip_ok(ctx, launch_all_resident(ctx, k_root_parts, dim3(cr * p.rp), dim3(kThreads), p.lds, a, p.rp), "k_root_parts launch"))
+      return DH_ERR_HIP;
+  }
+  a.root_run0 = 0;
+  return DH_OK;
+}
+
+// The root's full eigen-system on the side stream, beside the tree; the caller joins ev_join in front of k_finish.
+int fork_root_eig(dh_ctx* ctx, const RebuildPlan& p, const RebuildArgs& a) {
+  if (!ctx->side_stream) {
+    // lowest priority: what runs here (the root's eigen-system) is off the critical path and must not
+    // take workgroup slots / LDS from the level kernels that are ready at the same moment
+    int pr_lo = 0, pr_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);
+    if (!hip_ok(ctx, hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, pr_lo), "hipStreamCreate(side)") ||
+        !hip_ok(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming), "hipEventCreate") ||
+        !hip_ok(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming), "hipEventCreate"))
+      return DH_ERR_HIP;
+  }
+  if (!hip_ok(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "hipEventRecord(fork)") ||
+      !hip_ok(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0), "hipStreamWaitEvent(fork)"))
+    return DH_ERR_HIP;
+  hipLaunchKernelGGL(k_root_eig, dim3(p.runs), dim3(kThreads), p.lds, ctx->side_stream, a);
+  return hip_ok(ctx, hipEventRecord(ctx->ev_join, ctx->side_stream), "hipEventRecord(join)") ? DH_OK : DH_ERR_HIP;
+}
+
+// The level pipeline: k_split, k_ell_wave for the small children, k_ell for the rest
+void launch_levels(dh_ctx* ctx, const RebuildPlan& p, const RebuildArgs& a) {
+  for (int L = 0; L < p.nlev; ++L) {
+    const RebuildLevel& l = p.level[L];
+    hipLaunchKernelGGL(k_split, dim3(l.nchunk * l.cr * l.gp), dim3(kThreads), p.lds_split, ctx->stream, a, L, l.gp, l.cr);
+    if (l.wave) hipLaunchKernelGGL(k_ell_wave, dim3(p.runs * l.gw_l), dim3(64), p.lds_wave, ctx->stream, a, L, l.gw_l);
+    const dim3 grid(p.runs * l.g_ell);
+    if (p.fast && p.tail)
+      hipLaunchKernelGGL((k_ell<false, true>), grid, dim3(kThreads), l.lds_ell, ctx->stream, a, L, l.g_ell, l.wave, l.tp);
+    else if (p.fast)
+      hipLaunchKernelGGL(k_ell<false>, grid, dim3(kThreads), l.lds_ell, ctx->stream, a, L, l.g_ell, l.wave, l.tp);
+    else
+      hipLaunchKernelGGL(k_ell<true>, grid, dim3(kThreads), l.lds_ell, ctx->stream, a, L, l.g_ell, 0, l.tp);
+  }
+}
+
+// The work-queue tail: persistent workers; the queue form indexes its own partial-sum slots
+void launch_tail(dh_ctx* ctx, const RebuildPlan& p, const RebuildArgs& a, double* kpart_tail) {
+  RebuildArgs at = a;
+  at.tree = 1;
+  at.kpart = kpart_tail;
+  at.maxp = p.kp_cap;
+  hipLaunchKernelGGL(k_tree, dim3(p.g_tree), dim3(kThreads), p.lds, ctx->stream, at);
+}
+
+}  // namespace
+
 int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int d, int mode, int max_ells,
                             int32_t* nells, int32_t* status, double* ctrs, double* covs, double* ams,
                             double* axes, double* axlens, double* logvols, int32_t* leaf_of_point,
                             int32_t* nnodes, const int* active, const int* n_arr) {
   DH_CHECK_CTX(ctx);
   if (runs <= 0) return DH_OK;
-  if (!pts || n < 1 || d < 1 || max_ells < 1 || (mode != 0 && mode != 1))
+  if (!pts || !rebuild_shape_ok(n, d, mode, max_ells))
     return fail(ctx, DH_ERR_ARG, "rebuild: bad arguments (n=%d d=%d mode=%d)", n, d, mode);
-  const size_t lds = rebuild_lds_bytes(d);
-  if (lds > kLdsLimit) {
-    if (mode == 1 && !active && !n_arr)
-      return wide_single_launch(ctx, runs, pts, n, d, nells, status, ctrs, covs, ams, axes, axlens,
-                                logvols);
-    if (mode == 0 && !n_arr)  // (with a run mask: the device-resident loop's MultiEllipsoid.update, host-driven)
-      return wide_multi_launch(ctx, runs, pts, n, d, max_ells, nells, status, ctrs, covs, ams, axes, axlens,
-                               logvols, leaf_of_point, nnodes, active);
-    if (mode == 1 && active && !n_arr)  // the device-resident loop's masked Ellipsoid.update
-      return wide_single_launch_masked(ctx, runs, pts, n, d, nells, status, ctrs, covs, ams, axes, axlens, logvols,
-                                       active);
-    // ragged batch above d = 44 (the bootstrap replicas of a wide bound): the wide constructions take one point
-    // set per call, so the sizes (and the mask) come to the host and the sets go through one after the other
-    std::vector<int32_t> h_n((size_t)runs), h_act;
-    if (!hip_ok(ctx, hipMemcpyAsync(h_n.data(), n_arr, (size_t)runs * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H ragged sizes"))
-      return DH_ERR_HIP;
-    if (active) {
-      h_act.resize((size_t)runs);
-      if (!hip_ok(ctx, hipMemcpyAsync(h_act.data(), active, (size_t)runs * 4, hipMemcpyDeviceToHost, ctx->stream), "D2H run mask"))
-        return DH_ERR_HIP;
-    }
-    if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync")) return DH_ERR_HIP;
-    const size_t dd = (size_t)d * d;
-    for (int s = 0; s < runs; ++s) {
-      if (active && !h_act[(size_t)s]) continue;
-      const int cnt = h_n[(size_t)s];
-      if (cnt < 0 || cnt > n) return fail(ctx, DH_ERR_ARG, "rebuild: ragged size %d of set %d outside [0, %d]", cnt, s, n);
-      const size_t o = (size_t)s * max_ells;
-      int rc;
-      if (cnt < 2) {  // bounding_ellipsoid of a single point raises (bounding.py:1383-1385)
-        const int32_t st = DH_ERR_VALUE, one = 1;
-        rc = hip_ok(ctx, hipMemcpyAsync(status + s, &st, 4, hipMemcpyHostToDevice, ctx->stream), "H2D") &&
-                     hip_ok(ctx, hipMemcpyAsync(nells + s, &one, 4, hipMemcpyHostToDevice, ctx->stream), "H2D") &&
-                     hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync")
-                 ? DH_OK
-                 : DH_ERR_HIP;
-      } else if (mode == 1) {
-        rc = wide_single_launch(ctx, 1, pts + (size_t)s * n * d, cnt, d, nells + s, status + s, ctrs + o * d, covs + o * dd,
-                                ams + o * dd, axes + o * dd, axlens + o * d, logvols + o);
-      } else {
-        rc = wide_multi_launch(ctx, 1, pts + (size_t)s * n * d, cnt, d, max_ells, nells + s, status + s, ctrs + o * d,
-                               covs + o * dd, ams + o * dd, axes + o * dd, axlens + o * d, logvols + o,
-                               leaf_of_point ? leaf_of_point + (size_t)s * n : nullptr, nnodes ? nnodes + s : nullptr);
-      }
-      if (rc) return rc;
-    }
-    return DH_OK;
-  }
+  if (rebuild_lds_bytes(d) > kLdsLimit)
+    return wide_dispatch(ctx, runs, pts, n, d, mode, max_ells, nells, status, ctrs, covs, ams, axes, axlens, logvols,
+                         leaf_of_point, nnodes, active, n_arr);
+  RebuildSwitches sw;
+  sw.fast = env_int("DH_REBUILD_FAST", 1);
+  sw.deep = env_int("DH_DEEP", 1);
+  sw.deep_from = env_int("DH_DEEP_FROM", -1);
+  sw.root_parts = env_int("DH_ROOT_PARTS", 1);
+  sw.wave_ell = env_int("DH_WAVE_ELL", 1);
+  RebuildPlan p;
+  char err[kPlanErrLen];
+  int rc = rebuild_plan_sizes(runs, n, d, mode, max_ells, sw, sizeof(Node), p, err);
+  if (rc) return fail(ctx, rc, "%s", err);
+  if ((rc = ensure_lds_attributes(ctx, p))) return rc;
+  if ((rc = rebuild_plan_grids(p, query_caps(ctx, p), err))) return fail(ctx, rc, "%s", err);
   RebuildArgs a;
-  a.root_run0 = 0;
   a.pts = pts;
   a.n = n;
   a.d = d;
   a.runs = runs;
   a.mode = mode;
-  // every split creates two children of >= 2d points each: <= n/d nodes + root
-  a.max_nodes = mode == 1 ? 1 : (n / d + 3);
+  a.max_nodes = p.max_nodes;
   a.max_ells = max_ells;
-  a.prefactor = d * log(2.0) + d * lgamma(1.5) - lgamma(d / 2.0 + 1.0);
-  const int LD = d | 1;
-  const size_t NS = (size_t)d + 3 * (size_t)d * d + d + (size_t)d * LD;
-  a.reslist_cap = a.max_nodes * 24 + 64;
-  // scratch: reuse a context-owned buffer (grown on demand)
-  const size_t b_perm = (size_t)runs * n * 4, b_lab = (size_t)runs * n;
-  const size_t b_nodes = (size_t)runs * a.max_nodes * sizeof(Node);
-  const size_t b_es = (size_t)runs * a.max_nodes * NS * 8;
-  const size_t b_res = (size_t)runs * a.reslist_cap * 4;
-  a.maxw = n / (4 * d) + 1;
-  // depth: a balanced tree needs log2(n / 2d) levels; unbalanced splits need more.  The level kernels are launched
-  // for lv levels, the work-queue form (k_tree) takes whatever is deeper.
-  int lv = 4;
-  while ((1 << lv) < n / (2 * d) + 1) ++lv;
-  a.levels = mode == 1 ? 0 : (2 * lv + 8);
-  // 128 points per k-means part: five k_split workgroups per CU (see carve_split) -- or 256 where five 256-point
-  // tiles fit a CU's LDS as well (D <= 13): half the parts to meet at the device-scope barrier.  Measured (round 5, 64
-  // sets, tools/r5_tps.sh): eggbox 2-D 4.48 -> 4.10 ms, two blobs 5-D 0.720 -> 0.704; at D = 25 256-point parts lose
-  // (1.26 -> 1.40 ms: two workgroups per CU).
-  a.tps = split_lds_bytes(d, 256) * 5 <= kLdsLimit ? 256 : 128;
-  a.maxp = n / a.tps + a.maxw + 1;
-  // eigen-free tree nodes (MultiEllipsoid.update only: Ellipsoid.update's single node IS the output)
-  a.fast = mode == 0 && env_int("DH_REBUILD_FAST", 1) != 0 ? 1 : 0;  // diagnostic: 0 = eigh on every node
-  // The tree is built by the level pipeline (k_split / k_ell per level) for a balanced tree's depth (lv levels: an
-  // idle level pair costs 10 us, and the bench trees use lv = 6 exactly);
-  // whatever is deeper -- unbalanced splits -- is handed to persistent workers on a work queue (k_tree: the same
-  // node routines, any depth, any node size; in the common case it finds its queue empty and leaves).
-  // (The WHOLE tree by the work-queue form, DH_DEEP_FROM=0, gives the same bits but was measured slower in round 3:
-  // 64 C2 runs 1.44 against 1.29 ms -- it loses the level pipeline's five k_split workgroups per CU.)
+  a.prefactor = p.prefactor;
+  a.reslist_cap = p.reslist_cap;
+  a.maxw = p.maxw;
+  a.levels = p.levels;
+  a.tps = p.tps;
+  a.maxp = p.maxp;
+  a.fast = p.fast;
   a.tree = 0;  // (1 in k_tree's copy of the arguments only)
-  // level kernels for a balanced tree's depth, the work-queue tail for the rest (DH_DEEP=0: every level
-  // by level kernels and no tail, as does the diagnostic slow mode; DH_DEEP_FROM=f: the tail takes over at level f)
-  // (one level pair fewer -- a balanced tree's last split level is the one with n >> L >= 4 d: five pairs for the
-  // bench's 2000 x 25 live sets instead of six -- was measured in round 5 and is SLOWER: 1.411 against 1.382 ms per
-  // 64-run rebuild, eggbox 5.02 against 4.51: real trees are not balanced, and what is deeper than the level kernels
-  // goes to the work-queue tail, which costs more than an almost idle level pair)
-  int nlev = a.levels;
-  if (a.fast && env_int("DH_DEEP", 1) != 0) nlev = a.levels < lv ? a.levels : lv;
-  if (a.fast) {
-    const int f = env_int("DH_DEEP_FROM", -1);
-    if (f >= 0 && f < a.levels) nlev = f;
-  }
-  const bool tail = a.fast && nlev < a.levels;
-  a.tree_from = tail ? nlev : a.levels + 1;
-  a.tq_cap = 0;
-  a.kp_cap = 0;
-  if (tail) {
-    // partial-sum slots of the multi-part nodes the queue form may meet: a depth has at most n / tps + (nodes) parts
-    a.kp_cap = a.levels * (n / a.tps + 1) + 8;
-    // items: one ellipsoid per node, and per split node ceil(count / tps) parts
-    a.tq_cap = runs * (2 * a.max_nodes + a.levels * (n / a.tps + 1) + 8);
-  }
-  const size_t lds_split = split_lds_bytes(d, a.tps);
-  // the parts of one node meet at a device-scope barrier, so they must all be resident at the
-  // same time: 256 parts (65 536 points per run) fit the 256 CUs with room to spare
-  if ((long long)n * d >= (1ll << 31))  // (rows are addressed by 32-bit element offsets: stage_tile)
-    return fail(ctx, DH_ERR_ARG, "rebuild: n x d = %lld elements per run exceeds 2^31", (long long)n * d);
-  if (mode == 0 && n > 256 * kThreads)
-    return fail(ctx, DH_ERR_ARG, "rebuild: MultiEllipsoid.update supports at most %d points per run (n = %d)",
-                256 * kThreads, n);
-  // k_finish: tree (and result list) in LDS when they fit behind the standard layout
-  size_t lds_fin = lds;
-  a.fin_extra_off = 0;
-  a.fin_res_lds = 0;
-  {
-    const size_t off = (lds + 15) & ~(size_t)15;
-    const size_t nb_nodes = (size_t)a.max_nodes * sizeof(Node), nb_res = (size_t)a.reslist_cap * 4;
-    if (off + nb_nodes <= kLdsLimit) {
-      a.fin_extra_off = (int)off;
-      lds_fin = off + nb_nodes;
-      if (lds_fin + nb_res <= kLdsLimit) {
-        a.fin_res_lds = 1;
-        lds_fin += nb_res;
-      }
-    }
-  }
-  // parts of the root: cooperative only while all parts of all runs are resident with room to spare
-  // (a part idles at a barrier while part 0 runs the eigensolver, so on a full chip it only costs slots)
-  // Co-residency.  Workgroups that meet at a spin barrier -- the parts of the root, the parts of one
-  // k-means node -- must be on the chip together.  How many workgroups of a kernel fit is asked of the
-  // runtime (occupancy API x CU count), not assumed.  The whole grid of k_root_parts must fit (every part
-  // waits for part 0's solve); for k_split a CHUNK of runs must (round 5: cr runs x the level's parts per run, sized
-  // to this capacity; inside a chunk the workgroups are ordered part-major so that every run starts at once): chunks
-  // have consecutive workgroup ids and the dispatcher hands out workgroups in id order, so the lowest unfinished
-  // chunk is always dispatched in full as the workgroups in front of it finish, and those never wait for it.
-  int cap_root = 0, cap_split = 0, cap_split_level = 0, cap_tree = 0;
-  {
-    const int ncu = ctx->num_cu;
-    int occ_root = 0, occ_split = 0;
-    // (the LDS attribute must be in place for the query to count the dynamic allocation)
-    (void)hipFuncSetAttribute((const void*)k_root_parts, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)k_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_root, (const void*)k_root_parts, kThreads, lds) != hipSuccess)
-      occ_root = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_split, (const void*)k_split, kThreads, lds_split) != hipSuccess)
-      occ_split = 1;
-    cap_root = ncu * (occ_root > 0 ? occ_root : 1);
-    cap_split = ncu * (occ_split > 0 ? occ_split : 1);
-    cap_split_level = cap_split;  // (k_split's own: what its chunks are sized to)
-    if (tail) {
-      int occ_tree = 0;
-      (void)hipFuncSetAttribute((const void*)k_tree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_tree, (const void*)k_tree, kThreads, lds) != hipSuccess)
-        occ_tree = 1;
-      cap_tree = ncu * (occ_tree > 0 ? occ_tree : 1);
-      if (cap_tree < cap_split) cap_split = cap_tree;  // the parts of a node may be k_tree workgroups
-    }
-  }
-  // The parts of a run meet at spin waits, so what is launched together must be resident together: when all runs x
-  // parts do not fit, the root goes in chunks of runs that do (round 6; before, 128 runs x 8 parts fell back to the
-  // single-workgroup root, 447 us against 81 us per 64 runs).
-  int rp = n > 1 ? (n + kThreads - 1) / kThreads : 1;
-  if (rp > cap_root || (ctx->coop_launch && (long long)runs * rp > cap_root)) rp = 1;
-  if (env_int("DH_ROOT_PARTS", 1) == 0) rp = 1;  // diagnostic: the single-workgroup root for every run
-  int root_chunk = runs;
-  if (rp > 1 && (long long)runs * rp > cap_root) root_chunk = cap_root / rp;
-  if (mode == 0 && (n + a.tps - 1) / a.tps > cap_split)
-    return fail(ctx, DH_ERR_ARG, "rebuild: the %d parts of a %d-point node exceed the %d co-resident workgroups of k_split",
-                (n + a.tps - 1) / a.tps, n, cap_split);
-  // zeroed counters: nnodes | nsplit (levels+1) | nell (levels) | nparts (levels+1) | kerr | kbar (levels x maxw)
-  // ... | kp_top (runs) | tq_ctl (64) | nbar (runs x max_nodes x kBarStride) | tq_items (tq_cap x 2 ints)   [k_tree]
-  const size_t n_cnt_old = (size_t)runs * ((size_t)3 * a.levels + 5 + (size_t)a.levels * a.maxw * kBarStride);
-  const size_t n_cnt_tree = tail ? (size_t)runs + 64 + (size_t)runs * a.max_nodes * kBarStride + 2 * (size_t)a.tq_cap + 2 : 0;
-  const size_t b_cnt = (n_cnt_old + n_cnt_tree) * 4;
-  a.rootbuf_stride = 2 * ((size_t)rp * (2 * (size_t)d + (size_t)d * d + 1) + (size_t)d * d + 8);  // (value, tag) pairs
-  const size_t b_rb = (size_t)runs * a.rootbuf_stride * 8;
-  const size_t b_fl = (size_t)runs * a.max_nodes * 8, b_fi = (size_t)runs * a.max_nodes * 2 * 4;
-  const size_t b_pl = (size_t)2 * runs * a.maxp * 2 * 4, b_pb = (size_t)2 * runs * a.maxw * 4;
-  const size_t b_kp = mode == 1 ? 0 : (size_t)2 * runs * a.maxp * (2 * (size_t)d + 2) * 16;  // (value, tag) pairs
-  const size_t b_kpt = tail ? (size_t)2 * runs * a.kp_cap * (2 * (size_t)d + 2) * 16 : 0;  // the queue form's own
-  const size_t b_sl = (size_t)2 * runs * a.maxw * 4, b_el = (size_t)(a.levels > 0 ? a.levels : 1) * runs * 2 * a.maxw * 4;
-  const size_t b_sc = (size_t)runs * d * 8;
-  const size_t b_ps = mode == 1 ? 0 : (size_t)runs * n * d * 8;
-  const size_t b_of = a.fast ? (size_t)runs * max_ells * 4 : 0;
-  const size_t b_re = a.fast ? (size_t)runs * (2 * (size_t)d * d + d + 2) * 8 : 0;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t total = al(b_perm) * 2 + al(b_lab) + al(b_nodes) + al(b_es) + al(b_res) + al(b_cnt) +
-                       al(b_sl) + al(b_el) + al(b_sc) + al(b_ps) + al(b_pl) + al(b_pb) + al(b_kp) + al(b_kpt) + al(b_rb) + al(b_fl) + al(b_fi) +
-                       2 * al(b_of) + al(b_re);
-  if (total > ctx->rebuild_ws_cap) {
-    if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync")) return DH_ERR_HIP;
-    if (ctx->rebuild_ws) (void)hipFree(ctx->rebuild_ws);
-    ctx->rebuild_ws = nullptr;
-    ctx->rebuild_ws_cap = 0;
-    if (!hip_ok(ctx, hipMalloc((void**)&ctx->rebuild_ws, total), "hipMalloc(rebuild scratch)"))
-      return DH_ERR_NOMEM;
-    ctx->rebuild_ws_cap = total;
-    // (the k-means partials are recognised by their tags: no stale word of a fresh allocation may pass for one)
-    if (!hip_ok(ctx, hipMemsetAsync(ctx->rebuild_ws, 0, total, ctx->stream), "memset(rebuild scratch)")) return DH_ERR_HIP;
-  }
-  char* w = ctx->rebuild_ws;
-  a.perm = (int*)w;
-  w += al(b_perm);
-  a.perm2 = (int*)w;
-  w += al(b_perm);
-  a.lab = (unsigned char*)w;
-  w += al(b_lab);
-  a.nodes = (Node*)w;
-  w += al(b_nodes);
-  a.estore = (double*)w;
-  w += al(b_es);
-  a.reslist = (int*)w;
-  w += al(b_res);
-  int* cnt = (int*)w;
-  w += al(b_cnt);
-  a.nnodes_dev = cnt;
-  a.nsplit = cnt + runs;
-  a.nell = a.nsplit + (size_t)(a.levels + 1) * runs;
-  a.nparts = a.nell + (size_t)a.levels * runs;
-  a.kerr = a.nparts + (size_t)(a.levels + 1) * runs;
-  a.kbar = a.kerr + runs;
-  a.kp_top = a.nbar = a.tq_ctl = nullptr;
-  a.tq_items = nullptr;
-  if (tail) {
-    a.kp_top = cnt + n_cnt_old;
-    a.tq_ctl = a.kp_top + runs;
-    a.nbar = a.tq_ctl + 64;
-    int* q = a.nbar + (size_t)runs * a.max_nodes * kBarStride;
-    if (((uintptr_t)q) & 7) ++q;  // 8-byte items
-    a.tq_items = (unsigned long long*)q;
-  }
-  a.split_list = (int*)w;
-  w += al(b_sl);
-  a.ell_list = (int*)w;
-  w += al(b_el);
-  a.scale_g = (double*)w;
-  w += al(b_sc);
-  a.pts_scaled = (double*)w;
-  w += al(b_ps);
-  a.part_list = (int*)w;
-  w += al(b_pl);
-  a.part_base = (int*)w;
-  w += al(b_pb);
-  a.kpart = (double*)w;
-  w += al(b_kp);
-  double* kpart_tail = (double*)w;
-  w += al(b_kpt);
-  a.rootbuf = (double*)w;
-  w += al(b_rb);
-  a.fin_lse = (double*)w;
-  w += al(b_fl);
-  a.fin_int = (int*)w;
-  w += al(b_fi);
-  a.out_node = a.out_fast = nullptr;
-  a.root_eig = nullptr;
-  if (a.fast) {
-    a.out_node = (int*)w;
-    w += al(b_of);
-    a.out_fast = (int*)w;
-    w += al(b_of);
-    a.root_eig = (double*)w;
-    w += al(b_re);
-  }
+  a.tree_from = p.tree_from;
+  a.tq_cap = p.tq_cap;
+  a.kp_cap = p.kp_cap;
+  a.fin_extra_off = p.fin_extra_off;
+  a.fin_res_lds = p.fin_res_lds;
+  a.rootbuf_stride = p.rootbuf_stride;
   a.nells = nells;
   a.status = status;
   a.ctrs = ctrs;
@@ -4132,145 +4078,16 @@ int dh::rebuild_launch_full(dh_ctx* ctx, int runs, const double* pts, int n, int
   a.nnodes_out = nnodes;
   a.active = active;
   a.n_arr = n_arr;
+  double* kpart_tail = nullptr;
+  if ((rc = ensure_workspace(ctx, p, a, kpart_tail))) return rc;
   a.epoch = ++ctx->rebuild_epoch;
-  // k_ell's top levels: a tile of 512 points, if it fits (D <= 30)
-  size_t lds_top = rebuild_lds_bytes(d, 2 * kThreads);
-  if (lds_top > kLdsLimit || mode != 0) lds_top = 0;
-  DH_DEV_MEMO(attr_lds);
-  DH_DEV_MEMO(attr_top);
-  if (lds > attr_lds) {
-    const void* ks[8] = {(const void*)k_root_parts, (const void*)k_split, (const void*)k_ell<false>,
-                         (const void*)k_ell<true>, (const void*)k_out_eig, (const void*)k_root_eig,
-                         (const void*)k_tree, (const void*)k_ell<false, true>};
-    for (const void* kf : ks)
-      if (!hip_ok(ctx, hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                  "hipFuncSetAttribute(rebuild LDS)"))
-        return DH_ERR_HIP;
-    attr_lds = lds;
-    attr_top = 0;  // (k_ell's limit was just lowered to lds)
-  }
-  if (lds_top > attr_top) {
-    if (!hip_ok(ctx, hipFuncSetAttribute((const void*)k_ell<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_top),
-                "hipFuncSetAttribute(k_ell LDS)") ||
-        !hip_ok(ctx, hipFuncSetAttribute((const void*)k_ell<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_top),
-                "hipFuncSetAttribute(k_ell LDS)") ||
-        !hip_ok(ctx, hipFuncSetAttribute((const void*)k_ell<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_top),
-                "hipFuncSetAttribute(k_ell LDS)"))
-      return DH_ERR_HIP;
-    attr_top = lds_top;
-  }
-  DH_DEV_MEMO(attr_fin);
-  if (lds_fin > attr_fin) {
-    if (!hip_ok(ctx, hipFuncSetAttribute((const void*)k_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fin),
-                "hipFuncSetAttribute(k_finish LDS)"))
-      return DH_ERR_HIP;
-    attr_fin = lds_fin;
-  }
-  if (!hip_ok(ctx, hipMemsetAsync(cnt, 0, b_cnt, ctx->stream), "memset(rebuild counters)")) return DH_ERR_HIP;
-  for (int r0 = 0; r0 < runs; r0 += root_chunk) {
-    a.root_run0 = r0;
-    const int cr = runs - r0 < root_chunk ? runs - r0 : root_chunk;
-    if (!hip_ok(ctx, launch_all_resident(ctx, k_root_parts, dim3(cr * rp), dim3(kThreads), lds, a, rp), "k_root_parts launch"))
-      return DH_ERR_HIP;
-  }
-  a.root_run0 = 0;
-  bool forked = false;
-  if (a.fast) {
-    if (!ctx->side_stream) {
-      // lowest priority: what runs here (the root's eigen-system) is off the critical path and must not
-      // take workgroup slots / LDS from the level kernels that are ready at the same moment
-      int pr_lo = 0, pr_hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);
-      if (!hip_ok(ctx, hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, pr_lo), "hipStreamCreate(side)") ||
-          !hip_ok(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming), "hipEventCreate") ||
-          !hip_ok(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming), "hipEventCreate"))
-        return DH_ERR_HIP;
-    }
-    if (!hip_ok(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "hipEventRecord(fork)") ||
-        !hip_ok(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0), "hipStreamWaitEvent(fork)"))
-      return DH_ERR_HIP;
-    hipLaunchKernelGGL(k_root_eig, dim3(runs), dim3(kThreads), lds, ctx->side_stream, a);
-    if (!hip_ok(ctx, hipEventRecord(ctx->ev_join, ctx->side_stream), "hipEventRecord(join)")) return DH_ERR_HIP;
-    forked = true;
-  }
-  // small nodes by one wavefront each (k_ell_wave), from the level where the average child fits -- where eight such
-  // nodes (128-point tile, four D x D matrices) share a CU's LDS: D <= 13.  Measured (round 5, 64 sets): eggbox 2-D
-  // 6.54 -> 4.67 ms, two blobs 5-D 0.91 -> 0.75, 3-D blob 0.71 -> 0.62; above D = 13 the forms tried lost (1.29 -> 1.41
-  // ms at D = 25).  DH_WAVE_ELL=0: off.
-  int wave_from = nlev;
-  const size_t lds_wave = wave_lds_bytes(d);
-  if (a.fast && env_int("DH_WAVE_ELL", 1) != 0 && lds_wave * 8 <= kLdsLimit) {
-    wave_from = 0;
-    while (wave_from < nlev && (n >> (wave_from + 1)) > 2 * kWaveCap) ++wave_from;
-  }
-  // (Leaves built beside the level kernels -- on the side stream, or by a light kernel of their own on the main
-  // stream -- were measured no better in round 6: EXPERIMENTS.md.)
-  for (int L = 0; L < nlev; ++L) {
-    // Grids no larger than the level can need (round 5): level L splits at most 2^L nodes of a run -- at most
-    // n / tps + 2^L parts -- and creates at most 2^(L + 1) children.  Workgroups are dispatched at a finite rate: the
-    // 2 368 / 2 688-workgroup grids of the worst case cost the first levels 60 us each at 64 runs, most of them for
-    // workgroups that found nothing to do.
-    const long long nodes_L = L < 20 ? (1ll << L) : (1ll << 20);
-    const int gp = (int)(a.maxp < (long long)n / a.tps + nodes_L + 1 ? a.maxp : (long long)n / a.tps + nodes_L + 1);
-    const int ge = (int)(2ll * a.maxw < 2 * nodes_L ? 2ll * a.maxw : 2 * nodes_L);
-    // runs per chunk: cr * gp workgroups resident together, with an eighth of the chip to spare (the side stream's
-    // kernels hold slots too; a chunk that does not fit would still finish -- they do not wait for it -- only later)
-    // (ONE context per GPU is assumed, as for k_root_parts: a second process -- or a long-lived foreign kernel -- can
-    // hold slots this sizing counts on; DH_SPLIT_RESIDENT_PCT lowers the share of the chip a chunk may claim (87 by
-    // default, e.g. 40 on a GPU shared by two processes), and the spin limit fails a starved run instead of hanging)
-    // (round 6) no more k_ell / k_ell_wave workgroups than a few rounds of the chip: a workgroup takes every ge-th child
-    // of its run (the kernels' own loops).  The bound above is the worst case; a many-mode tree's deep level (eggbox 2-D,
-    // nlive 5 000, 16 runs: 1 065 parts and 1 252 children possible per run, some 200 there) was 20 000 workgroups of
-    // which a fifth found work, and the dispatch of the rest half the level's time.
-    const int split_room = cap_split_level > 0 ? (int)((long long)cap_split_level * ctx->split_resident_pct / 100) : 1;
-    // (k_split keeps the worst case gp: a loop over parts in it costs registers it does not have -- 5 spilled VGPRs --
-    // and, where the parts are real, serialises two k-means chains)
-    const int cap_ell = 2 * ctx->num_cu;  // (k_ell: two workgroups per CU)
-    const int want_e = 8 * cap_ell / runs > 1 ? 8 * cap_ell / runs : 1;
-    const int ge_l = want_e < ge ? want_e : ge;
-    // (k_ell_wave: 16 384 one-wavefront workgroups; 8 192 / 4 096 / 2 048 measured on the C3 loop: 0.088 / 0.089 / 0.089 s
-    // against 0.087 -- its time is its nodes, not its dispatch)
-    const int want_w = 16384 / runs > 1 ? 16384 / runs : 1;
-    const int gw_l = want_w < ge ? want_w : ge;
-    int cr = cap_split_level > 0 ? split_room / gp : 1;
-    cr = cr < 1 ? 1 : (cr > runs ? runs : cr);
-    const int nchunk = (runs + cr - 1) / cr;
-    cr = (runs + nchunk - 1) / nchunk;  // (chunks of equal size)
-    hipLaunchKernelGGL(k_split, dim3(nchunk * cr * gp), dim3(kThreads), lds_split, ctx->stream, a, L, gp, cr);
-    const int wave = L >= wave_from ? 1 : 0;
-    if (wave) hipLaunchKernelGGL(k_ell_wave, dim3(runs * gw_l), dim3(64), lds_wave, ctx->stream, a, L, gw_l);
-    // The top levels' children are several 256-point tiles each and few (one workgroup per CU or less): their
-    // workgroups stage 512 points at once -- a 1 000-point child is gathered three times instead of seven (covariance
-    // pass 2 + Mahalanobis pass 1, the last tile still staged), a 500-point child once instead of three times.  Only
-    // while the level's workgroups fill at most HALF the CUs (round 6: at 128 runs level 0's 256 one-per-CU workgroups
-    // with the big tile lost to two-per-CU with the small one, 2.09 -> 2.05 ms; the LDS of such a tile allows no second one).
-    const bool top = lds_top > 0 && (n >> (L + 1)) > kThreads && 2ll * runs * ge <= ctx->num_cu;
-    const size_t lds_ell = top ? lds_top : lds;
-    const int tp = top ? 2 * kThreads : kThreads;
-    if (a.fast && tail)
-      hipLaunchKernelGGL((k_ell<false, true>), dim3(runs * ge_l), dim3(kThreads), lds_ell, ctx->stream, a, L, ge_l, wave, tp);
-    else if (a.fast)
-      hipLaunchKernelGGL(k_ell<false>, dim3(runs * ge_l), dim3(kThreads), lds_ell, ctx->stream, a, L, ge_l, wave, tp);
-    else
-      hipLaunchKernelGGL(k_ell<true>, dim3(runs * ge), dim3(kThreads), lds_ell, ctx->stream, a, L, ge, 0, tp);
-  }
-  if (tail) {
-    // persistent workers: as many as can be resident (the parts of a node meet at spin barriers), but
-    // no more than the tree can ever keep busy; the queue form indexes its own partial-sum slots
-    RebuildArgs at = a;
-    at.tree = 1;
-    at.kpart = kpart_tail;
-    at.maxp = a.kp_cap;
-    const long long want = (long long)runs * (n / a.tps + 2 * a.maxw + 1);
-    const int G = (int)(want < cap_tree ? (want < 1 ? 1 : want) : cap_tree);
-    hipLaunchKernelGGL(k_tree, dim3(G), dim3(kThreads), lds, ctx->stream, at);
-  }
-  if (forked && !hip_ok(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)")) return DH_ERR_HIP;
-  hipLaunchKernelGGL(k_finish, dim3(runs), dim3(kThreads), lds_fin, ctx->stream, a);
-  if (a.fast) {
-    const int G = max_ells < 8 ? max_ells : 8;
-    hipLaunchKernelGGL(k_out_eig, dim3(runs * G), dim3(kThreads), lds, ctx->stream, a, G);
-  }
+  if ((rc = launch_root(ctx, p, a))) return rc;
+  if (p.fast && (rc = fork_root_eig(ctx, p, a))) return rc;
+  launch_levels(ctx, p, a);
+  if (p.tail) launch_tail(ctx, p, a, kpart_tail);
+  if (p.fast && !hip_ok(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)")) return DH_ERR_HIP;
+  hipLaunchKernelGGL(k_finish, dim3(runs), dim3(kThreads), p.lds_fin, ctx->stream, a);
+  if (p.fast) hipLaunchKernelGGL(k_out_eig, dim3(runs * p.g_out), dim3(kThreads), p.lds, ctx->stream, a, p.g_out);
   return hip_ok(ctx, hipGetLastError(), "rebuild launch") ? DH_OK : DH_ERR_HIP;
 }
 
@@ -4414,12 +4231,8 @@ int dh_enlarge_batch_dev(dh_ctx* ctx, int runs, int max_ells, const int32_t* nel
   if (runs <= 0) return DH_OK;
   if (!nells || !covs || !ams || !axes || !axlens || !logvols || d < 1 || max_ells < 1)
     return fail(ctx, DH_ERR_ARG, "enlarge: bad arguments");
-  const int m = runs * max_ells;
-  const int G = max_ells < 4 ? max_ells : 4;
-  hipLaunchKernelGGL(scale_logvol_kernel, dim3(runs * G), dim3(d > 64 ? 1024 : 256), (size_t)2 * d * 8 + 64, ctx->stream, m, d,
-                     covs, ams, axes, axlens, logvols, (const double*)nullptr, log_enlarge, nells,
-                     max_ells, (const int*)nullptr, (const double*)nullptr, G);
-  return hip_ok(ctx, hipGetLastError(), "enlarge launch") ? DH_OK : DH_ERR_HIP;
+  return dh::enlarge_launch_masked(ctx, runs, max_ells, nells, d, covs, ams, axes, axlens, logvols, log_enlarge, nullptr,
+                                   nullptr);
 }
 
 int dh_scale_to_logvol(dh_ctx* ctx, int m, int d, double* covs, double* ams, double* axes, double* axlens,
