@@ -580,10 +580,17 @@ int dh::friends_whiten_runs_launch(dh_ctx* ctx, int runs, const double* X, const
 
 namespace {
 inline size_t fr_al(size_t x) { return (x + 255) & ~(size_t)255; }
+// The clustering's limit: the 4 waves' delta columns [d][64] next to the metric must fit the 160 KB of LDS a workgroup
+// can have, (d^2 + 4 * 65 d) * 8 bytes = 162 792 at d = 63 and 165 888 at d = 64.  include/dynhip.h states the same.
+constexpr int kFrClusterMaxD = 63;
+constexpr size_t fr_adjacency_bytes(size_t d) { return (d * d + 4 * (d + d * 64)) * 8; }
+static_assert(fr_adjacency_bytes(kFrClusterMaxD) <= 160 * 1024 && fr_adjacency_bytes(kFrClusterMaxD + 1) > 160 * 1024,
+              "kFrClusterMaxD is the largest d whose adjacency tile fits the LDS");
 int fr_adjacency_lds(dh_ctx* ctx, int d, size_t* lds) {
-  const size_t dd = (size_t)d * d;
-  *lds = (dd + 4 * ((size_t)d + (size_t)d * 64)) * 8;
-  if (*lds > 159 * 1024) return fail(ctx, DH_ERR_ARG, "friends_update: clustering needs d <= 60 (d = %d)", d);
+  *lds = fr_adjacency_bytes((size_t)d);
+  if (d > kFrClusterMaxD)
+    return fail(ctx, DH_ERR_ARG, "friends_update: clustering (am_prev != NULL) needs d <= %d (d = %d)", kFrClusterMaxD,
+                d);
   DH_DEV_MEMO(attr_adj);
   if (*lds > attr_adj) {
     if (!hip_ok(ctx, hipFuncSetAttribute((const void*)fr_adjacency, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -593,6 +600,10 @@ int fr_adjacency_lds(dh_ctx* ctx, int d, size_t* lds) {
   }
   return DH_OK;
 }
+// fr_shape's three padded matrices: above 64 KB from d = 52, 100 KB at d = 64.  Relied on: the runtime grants a dynamic
+// LDS request up to the device's 160 KB without hipFuncAttributeMaxDynamicSharedMemorySize being raised (observed on
+// the MI355X, not a documented guarantee).  A runtime that starts to enforce the attribute fails the d = 52 ... 64 cases
+// of tests/test_gpu_friends_hp.py::test_update_within_bounds; the cure is fr_adjacency_lds's memo for this kernel.
 size_t fr_shape_lds(int d) { return ((size_t)3 * d * (d | 1) + d + 128) * 8 + (128 + d + 8) * 4; }
 }  // namespace
 

@@ -551,7 +551,12 @@ int dh_bootstrap_expand(dh_ctx* ctx, int runs, const double* pts, int n, int d, 
  * (in_mask[b*n + i] != 0 iff point i was resampled; the index bookkeeping of
  * _bootstrap_points, bounding.py:1593-1616, stays on the host).  Outputs are already scaled by
  * the radius (cov r^2, am / r^2, axes r, axes_inv / r); logvol = ln volume of ONE shape.
- * DH_ERR_VALUE: non-finite or singular covariance, or zero radius (the reference divides by 0). */
+ * 2 <= n, 1 <= d <= 64; with clustering (am_prev != NULL) d <= 63: the adjacency tile of the pairwise distances,
+ * (d^2 + 260 d) * 8 bytes, must fit the 160 KB of LDS of a workgroup -- d = 64 with a metric is DH_ERR_ARG, with
+ * am_prev = NULL it works.  The same limits hold for dh_friends_update_batch.
+ * DH_ERR_VALUE: non-finite or singular covariance, or zero radius (the reference divides by 0); the contents of
+ * the output arrays are then unspecified (the unscaled intermediates may have been written).  The batched call
+ * below leaves a failed run's outputs untouched. */
 int dh_friends_update(dh_ctx* ctx, const double* pts, int n, int d, int kind,
                       const double* am_prev, int nboot, const uint8_t* in_mask,
                       double* cov, double* am, double* axes, double* axes_inv,

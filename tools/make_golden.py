@@ -705,10 +705,38 @@ def gen_ell_hp(out):
     print("wrote", out, len(keys), "cases,", len(g), "arrays")
 
 
+def _friends_hp_one(job):
+    import friends_hp_ref
+    if isinstance(job, tuple):
+        return job, friends_hp_ref.within_record(*job)
+    return job, friends_hp_ref.update_record(job)
+
+
+def gen_friends_hp(out):
+    """High-precision results (mpmath, 50 digits) of the RadFriends / SupFriends checks on the seeded cases of
+    tests/friends_cases.py (tests/test_friends_hp_cpu.py, tests/test_gpu_friends_hp.py): partitions and their margins,
+    spectra and square roots of the exact covariances, the membership distances next to the threshold.  Nothing of the
+    reference project is involved: the reference here is tests/friends_hp_ref.py.  Outputs only -- the inputs are
+    regenerated from their seeds.  A few minutes of mpmath, spread over the processors."""
+    import multiprocessing
+    import friends_hp_ref
+    ukeys, wkeys = friends_hp_ref.all_keys()
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        records = dict(pool.imap_unordered(_friends_hp_one, ukeys + wkeys, chunksize=1))
+    g = friends_hp_ref.pack_fixture({k: records[k] for k in ukeys}, {k: records[k] for k in wkeys})
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(ukeys), "update cases,", len(wkeys), "membership cases,", len(g), "arrays")
+
+
 if __name__ == "__main__":
     gdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(gdir, exist_ok=True)
     which = sys.argv[1:] or ["bounding", "proposals", "rng", "runs", "friends", "wide", "nsloop"]
+    if "friends_hp" in which:  # not in the default list; needs no reference project (tests/friends_hp_ref.py)
+        gen_friends_hp(os.path.join(gdir, "friends_hp.npz"))
+        which = [w for w in which if w != "friends_hp"]
+        if not which:
+            sys.exit(0)
     if "ell_hp" in which:  # not in the default list; needs no reference project (tests/ell_hp_ref.py is the reference)
         gen_ell_hp(os.path.join(gdir, "ell_hp.npz"))
         which = [w for w in which if w != "ell_hp"]
