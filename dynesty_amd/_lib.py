@@ -10,6 +10,7 @@ import os
 
 import numpy as np
 
+from .errors import FIELDS as REAL_FIELDS, Errors
 from .marginals import Marginals
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -133,6 +134,8 @@ SIGNATURES = {
     "dh_merged_quantile": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     "dh_merged_hist1d": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp]),
     "dh_merged_hist2d": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "dh_merged_realize": (_i, [_vp, _u64, C.c_int64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dh_merged_realization": (_i, [_vp, _u64, C.c_int64, _i, _vp, _i, C.c_int64, C.c_int64, _vp]),
     "dh_set_rwalk_items": (_i, [_vp, _i, C.c_longlong]),
     "dh_slice_batch_philox": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _dbl, _dbl, _i, _i, _u64, _u64, _u64,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -259,11 +262,13 @@ MERGED_FIELDS = dict(logl=(0, np.float64, False), logvol=(1, np.float64, False),
 SUMMARY_FIELDS = ("niter", "logz", "logzerr", "h", "ess", "ncall")
 
 
-class DeviceMergedRun(dict, Marginals):
+class DeviceMergedRun(dict, Marginals, Errors):
     """The merged run of Context.merge_runs / merge_kept: it lives on the device (one per context, replaced by the
     context's next merge); only what is asked for comes to the host.  `summary`: niter (points), logz, logzerr, h,
     ess, ncall (sum over the points; 0 without per-point bookkeeping).  quantile / histogram / histogram2d /
-    corner_data (marginals.Marginals) are computed on the device too: dh_merged_quantile, _hist1d, _hist2d."""
+    corner_data (marginals.Marginals) are computed on the device too: dh_merged_quantile, _hist1d, _hist2d; so are
+    logz_realizations / logz_error / jitter_run / realization / reweight (errors.Errors): dh_merged_realize,
+    dh_merged_realization."""
 
     def __init__(self, ctx, summary, ndim, have_pt):
         super().__init__()
@@ -364,6 +369,49 @@ class DeviceMergedRun(dict, Marginals):
         out = np.empty((len(pairs), nbx, nby))
         ctx._check_merge(ctx.lib.dh_merged_hist2d(ctx.handle, len(pairs), _ptr(pairs), nbx, nby, _ptr(xedges),
                                                   _ptr(yedges), int(weighted), _ptr(out)))
+        return out
+
+    def _err_logl(self):
+        return self.field("logl")
+
+    @staticmethod
+    def _err_seed(seed):
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed: an unsigned 64-bit integer")
+        return int(seed)
+
+    def _err_logrwt(self, logrwt):
+        if logrwt is None:
+            return None
+        logrwt = np.ascontiguousarray(logrwt, dtype=np.float64)
+        if logrwt.shape != (self.niter,):
+            raise ValueError(f"logrwt of shape {logrwt.shape} for {self.niter} points")
+        return logrwt
+
+    def _err_realize(self, seed, first, nreal, jitter, logrwt, means):
+        ctx = self._live()
+        seed, logrwt, nreal = self._err_seed(seed), self._err_logrwt(logrwt), int(nreal)
+        if not -(1 << 63) <= int(first) < 1 << 63 or not -(1 << 31) <= nreal < 1 << 31:
+            raise ValueError("first / nreal: out of range")
+        n = max(nreal, 0)
+        lz, h, ess = np.empty(n), np.empty(n), np.empty(n)
+        mean = np.empty((n, self.ndim)) if means else None
+        ctx._check_merge(ctx.lib.dh_merged_realize(ctx.handle, seed, int(first), nreal, int(jitter), _ptr(logrwt),
+                                                   int(means), _ptr(lz), _ptr(h), _ptr(ess), _ptr(mean)))
+        return lz, h, ess, mean
+
+    def _err_field(self, seed, real, jitter, logrwt, field, first, count):
+        ctx = self._live()
+        seed, logrwt = self._err_seed(seed), self._err_logrwt(logrwt)
+        if field not in REAL_FIELDS:
+            raise ValueError(f"field {field!r}: one of {REAL_FIELDS}")
+        first = int(first)
+        count = self.niter - first if count is None else int(count)
+        if not -(1 << 63) <= int(real) < 1 << 63 or first < 0 or count < 0 or first + count > self.niter:
+            raise ValueError(f"realization {real}: [{first}, {first + count}) of {self.niter} points")
+        out = np.empty(count)
+        ctx._check_merge(ctx.lib.dh_merged_realization(ctx.handle, seed, int(real), int(jitter), _ptr(logrwt),
+                                                       MERGED_FIELDS[field][0], first, count, _ptr(out)))
         return out
 
     def to_merged_run(self):

@@ -1387,3 +1387,457 @@ int dh_merged_hist2d(dh_ctx* ctx, int npair, const int32_t* pairs, int nbx, int 
 }
 
 }  // extern "C"
+
+// ---- statistical errors of the merged run: volume-jitter realizations and reweighting -----
+//
+// Realization r (a global index) of the prior-volume sequence: point k shrinks the volume by t_k = u_k^(1 / n_k), its
+// step is s_k = log(u_k) / n_k, with u_k = uniform_double of words 2k and 2k + 1 of subsequence r of the Philox4x32-10
+// stream keyed by `seed` (utils.jitter_run, utils.py:1317-1408; tests/philox_ref.py restates the words).  jitter = 0
+// takes the merged run's own expected step -log1p(1 / n_k) (with logrwt: utils.reweight_run, utils.py:1663-1708).
+// The integrals are utils.compute_integrals' (utils.py:1411-1467) in the arithmetic of the scans above.
+//
+// A batch never holds a (realization x point) array: the words are a function of (seed, r, k), so each pass makes its
+// steps again.  me_step_sums: per-chunk sums of the steps; me_step_carry: their exclusive scan over the chunks;
+// me_integrate: ln X, ln w and the chunk's sums of w, w^2, the information's terms and w v, each scaled by the chunk's
+// own largest term; me_finish: the chunks' sums in chunk order, rescaled to the largest chunk.  A workgroup loads its
+// chunk's n, ln L, logaddexp(l_k, l_{k-1}) and logrwt once and carries kRealTile realizations through it.  Every
+// reduction has a fixed order and a realization's numbers depend on (seed, r) alone: it comes out bit-identical alone,
+// in any batch, at any position.
+namespace {
+
+constexpr int kRealTile = 4;         // realizations a workgroup carries through its chunk
+constexpr int kRealLaunch = 64;      // realizations per set of launches: the scratch is chunks x 64 x (6 + D) doubles
+constexpr int kRealMax = 65536;      // realizations per call
+constexpr int kSeg = kChunk / kT;    // a chunk's mean sums: kSeg segments of kT points, summed in segment order
+constexpr int kColTile = kT / kSeg;  // columns per step of the mean sums
+constexpr int kMeanLoads = 16;       // rows of v a thread of the mean sums has in flight
+constexpr int kFinLoads = 8;         // chunks a thread of me_finish has in flight
+constexpr int kPart = 5;             // per (realization, chunk): max ln w, max ln w without logrwt, sum w, sum w^2, sum of H's terms
+constexpr double kLnHalf = -0.6931471805599453;
+
+__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t seq, uint64_t blk, uint32_t* w) {
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  uint32_t c0 = (uint32_t)blk, c1 = (uint32_t)(blk >> 32), c2 = (uint32_t)seq, c3 = (uint32_t)(seq >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+  }
+  w[0] = c0;
+  w[1] = c1;
+  w[2] = c2;
+  w[3] = c3;
+}
+// rocrand's uniform_distribution_double(v1, v2): (0, 1], exact
+__device__ __forceinline__ double uniform_double(uint32_t w0, uint32_t w1) {
+  const unsigned long long m = (unsigned long long)w0 | ((unsigned long long)(w1 >> 11) << 32);
+  return 1.1102230246251565e-16 + (double)m * 1.1102230246251565e-16;
+}
+__device__ __forceinline__ double expected_step(int n) { return -log1p(1.0 / (double)n); }
+
+// the steps of the points k0 .. k0 + kItems - 1 (k0 a multiple of kItems: whole Philox blocks)
+__device__ __forceinline__ void real_steps(int jitter, uint64_t seed, uint64_t seq, long long k0, const int* n, double* s) {
+  if (jitter) {
+#pragma unroll
+    for (int j = 0; j < kItems; j += 2) {
+      uint32_t w[4];
+      philox4x32_10(seed, seq, (uint64_t)(k0 + j) >> 1, w);
+      s[j] = log(uniform_double(w[0], w[1])) / (double)n[j];
+      s[j + 1] = log(uniform_double(w[2], w[3])) / (double)n[j + 1];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) s[j] = expected_step(n[j]);
+  }
+}
+// one point's step (the per-point fields of one realization)
+__device__ __forceinline__ double real_step(int jitter, uint64_t seed, uint64_t seq, long long k, int n) {
+  if (!jitter) return expected_step(n);
+  uint32_t w[4];
+  philox4x32_10(seed, seq, (uint64_t)k >> 1, w);
+  const bool odd = k & 1;
+  return log(uniform_double(odd ? w[2] : w[0], odd ? w[3] : w[1])) / (double)n;
+}
+
+struct Pair2 {
+  double a, b;
+};
+struct Max2 {
+  typedef Pair2 T;
+  __device__ static T id() { return T{-INFINITY, -INFINITY}; }
+  __device__ static T op(T x, T y) { return T{fmax(x.a, y.a), fmax(x.b, y.b)}; }
+};
+struct Trip {
+  double a, b, c;
+};
+struct Sum3 {
+  typedef Trip T;
+  __device__ static T id() { return T{0.0, 0.0, 0.0}; }
+  __device__ static T op(T x, T y) { return T{x.a + y.a, x.b + y.b, x.c + y.c}; }
+};
+
+struct RArgs {
+  long long M, first;  // points; global index of this launch set's realization 0
+  int D, nblk, nreal, jitter, want_mean;
+  uint64_t seed;
+  const double *logl, *lae, *rwt, *v;  // rwt: null without logrwt
+  const int* n;
+  double *sums, *part, *mpart, *out;  // [nreal][nblk], [nreal][nblk][kPart], [nreal][nblk][D], [nreal][3 + D]
+};
+
+__global__ void __launch_bounds__(kT) me_lae(long long M, const double* __restrict__ logl, double* __restrict__ lae) {
+  const long long k = (long long)blockIdx.x * kT + threadIdx.x;
+  if (k >= M) return;
+  lae[k] = logaddexp_np(logl[k], k > 0 ? logl[k - 1] : -1.e300);
+}
+
+// a thread's kItems live counts; past the end the last point's (a clamped load: the step is masked where it is used)
+__device__ __forceinline__ void load_counts(const RArgs& a, long long k0, int* n) {
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const long long k = k0 + j < a.M ? k0 + j : a.M - 1;
+    n[j] = a.n[k];
+  }
+}
+
+__global__ void __launch_bounds__(kT) me_step_sums(RArgs a) {
+  __shared__ double lds[2 * kT];
+  const long long k0 = (long long)blockIdx.x * kChunk + (long long)threadIdx.x * kItems;
+  int n[kItems];
+  load_counts(a, k0, n);
+  const int b0 = blockIdx.y * kRealTile, nb = a.nreal - b0 < kRealTile ? a.nreal - b0 : kRealTile;
+  for (int b = 0; b < nb; ++b) {
+    double s[kItems];
+    real_steps(a.jitter, a.seed, (uint64_t)(a.first + b0 + b), k0, n, s);
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) acc += k0 + j < a.M ? s[j] : 0.0;
+    double ex, tot;
+    block_scan<SumD>(acc, lds, &ex, &tot);
+    if (threadIdx.x == 0) a.sums[(size_t)(b0 + b) * a.nblk + blockIdx.x] = tot;
+  }
+}
+
+// workgroup b: sums[b][c] becomes the sum of the chunks before c (scan_carry's order)
+__global__ void __launch_bounds__(kT) me_step_carry(RArgs a) {
+  __shared__ double lds[2 * kT];
+  double* part = a.sums + (size_t)blockIdx.x * a.nblk;
+  double carry = 0.0;
+  for (int c0 = 0; c0 < a.nblk; c0 += kT) {
+    const int c = c0 + threadIdx.x;
+    const double v = c < a.nblk ? part[c] : 0.0;
+    double ex, tot;
+    block_scan<SumD>(v, lds, &ex, &tot);
+    if (c < a.nblk) part[c] = carry + ex;
+    carry = carry + tot;
+  }
+}
+
+// dynamic LDS: the scans' 2 kT Trip; with means kRealTile x kChunk weights and kSeg x kRealTile x kColTile partial sums
+__global__ void __launch_bounds__(kT) me_integrate(RArgs a) {
+  extern __shared__ double dyn[];
+  double* wl = dyn + 2 * kT * 3;
+  double* mp = wl + kRealTile * kChunk;
+  const int t = threadIdx.x;
+  const long long kb = (long long)blockIdx.x * kChunk, k0 = kb + (long long)t * kItems;
+  int n[kItems];
+  double l[kItems + 1], lae[kItems], rw[kItems];
+  load_counts(a, k0, n);
+  {
+    const long long km = k0 > 0 ? (k0 - 1 < a.M ? k0 - 1 : a.M - 1) : 0;
+    const double lm = a.logl[km];
+    l[0] = k0 > 0 ? lm : -1.e300;
+  }
+#pragma unroll
+  for (int j = 0; j < kItems; ++j) {
+    const long long k = k0 + j < a.M ? k0 + j : a.M - 1;
+    l[j + 1] = a.logl[k];
+    lae[j] = a.lae[k];
+    rw[j] = 0.0;
+  }
+  if (a.rwt) {
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) rw[j] = a.rwt[k0 + j < a.M ? k0 + j : a.M - 1];
+  }
+  const int b0 = blockIdx.y * kRealTile, nb = a.nreal - b0 < kRealTile ? a.nreal - b0 : kRealTile;
+  for (int b = 0; b < nb; ++b) {
+    double s[kItems];
+    real_steps(a.jitter, a.seed, (uint64_t)(a.first + b0 + b), k0, n, s);
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) {
+      s[j] = k0 + j < a.M ? s[j] : 0.0;  // (a step of 0 is a weight of 0: the points past the end add nothing)
+      acc += s[j];
+    }
+    double ex, tot;
+    block_scan<SumD>(acc, dyn, &ex, &tot);
+    double run = a.sums[(size_t)(b0 + b) * a.nblk + blockIdx.x] + ex;  // ln X of the point before k0
+    double ldv[kItems], lw[kItems];
+    Pair2 mx = Max2::id();
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) {
+      ldv[j] = run + log(-expm1(s[j])) + kLnHalf;  // ln (X_{k-1} - X_k) / 2; s = 0: -inf
+      run = run + s[j];
+      const double lh = lae[j] + ldv[j];
+      lw[j] = lh + rw[j];
+      mx = Max2::op(mx, Pair2{lw[j], lh});
+    }
+    Pair2 mex, mtot;
+    block_scan<Max2>(mx, (Pair2*)dyn, &mex, &mtot);
+    const double mref = mtot.a == -INFINITY ? 0.0 : mtot.a, href = mtot.b == -INFINITY ? 0.0 : mtot.b;
+    Trip sum = Sum3::id();
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) {
+      const double w = exp(lw[j] - mref);
+      const double w0 = exp(l[j] - href + ldv[j]), w1 = exp(l[j + 1] - href + ldv[j]);
+      sum.a += w;
+      sum.b = fma(w, w, sum.b);
+      sum.c += (w0 > 0 ? w0 * l[j] : 0.0) + (w1 > 0 ? w1 * l[j + 1] : 0.0);
+      if (a.want_mean) wl[b * kChunk + t * kItems + j] = w;
+    }
+    Trip sex, stot;
+    block_scan<Sum3>(sum, (Trip*)dyn, &sex, &stot);
+    if (t == 0) {
+      double* p = a.part + ((size_t)(b0 + b) * a.nblk + blockIdx.x) * kPart;
+      p[0] = mtot.a;
+      p[1] = mtot.b;
+      p[2] = stot.a;
+      p[3] = stot.b;
+      p[4] = stot.c;
+    }
+  }
+  if (!a.want_mean) return;
+  __syncthreads();
+  // sum w v_c of the chunk: thread (segment, column) adds its kT points in order for the tile's realizations (one load
+  // of v serves them all), then the segments are added in order
+  const int seg = t / kColTile, cc = t % kColTile;
+  for (int c0 = 0; c0 < a.D; c0 += kColTile) {
+    const int c = c0 + cc < a.D ? c0 + cc : a.D - 1;
+    double acc[kRealTile];
+#pragma unroll
+    for (int b = 0; b < kRealTile; ++b) acc[b] = 0.0;
+    for (int i0 = 0; i0 < kT; i0 += kMeanLoads) {  // (kMeanLoads rows in flight: the sums keep their order)
+      double x[kMeanLoads];
+#pragma unroll
+      for (int i = 0; i < kMeanLoads; ++i) {
+        const int p = seg * kT + i0 + i;
+        const long long k = kb + p < a.M ? kb + p : a.M - 1;
+        x[i] = a.v[(size_t)k * a.D + c];
+      }
+#pragma unroll
+      for (int i = 0; i < kMeanLoads; ++i) {
+#pragma unroll
+        for (int b = 0; b < kRealTile; ++b) acc[b] = fma(wl[b * kChunk + seg * kT + i0 + i], x[i], acc[b]);
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < kRealTile; ++b) mp[(seg * kRealTile + b) * kColTile + cc] = acc[b];
+    __syncthreads();
+    if (t < kRealTile * kColTile) {
+      const int b = t / kColTile;
+      double tot = 0.0;
+      for (int g = 0; g < kSeg; ++g) tot += mp[(g * kRealTile + b) * kColTile + cc];
+      if (b < nb && c0 + cc < a.D) a.mpart[((size_t)(b0 + b) * a.nblk + blockIdx.x) * a.D + c0 + cc] = tot;
+    }
+    __syncthreads();
+  }
+}
+
+// workgroup b: out[b] = {ln Z, H, ESS, mean_0 ..}: the chunks' sums in chunk order, each rescaled to the largest chunk
+__global__ void __launch_bounds__(kT) me_finish(RArgs a) {
+  __shared__ Pair2 lds[2 * kT];
+  __shared__ double res[3];
+  const int t = threadIdx.x;
+  const double* part = a.part + (size_t)blockIdx.x * a.nblk * kPart;
+  Pair2 mx = Max2::id();
+  for (int c = t; c < a.nblk; c += kT) mx = Max2::op(mx, Pair2{part[(size_t)c * kPart], part[(size_t)c * kPart + 1]});
+  Pair2 mex, mtot;
+  block_scan<Max2>(mx, lds, &mex, &mtot);
+  const double ms = mtot.a, hs = mtot.b;
+  const int nq = 3 + (a.want_mean ? a.D : 0);
+  double* out = a.out + (size_t)blockIdx.x * (3 + a.D);
+  for (int q0 = 0; q0 < nq; q0 += kT) {
+    const int q = q0 + t;
+    double acc = 0.0;
+    if (q < nq) {
+      const double* mcol = a.want_mean ? a.mpart + (size_t)blockIdx.x * a.nblk * a.D + (q >= 3 ? q - 3 : 0) : nullptr;
+      const int mi = q == 2 ? 1 : 0;
+      const double top = q == 2 ? hs : ms;
+      const double* xs = q < 3 ? part + 2 + q : mcol;  // the chunks' sums of this quantity, xd apart
+      const size_t xd = q < 3 ? kPart : (size_t)a.D;
+      for (int c0 = 0; c0 < a.nblk; c0 += kFinLoads) {  // (kFinLoads chunks in flight, added in chunk order)
+        double m[kFinLoads], x[kFinLoads];
+#pragma unroll
+        for (int i = 0; i < kFinLoads; ++i) {
+          const size_t c = (size_t)(c0 + i < a.nblk ? c0 + i : a.nblk - 1);
+          m[i] = part[c * kPart + mi];
+          x[i] = xs[c * xd];
+        }
+#pragma unroll
+        for (int i = 0; i < kFinLoads; ++i) {
+          const double sc = m[i] == -INFINITY || c0 + i >= a.nblk ? 0.0 : exp(q == 1 ? 2.0 * (m[i] - top) : m[i] - top);
+          acc = fma(sc, x[i], acc);
+        }
+      }
+    }
+    if (q < 3) res[q] = acc;
+    __syncthreads();
+    const double lz = ms + log(res[0]);
+    if (q == 0) out[0] = lz;
+    if (q == 1) out[2] = res[0] * res[0] / res[1];
+    if (q == 2) out[1] = exp(hs - lz) * res[2] - lz;
+    if (q >= 3 && q < nq) out[q] = acc / res[0];
+  }
+}
+
+// the per-point fields of one realization through the scans above
+struct FRealVol {
+  typedef SumD Op;
+  const int* n;
+  double *step, *logvol;
+  uint64_t seed, seq;
+  int jitter;
+  __device__ double term(long long k) const {
+    const double s = real_step(jitter, seed, seq, k, n[k]);
+    step[k] = s;
+    return s;
+  }
+  __device__ void put(long long k, double incl, double) const { logvol[k] = incl; }
+};
+struct FRealLogz {
+  typedef Lse Op;
+  const double *lae, *rwt, *logvol, *step;
+  double *logwt, *logz;
+  __device__ LsePair term(long long k) const {
+    const double v0 = k > 0 ? logvol[k - 1] : 0.0, s = step[k];
+    const double lh = lae[k] + (v0 + log(-expm1(s)) + kLnHalf);
+    const double lw = lh + (rwt ? rwt[k] : 0.0);
+    logwt[k] = lw;
+    return LsePair{lw, 1.0};
+  }
+  __device__ void put(long long k, LsePair incl, LsePair) const { logz[k] = incl.m + log(incl.s); }
+};
+
+// logrwt: NaN and +inf are refused (-inf is a weight of 0)
+int check_logrwt(dh_ctx* ctx, const char* what, const double* rwt, long long M) {
+  if (!rwt) return DH_OK;
+  for (long long k = 0; k < M; ++k)
+    if (!(rwt[k] < INFINITY)) return fail(ctx, DH_ERR_VALUE, "%s: logrwt[%lld] = %g (NaN and +inf are not weights)", what, k, rwt[k]);
+  return DH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int jitter, const double* logrwt_or_null,
+                      int want_mean, double* logz, double* h, double* ess, double* mean) {
+  DH_CHECK_CTX(ctx);
+  if (need_merged(ctx)) return DH_ERR_ARG;
+  const dh_merged& m = ctx->merged;
+  if (nreal < 1 || nreal > kRealMax || (jitter != 0 && jitter != 1) || (!jitter && nreal != 1) || first < 0 ||
+      first > INT64_MAX - nreal || !logz || (!!want_mean != !!mean))
+    return fail(ctx, DH_ERR_ARG,
+                "merged_realize: nreal %d (1 to %d; 1 with jitter = 0), jitter %d (0 or 1), first %lld (>= 0), logz, and "
+                "want_mean with mean", nreal, kRealMax, jitter, (long long)first);
+  int rc = check_logrwt(ctx, "merged_realize", logrwt_or_null, m.M);
+  if (rc) return rc;
+  const size_t M = (size_t)m.M, D = (size_t)m.ndim, nblk = blocks_for(M, kChunk);
+  const size_t tile = (size_t)(nreal < kRealLaunch ? nreal : kRealLaunch), W = 3 + D;
+  arena_reset(ctx);
+  rc = arena_reserve(ctx, (M * 2 + tile * nblk * (1 + kPart + (want_mean ? D : 0)) + (size_t)nreal * W) * 8 + 16 * 256);
+  if (rc) return rc;
+  RArgs a;
+  a.M = m.M;
+  a.D = m.ndim;
+  a.nblk = (int)nblk;
+  a.jitter = jitter;
+  a.want_mean = want_mean ? 1 : 0;
+  a.seed = seed;
+  a.logl = m.logl;
+  a.v = m.v;
+  a.n = m.n;
+  double* lae = (double*)arena_get(ctx, M * 8);
+  a.rwt = logrwt_or_null ? arena_up(ctx, logrwt_or_null, M) : nullptr;
+  a.sums = (double*)arena_get(ctx, tile * nblk * 8);
+  a.part = (double*)arena_get(ctx, tile * nblk * kPart * 8);
+  a.mpart = want_mean ? (double*)arena_get(ctx, tile * nblk * D * 8) : nullptr;
+  double* d_out = (double*)arena_get(ctx, (size_t)nreal * W * 8);
+  if (!lae || (logrwt_or_null && !a.rwt) || !a.sums || !a.part || (want_mean && !a.mpart) || !d_out) return DH_ERR_NOMEM;
+  a.lae = lae;
+  hipStream_t st = ctx->stream;
+  const size_t lds = (size_t)(2 * kT * 3 + (want_mean ? kRealTile * kChunk + kSeg * kRealTile * kColTile : 0)) * 8;
+  if (!lds_limit(ctx, me_integrate, lds)) return DH_ERR_HIP;
+  hipLaunchKernelGGL(me_lae, dim3(blocks_for(M, kT)), dim3(kT), 0, st, m.M, m.logl, lae);
+  for (int r0 = 0; r0 < nreal; r0 += kRealLaunch) {
+    a.nreal = nreal - r0 < kRealLaunch ? nreal - r0 : kRealLaunch;
+    a.first = (long long)first + r0;
+    a.out = d_out + (size_t)r0 * W;
+    const dim3 grid((unsigned)nblk, blocks_for((size_t)a.nreal, kRealTile));
+    hipLaunchKernelGGL(me_step_sums, grid, dim3(kT), 0, st, a);
+    hipLaunchKernelGGL(me_step_carry, dim3(a.nreal), dim3(kT), 0, st, a);
+    hipLaunchKernelGGL(me_integrate, grid, dim3(kT), lds, st, a);
+    hipLaunchKernelGGL(me_finish, dim3(a.nreal), dim3(kT), 0, st, a);
+  }
+  if (!hip_ok(ctx, hipGetLastError(), "realize launch")) return DH_ERR_HIP;
+  std::vector<double> host((size_t)nreal * W);
+  if (!down(ctx, host.data(), (const double*)d_out, host.size())) return DH_ERR_HIP;
+  rc = dh_sync(ctx);
+  if (rc) return rc;
+  for (size_t b = 0; b < (size_t)nreal; ++b) {
+    logz[b] = host[b * W];
+    if (h) h[b] = host[b * W + 1];
+    if (ess) ess[b] = host[b * W + 2];
+    if (mean)
+      for (size_t c = 0; c < D; ++c) mean[b * D + c] = host[b * W + 3 + c];
+  }
+  return DH_OK;
+}
+
+int dh_merged_realization(dh_ctx* ctx, uint64_t seed, int64_t real, int jitter, const double* logrwt_or_null, int field,
+                          int64_t first, int64_t count, double* out) {
+  DH_CHECK_CTX(ctx);
+  if (need_merged(ctx)) return DH_ERR_ARG;
+  const dh_merged& m = ctx->merged;
+  if (real < 0 || (jitter != 0 && jitter != 1) ||
+      (field != DH_MERGED_LOGVOL && field != DH_MERGED_LOGWT && field != DH_MERGED_LOGZ))
+    return fail(ctx, DH_ERR_ARG, "merged_realization: real %lld (>= 0), jitter %d (0 or 1), field %d (LOGVOL, LOGWT or LOGZ)",
+                (long long)real, jitter, field);
+  if (first < 0 || count < 0 || first > m.M || count > m.M - first || (count && !out))
+    return fail(ctx, DH_ERR_ARG, "merged_realization: [%lld, %lld + %lld) of %lld points", (long long)first, (long long)first,
+                (long long)count, m.M);
+  int rc = check_logrwt(ctx, "merged_realization", logrwt_or_null, m.M);
+  if (rc) return rc;
+  if (!count) return DH_OK;
+  const size_t M = (size_t)m.M, nblk = blocks_for(M, kChunk);
+  arena_reset(ctx);
+  rc = arena_reserve(ctx, M * 6 * 8 + (nblk + 1) * sizeof(LsePair) + 16 * 256);
+  if (rc) return rc;
+  double* lae = (double*)arena_get(ctx, M * 8);
+  const double* rwt = logrwt_or_null ? arena_up(ctx, logrwt_or_null, M) : nullptr;
+  double* step = (double*)arena_get(ctx, M * 8);
+  double* logvol = (double*)arena_get(ctx, M * 8);
+  double* logwt = (double*)arena_get(ctx, M * 8);
+  double* logz = (double*)arena_get(ctx, M * 8);
+  void* part = arena_get(ctx, (nblk + 1) * sizeof(LsePair));
+  if (!lae || (logrwt_or_null && !rwt) || !step || !logvol || !logwt || !logz || !part) return DH_ERR_NOMEM;
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(me_lae, dim3(blocks_for(M, kT)), dim3(kT), 0, st, m.M, m.logl, lae);
+  if (!run_scan(ctx, FRealVol{m.n, step, logvol, seed, (uint64_t)real, jitter}, m.M, part)) return DH_ERR_HIP;
+  if (field != DH_MERGED_LOGVOL &&
+      !run_scan(ctx, FRealLogz{lae, rwt, logvol, step, logwt, logz}, m.M, part))
+    return DH_ERR_HIP;
+  const double* src = field == DH_MERGED_LOGVOL ? logvol : field == DH_MERGED_LOGWT ? logwt : logz;
+  if (!down(ctx, out, src + first, (size_t)count)) return DH_ERR_HIP;
+  return dh_sync(ctx);
+}
+
+}  // extern "C"

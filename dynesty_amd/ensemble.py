@@ -13,6 +13,7 @@ is asked for them.
 """
 import numpy as np
 
+from .errors import Errors, realization_host, realize_host
 from .marginals import Marginals
 
 RECORD_FIELDS = ("run", "logz", "logzerr", "niter", "ncall", "h")
@@ -202,13 +203,26 @@ def combine_logz(table):
     return float(lz[ok].mean()), se, n
 
 
-class MergedRun(dict, Marginals):
+class MergedRun(dict, Marginals, Errors):
     """Result of `merge_static_runs`: the fields of the reference's merged
     `Results` (utils.merge_runs) that are defined for an ensemble of static
     runs, with attribute access.  quantile / histogram / histogram2d /
     corner_data (marginals.Marginals) are NumPy here; the device's merged run
-    (_lib.DeviceMergedRun) offers the same four computed where it lives."""
+    (_lib.DeviceMergedRun) offers the same four computed where it lives.
+    logz_realizations / logz_error / jitter_run / realization / reweight
+    (errors.Errors) likewise: the same function of (seed, realization) here
+    in NumPy as there on the device."""
     __getattr__ = dict.get
+
+    def _err_logl(self):
+        return np.asarray(self["logl"], dtype=np.float64)
+
+    def _err_realize(self, seed, first, nreal, jitter, logrwt, means):
+        return realize_host(self["logl"], self["samples_n"], self.get("samples"), seed, first, nreal, jitter,
+                            logrwt, means)
+
+    def _err_field(self, seed, real, jitter, logrwt, field, first, count):
+        return realization_host(self["logl"], self["samples_n"], seed, real, jitter, logrwt, field, first, count)
 
     def importance_weights(self):
         """Normalised posterior weights exp(logwt - logz[-1])."""

@@ -695,6 +695,34 @@ int dh_merged_hist1d(dh_ctx* ctx, int ncol, const int32_t* cols_or_null, int nbi
 int dh_merged_hist2d(dh_ctx* ctx, int npair, const int32_t* pairs, int nbx, int nby, const double* xedges,
                      const double* yedges, int weighted, double* out);
 
+/* ---- statistical errors of the merged run ------------------------------------------------
+ * Realizations of the prior-volume sequence -- utils.jitter_run (utils.py:1317-1408) -- and reweighting --
+ * utils.reweight_run (utils.py:1663-1708) -- where the merged run lives.  Realization r >= 0 is a global index: point
+ * k's volume shrinks by t_k = u_k^(1 / n_k), n_k the SAMPLES_N field and u_k = uniform_double(w_2k, w_2k+1) in (0, 1]
+ * of the words of subsequence r of the Philox4x32-10 stream keyed by `seed` (rocrand's stream model and transform).
+ * For a merged run, whose live count never drops by more than 1 per point, that is the distribution of the
+ * reference's exact form and of approx=True alike; the stream is not NumPy's.  A realization is a function of
+ * (seed, r) alone: bit-identical alone, in a batch of any size, at any position.  jitter = 0 takes the expected
+ * volumes instead, the merged run's own steps -log1p(1 / n_k).  logrwt_or_null: M values on the host added to ln w
+ * (ln of the new over the old target); -inf is a weight of 0.  The integrals are utils.compute_integrals'
+ * (utils.py:1411-1467), every sum in a fixed order.
+ * DH_ERR_ARG (nothing was touched): no merged run, jitter outside {0, 1}, and what each call names below.
+ * DH_ERR_VALUE: a NaN or +inf in logrwt.  The merged run stays in place after either.
+ *
+ * Realizations first .. first + nreal - 1 at once.  logz: nreal values of ln Z; h (or NULL): the information
+ * sum(w0 l0 + w1 l1) - ln Z (the two trapezoid halves, WITHOUT logrwt, as the reference); ess (or NULL):
+ * (sum w)^2 / sum w^2; mean (want_mean = 1: nreal x ndim, else NULL with want_mean = 0): sum w v / sum w.
+ * DH_ERR_ARG: nreal outside [1, 65536], nreal != 1 with jitter = 0, first < 0, logz NULL, want_mean or mean without
+ * the other. */
+int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int jitter, const double* logrwt_or_null,
+                      int want_mean, double* logz, double* h, double* ess, double* mean);
+/* `count` points from point `first` on of one per-point field of realization `real`: DH_MERGED_LOGVOL (ln X),
+ * DH_MERGED_LOGWT or DH_MERGED_LOGZ (cumulative).  The last LOGZ equals dh_merged_realize's ln Z of that realization
+ * to rounding (the same terms, summed as the merge's own scan sums them).  DH_ERR_ARG: real < 0, another field, a
+ * slice outside [0, M). */
+int dh_merged_realization(dh_ctx* ctx, uint64_t seed, int64_t real, int jitter, const double* logrwt_or_null, int field,
+                          int64_t first, int64_t count, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -685,6 +685,42 @@ def gen_merge_marginals(out, merge_npz):
     print("wrote", out, len(g), "arrays")
 
 
+def gen_merge_errors(out, merge_npz):
+    """Statistical errors of the merged run merge.npz already holds (tests/test_merge_errors_cpu.py,
+    tests/test_gpu_merge_errors.py): a Results of its ref/* arrays; the last logz of utils.jitter_run(res,
+    default_rng(i)) for i < 2000 (exact form) and of jitter_run(res, default_rng(10000 + i), approx=True), the last
+    information of the first 200 of each, and utils.reweight_run(res, logp_new) for
+    logp_new = logl + 0.3 default_rng(3).standard_normal(M): its logwt, logz and information arrays.
+
+    The information: both functions compute it (compute_integrals' fourth result) and hand it to results_substitute
+    under the key 'h', which a Results does not have, so their results still carry the INPUT run's information.  What is
+    recorded here is the value they computed: utils.compute_integrals on the result's own logvol (and reweight)."""
+    from dynesty import utils as dyu
+    m = np.load(merge_npz)
+    res = dyu.Results({k: m["ref/" + k] for k in ("samples_u", "samples_id", "samples_it", "logl", "samples", "samples_n",
+                                                  "logvol", "logwt", "logz", "logzerr", "information", "ncall")})
+    nreal, ninfo = 2000, 200
+    g = {}
+    for name, first, approx in (("exact", 0, False), ("approx", 10000, True)):
+        lz, h = np.empty(nreal), np.empty(ninfo)
+        for i in range(nreal):
+            r = dyu.jitter_run(res, rstate=np.random.default_rng(first + i), approx=approx)
+            lz[i] = r.logz[-1]
+            if i < ninfo:
+                assert np.array_equal(r.information, res.information)  # (the dropped 'h', see above)
+                h[i] = dyu.compute_integrals(logl=np.asarray(res.logl), logvol=np.asarray(r.logvol))[3][-1]
+        g[f"jitter/{name}/logz"], g[f"jitter/{name}/information"] = lz, h
+    logl = np.asarray(res.logl)
+    g["reweight/logp_new"] = logl + 0.3 * np.random.default_rng(3).standard_normal(len(logl))
+    rw = dyu.reweight_run(res, g["reweight/logp_new"])
+    for k in ("logwt", "logz"):
+        g["reweight/" + k] = np.asarray(getattr(rw, k))
+    g["reweight/information"] = dyu.compute_integrals(logl=logl, logvol=np.asarray(res.logvol),
+                                                      reweight=g["reweight/logp_new"] - logl)[3]
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(g), "arrays")
+
+
 def _ell_hp_one(key):
     import ell_hp_ref
     return key, ell_hp_ref.case_record(key)
@@ -763,5 +799,7 @@ if __name__ == "__main__":
         gen_merge_device(os.path.join(gdir, "merge_device.npz"), os.path.join(gdir, "merge.npz"))
     if "merge_marginals" in which:  # not in the default list; reads merge.npz, which stays as it is
         gen_merge_marginals(os.path.join(gdir, "merge_marginals.npz"), os.path.join(gdir, "merge.npz"))
+    if "merge_errors" in which:  # not in the default list; reads merge.npz, which stays as it is
+        gen_merge_errors(os.path.join(gdir, "merge_errors.npz"), os.path.join(gdir, "merge.npz"))
     if "livesets" in which:  # not in the default list: two partial reference runs (minutes)
         gen_livesets(os.path.join(gdir, "livesets.npz"))
