@@ -764,10 +764,55 @@ def gen_friends_hp(out):
     print("wrote", out, len(ukeys), "update cases,", len(wkeys), "membership cases,", len(g), "arrays")
 
 
+def _proposal_hp_one(key):
+    import proposal_hp_ref
+    if key.startswith("chain/"):
+        return key, proposal_hp_ref.chain_record(key)
+    if key.startswith("slice/"):
+        return key, proposal_hp_ref.slice_record(key)
+    return key, proposal_hp_ref.step_record(key)
+
+
+def gen_proposal_hp(out):
+    """High-precision results (mpmath, 50 digits; np.longdouble) of the proposal geometry on the seeded cases of
+    tests/proposal_cases.py (tests/test_proposal_hp_cpu.py, tests/test_gpu_proposal_hp.py): ur^(1/n) / |z| of every
+    one-step walker and of every draw inside an ellipsoid, the constructed generator states, and the end points,
+    accumulated bounds and counts of the rwalk chains and of the rslice / slice cases.  Nothing of the reference
+    project is involved: the reference here is tests/proposal_hp_ref.py.  Refuses to write a one-step case with an
+    undecidable walker or a chain or slice case above the 2 % cap.  Half a minute on 16 processors."""
+    import multiprocessing
+    import proposal_hp_ref
+    skeys, ekeys, ckeys = proposal_hp_ref.all_keys()
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        records = dict(pool.imap_unordered(_proposal_hp_one, ckeys + skeys + ekeys, chunksize=1))
+    for k in skeys + ekeys:
+        assert records[k]["undecidable"] == 0, f"{k}: {records[k]['undecidable']} undecidable walkers: choose other inputs"
+    for k in ekeys:
+        print(k, "constructed in at most", records[k]["tries"], "tries")
+    for k in ckeys:
+        if k.startswith("slice/"):
+            proposal_hp_ref.check_slice_caps(records[k], k)
+            print(k, "undecidable", int(records[k]["undecidable"].sum()), "smallest margin %.3g" % records[k]["margin"],
+                  "calls", int(records[k]["ncalls"].sum()), "expansions", int(records[k]["n_expand"].sum()),
+                  "contractions", int(records[k]["n_contract"].sum()))
+            continue
+        proposal_hp_ref.check_caps(records[k], k)
+        print(k, "undecidable", int(records[k]["undecidable"].sum()), "smallest margin %.3g" % records[k]["margin"],
+              "accepts", int(records[k]["accept"].sum()), "rejects", int(records[k]["reject"].sum()))
+    g = proposal_hp_ref.pack_fixture(records)
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(skeys), "one-step sets,", len(ekeys), "constructed sets,", len(ckeys), "chains,", len(g), "arrays")
+
+
 if __name__ == "__main__":
     gdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(gdir, exist_ok=True)
     which = sys.argv[1:] or ["bounding", "proposals", "rng", "runs", "friends", "wide", "nsloop"]
+    if "proposal_hp" in which:  # not in the default list; needs no reference project (tests/proposal_hp_ref.py)
+        gen_proposal_hp(os.path.join(gdir, "proposal_hp.npz"))
+        which = [w for w in which if w != "proposal_hp"]
+        if not which:
+            sys.exit(0)
     if "friends_hp" in which:  # not in the default list; needs no reference project (tests/friends_hp_ref.py)
         gen_friends_hp(os.path.join(gdir, "friends_hp.npz"))
         which = [w for w in which if w != "friends_hp"]
