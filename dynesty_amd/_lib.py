@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .errors import FIELDS as REAL_FIELDS, Errors
+from .errors import FIELDS as REAL_FIELDS, MAX_BOOT, Errors
 from .marginals import Marginals
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -136,6 +136,8 @@ SIGNATURES = {
     "dh_merged_hist2d": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "dh_merged_realize": (_i, [_vp, _u64, C.c_int64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "dh_merged_realization": (_i, [_vp, _u64, C.c_int64, _i, _vp, _i, C.c_int64, C.c_int64, _vp]),
+    "dh_merged_bootstrap": (_i, [_vp, _u64, C.c_int64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dh_merged_bootstrap_run": (_i, [_vp, _u64, C.c_int64, _i, _vp, _i, C.c_int64, C.c_int64, _vp, _vp]),
     "dh_set_rwalk_items": (_i, [_vp, _i, C.c_longlong]),
     "dh_slice_batch_philox": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _dbl, _dbl, _i, _i, _u64, _u64, _u64,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -259,6 +261,9 @@ MERGED_FIELDS = dict(logl=(0, np.float64, False), logvol=(1, np.float64, False),
                      samples_run=(9, np.int32, False), samples_seq=(10, np.int32, False),
                      samples_n=(11, np.int32, False), final=(12, np.int32, False), samples_id=(13, np.int32, False),
                      samples_it=(14, np.int32, False), ncall=(15, np.int32, False))
+# dh_merged_bootstrap_run: result name -> (DH_MERGED_* code, dtype)
+BOOT_RUN_FIELDS = dict(idx=(16, np.int64), samples_n=(11, np.int32), logvol=(1, np.float64), logwt=(2, np.float64),
+                       logz=(3, np.float64))
 SUMMARY_FIELDS = ("niter", "logz", "logzerr", "h", "ess", "ncall")
 
 
@@ -268,7 +273,8 @@ class DeviceMergedRun(dict, Marginals, Errors):
     ess, ncall (sum over the points; 0 without per-point bookkeeping).  quantile / histogram / histogram2d /
     corner_data (marginals.Marginals) are computed on the device too: dh_merged_quantile, _hist1d, _hist2d; so are
     logz_realizations / logz_error / jitter_run / realization / reweight (errors.Errors): dh_merged_realize,
-    dh_merged_realization."""
+    dh_merged_realization; and the strand bootstrap's bootstrap_realizations / resample_run / simulate_run /
+    logz_error_sampling / logz_error_total: dh_merged_bootstrap, dh_merged_bootstrap_run (a merge with id / it / nc)."""
 
     def __init__(self, ctx, summary, ndim, have_pt):
         super().__init__()
@@ -412,6 +418,47 @@ class DeviceMergedRun(dict, Marginals, Errors):
         out = np.empty(count)
         ctx._check_merge(ctx.lib.dh_merged_realization(ctx.handle, seed, int(real), int(jitter), _ptr(logrwt),
                                                        MERGED_FIELDS[field][0], first, count, _ptr(out)))
+        return out
+
+    def _err_mult(self, mult, nboot):
+        if not self.have_pt:
+            raise ValueError("the strand bootstrap needs the points' bookkeeping: the merge was not given id / it / nc")
+        if mult is None:
+            return None
+        mult = np.ascontiguousarray(mult)
+        if mult.ndim != 1 or mult.dtype.kind not in "iu" or len(mult) != int(self.field("samples_n", 0, 1)[0]):
+            raise ValueError("mult: one integer per strand (run * nlive + slot)")
+        if int(nboot) != 1:
+            raise ValueError("mult: given multiplicities are one bootstrap (nboot = 1)")
+        if (mult < 0).any() or (mult >= 1 << 31).any():
+            raise ValueError("mult: multiplicities are non-negative 32-bit integers")
+        return mult.astype(np.int32)
+
+    def _err_bootstrap(self, seed, first, nboot, jitter, mult, means):
+        ctx = self._live()
+        seed, nboot, mult = self._err_seed(seed), int(nboot), self._err_mult(mult, nboot)
+        if not 1 <= nboot <= MAX_BOOT or not 0 <= int(first) < (1 << 63) - nboot:
+            raise ValueError(f"nboot {nboot} outside [1, {MAX_BOOT}], or first {first} not a bootstrap index")
+        lz, h, ess, npts = np.empty(nboot), np.empty(nboot), np.empty(nboot), np.empty(nboot, dtype=np.int64)
+        mean = np.empty((nboot, self.ndim)) if means else None
+        ctx._check_merge(ctx.lib.dh_merged_bootstrap(ctx.handle, seed, int(first), nboot, int(jitter), _ptr(mult),
+                                                     int(means), _ptr(lz), _ptr(h), _ptr(ess), _ptr(mean), _ptr(npts)))
+        return lz, h, ess, mean, npts
+
+    def _err_bootstrap_run(self, seed, boot, jitter, mult):
+        ctx = self._live()
+        seed, mult = self._err_seed(seed), self._err_mult(mult, 1)
+        if not 0 <= int(boot) < (1 << 63) - 1:
+            raise ValueError("boot: a non-negative bootstrap index")
+        npts = np.zeros(1, dtype=np.int64)
+        out = {}
+        for k, (code, dtype) in BOOT_RUN_FIELDS.items():  # (the first call sizes the fetches)
+            if not out:
+                ctx._check_merge(ctx.lib.dh_merged_bootstrap_run(ctx.handle, seed, int(boot), int(jitter), _ptr(mult), code,
+                                                                 0, 0, None, _ptr(npts)))
+            out[k] = np.empty(int(npts[0]), dtype=dtype)
+            ctx._check_merge(ctx.lib.dh_merged_bootstrap_run(ctx.handle, seed, int(boot), int(jitter), _ptr(mult), code,
+                                                             0, int(npts[0]), _ptr(out[k]), None))
         return out
 
     def to_merged_run(self):

@@ -61,6 +61,11 @@ struct dh_merged {
   int *run = nullptr, *seq = nullptr, *id = nullptr, *it = nullptr, *nc = nullptr, *n = nullptr, *fin = nullptr;
   long long* idx = nullptr;  // indices of the last dh_merged_resample (an allocation of its own, grow-only)
   long long idx_cap = 0, idx_n = 0;
+  // the strand bootstrap's tie structure (an allocation of its own, built by the first dh_merged_bootstrap*): the final
+  // points that share their ln L with a neighbour, in merged order, and per point how many of them come before it
+  int* tie_ep = nullptr;   // [tie_n] merged indices
+  int* tie_idx = nullptr;  // [M + 1]
+  int tie_n = -1;          // -1: not built
 };
 
 struct dh_ctx {

@@ -622,6 +622,8 @@ int merge_core(dh_ctx* ctx, int problem, int R, int N, int D, long long stride, 
       (void)hipFree(mbase);
     } else {
       m.idx = nullptr;
+      m.tie_idx = m.tie_ep = nullptr;
+      m.tie_n = -1;
       ctx->merged = m;
     }
     return rc;
@@ -710,6 +712,7 @@ void dh::kept_free(dh_ctx* ctx) {
 void dh::merged_free(dh_ctx* ctx) {
   if (ctx->merged.base) (void)hipFree(ctx->merged.base);
   if (ctx->merged.idx) (void)hipFree(ctx->merged.idx);
+  if (ctx->merged.tie_idx) (void)hipFree(ctx->merged.tie_idx);  // (tie_ep lies in the same allocation)
   ctx->merged = dh_merged();
 }
 
@@ -1490,6 +1493,7 @@ struct RArgs {
   uint64_t seed;
   const double *logl, *lae, *rwt, *v;  // rwt: null without logrwt
   const int* n;
+  const int* map;  // me_integrate<true> (the strand bootstrap): point k reads logl and v at map[k]; n and lae are per k
   double *sums, *part, *mpart, *out;  // [nreal][nblk], [nreal][nblk][kPart], [nreal][nblk][D], [nreal][3 + D]
 };
 
@@ -1542,6 +1546,8 @@ __global__ void __launch_bounds__(kT) me_step_carry(RArgs a) {
 }
 
 // dynamic LDS: the scans' 2 kT Trip; with means kRealTile x kChunk weights and kSeg x kRealTile x kColTile partial sums
+// kMap: logl and the rows of v are read through a.map (the unmapped instantiation is the code it was before the map)
+template <bool kMap>
 __global__ void __launch_bounds__(kT) me_integrate(RArgs a) {
   extern __shared__ double dyn[];
   double* wl = dyn + 2 * kT * 3;
@@ -1553,13 +1559,13 @@ __global__ void __launch_bounds__(kT) me_integrate(RArgs a) {
   load_counts(a, k0, n);
   {
     const long long km = k0 > 0 ? (k0 - 1 < a.M ? k0 - 1 : a.M - 1) : 0;
-    const double lm = a.logl[km];
+    const double lm = a.logl[kMap ? (long long)a.map[km] : km];
     l[0] = k0 > 0 ? lm : -1.e300;
   }
 #pragma unroll
   for (int j = 0; j < kItems; ++j) {
     const long long k = k0 + j < a.M ? k0 + j : a.M - 1;
-    l[j + 1] = a.logl[k];
+    l[j + 1] = a.logl[kMap ? (long long)a.map[k] : k];
     lae[j] = a.lae[k];
     rw[j] = 0.0;
   }
@@ -1630,7 +1636,7 @@ __global__ void __launch_bounds__(kT) me_integrate(RArgs a) {
       for (int i = 0; i < kMeanLoads; ++i) {
         const int p = seg * kT + i0 + i;
         const long long k = kb + p < a.M ? kb + p : a.M - 1;
-        x[i] = a.v[(size_t)k * a.D + c];
+        x[i] = a.v[(size_t)(kMap ? (long long)a.map[k] : k) * a.D + c];
       }
 #pragma unroll
       for (int i = 0; i < kMeanLoads; ++i) {
@@ -1765,6 +1771,7 @@ int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int 
   a.logl = m.logl;
   a.v = m.v;
   a.n = m.n;
+  a.map = nullptr;
   double* lae = (double*)arena_get(ctx, M * 8);
   a.rwt = logrwt_or_null ? arena_up(ctx, logrwt_or_null, M) : nullptr;
   a.sums = (double*)arena_get(ctx, tile * nblk * 8);
@@ -1775,7 +1782,7 @@ int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int 
   a.lae = lae;
   hipStream_t st = ctx->stream;
   const size_t lds = (size_t)(2 * kT * 3 + (want_mean ? kRealTile * kChunk + kSeg * kRealTile * kColTile : 0)) * 8;
-  if (!lds_limit(ctx, me_integrate, lds)) return DH_ERR_HIP;
+  if (!lds_limit(ctx, me_integrate<false>, lds)) return DH_ERR_HIP;
   hipLaunchKernelGGL(me_lae, dim3(blocks_for(M, kT)), dim3(kT), 0, st, m.M, m.logl, lae);
   for (int r0 = 0; r0 < nreal; r0 += kRealLaunch) {
     a.nreal = nreal - r0 < kRealLaunch ? nreal - r0 : kRealLaunch;
@@ -1784,7 +1791,7 @@ int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int 
     const dim3 grid((unsigned)nblk, blocks_for((size_t)a.nreal, kRealTile));
     hipLaunchKernelGGL(me_step_sums, grid, dim3(kT), 0, st, a);
     hipLaunchKernelGGL(me_step_carry, dim3(a.nreal), dim3(kT), 0, st, a);
-    hipLaunchKernelGGL(me_integrate, grid, dim3(kT), lds, st, a);
+    hipLaunchKernelGGL(me_integrate<false>, grid, dim3(kT), lds, st, a);
     hipLaunchKernelGGL(me_finish, dim3(a.nreal), dim3(kT), 0, st, a);
   }
   if (!hip_ok(ctx, hipGetLastError(), "realize launch")) return DH_ERR_HIP;
@@ -1837,6 +1844,407 @@ int dh_merged_realization(dh_ctx* ctx, uint64_t seed, int64_t real, int jitter, 
     return DH_ERR_HIP;
   const double* src = field == DH_MERGED_LOGVOL ? logvol : field == DH_MERGED_LOGWT ? logwt : logz;
   if (!down(ctx, out, src + first, (size_t)count)) return DH_ERR_HIP;
+  return dh_sync(ctx);
+}
+
+}  // extern "C"
+
+// ---- the strand bootstrap of the merged run (utils.resample_run, utils.py:1495-1660) ---------
+//
+// A strand is a (run, live slot) pair, its key run * nlive + slot.  Bootstrap b draws S = runs * nlive strands from
+// subsequence 2^63 + b of the stream (mb_draw: an integer histogram, exact in any order), one scan over the merged
+// points of (m_k, final ? m_k : 0) gives every point's offset in the resampled run, the exclusive sum E of the final
+// points' multiplicities and the totals M' and T, and mb_expand, a thread per expanded position, finds its merged point
+// by a search of the offsets and its live count by the reference's rule: T - E (- the copy's index for a final point)
+// where the point is alone at its ln L, and in a group of equal ln L, g positions long,
+//   n'(i) = T - E(behind the group) + sum over the group's final points with m > 0 of int((g - 1 - i) / (g / m)) + 1
+// (float64, as written).  The group's final points are read from a list built once per merged run (FTie).  The
+// integrals are section 3.8.2's kernels over (n', lae', logl[src], v[src]) with realization index b.
+namespace {
+
+constexpr int kBootMax = 65536;  // bootstraps per call
+
+struct Pair2L {
+  long long a, b;
+};
+struct SumL2 {
+  typedef Pair2L T;
+  __device__ static T id() { return T{0, 0}; }
+  __device__ static T op(T x, T y) { return T{x.a + y.a, x.b + y.b}; }
+};
+
+__device__ __forceinline__ bool tied_point(const double* logl, long long M, long long k) {
+  const double l = logl[k];
+  return (k > 0 && logl[k - 1] == l) || (k + 1 < M && logl[k + 1] == l);
+}
+
+// the final points that share their ln L with a neighbour: tie_ep in merged order, tie_idx[k] = how many lie before k
+struct FTie {
+  typedef SumI Op;
+  const double* logl;
+  const int* fin;
+  int *tie_idx, *tie_ep;
+  long long M;
+  __device__ int term(long long k) const { return fin[k] && tied_point(logl, M, k) ? 1 : 0; }
+  __device__ void put(long long k, int incl, int excl) const {
+    tie_idx[k] = excl;
+    if (incl != excl) tie_ep[excl] = (int)k;
+    if (k == M - 1) tie_idx[M] = incl;
+  }
+};
+
+__global__ void __launch_bounds__(kT) mb_draw(int S, uint64_t seed, uint64_t seq, int* __restrict__ mult) {
+  const int j = blockIdx.x * kT + threadIdx.x;
+  if (j >= S) return;
+  uint32_t w[4];
+  philox4x32_10(seed, seq, (uint64_t)j >> 1, w);  // draw j: words 2j and 2j + 1
+  const bool odd = j & 1;
+  const unsigned long long x = (unsigned long long)(odd ? w[2] : w[0]) | ((unsigned long long)(odd ? w[3] : w[1]) << 32);
+  atomicAdd(&mult[__umul64hi(x, (unsigned long long)S)], 1);  // the high 64 bits of x S: in [0, S)
+}
+
+// offsets, E and the totals {M', T, a slot outside [0, nlive) was seen}
+struct FBoot {
+  typedef SumL2 Op;
+  const int *run, *id, *fin, *mult;
+  int N;
+  long long M;
+  int *off, *E;
+  long long* tot;
+  __device__ Pair2L term(long long k) const {
+    const int s = id[k];
+    if (s < 0 || s >= N) {
+      tot[2] = 1;
+      return Pair2L{0, 0};
+    }
+    const long long m = mult[(long long)run[k] * N + s];
+    return Pair2L{m, fin[k] ? m : 0};
+  }
+  __device__ void put(long long k, Pair2L incl, Pair2L excl) const {
+    off[k] = (int)excl.a;  // (meaningful below 2^31: the call stops at the totals otherwise)
+    E[k] = (int)excl.b;
+    if (k == M - 1) {
+      tot[0] = incl.a;
+      tot[1] = incl.b;
+    }
+  }
+};
+
+struct XArgs {
+  long long M, Mx, T;  // merged points, expanded positions, sum of the multiplicities
+  int N;
+  const double* logl;
+  const int *run, *id, *fin, *mult, *off, *E, *tie_idx, *tie_ep;
+  int *src, *n;
+};
+
+// first k in [0, M) with logl[k] >= l (upper = false) or > l (upper = true)
+__device__ __forceinline__ long long bound_logl(const double* logl, long long M, double l, bool upper) {
+  long long lo = 0, hi = M;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (upper ? logl[mid] <= l : logl[mid] < l)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(kT) mb_expand(XArgs a) {
+  const long long p = (long long)blockIdx.x * kT + threadIdx.x;
+  if (p >= a.Mx) return;
+  long long lo = 0, hi = a.M;  // the last k with off[k] <= p (points never drawn share their successor's offset)
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (a.off[mid] <= p)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  const long long k = lo - 1;
+  long long n;
+  if (!tied_point(a.logl, a.M, k)) {
+    n = a.T - a.E[k] - (a.fin[k] ? p - a.off[k] : 0);
+  } else {
+    const double l = a.logl[k];
+    const long long ga = bound_logl(a.logl, a.M, l, false), gb = bound_logl(a.logl, a.M, l, true);
+    const long long p0 = a.off[ga], g = (gb < a.M ? a.off[gb] : a.Mx) - p0, i = p - p0;
+    n = a.T - (gb < a.M ? a.E[gb] : a.T);
+    const int e1 = a.tie_idx[gb];
+    for (int e = a.tie_idx[ga]; e < e1; ++e) {
+      const int kk = a.tie_ep[e];
+      const int m = a.mult[(long long)a.run[kk] * a.N + a.id[kk]];
+      if (m > 0) n += (long long)((double)(g - 1 - i) / ((double)g / (double)m)) + 1;
+    }
+  }
+  a.src[p] = (int)k;
+  a.n[p] = (int)n;
+}
+
+__global__ void __launch_bounds__(kT) mb_lae(long long Mx, const double* __restrict__ logl, const int* __restrict__ src,
+                                             double* __restrict__ lae) {
+  const long long p = (long long)blockIdx.x * kT + threadIdx.x;
+  if (p >= Mx) return;
+  lae[p] = logaddexp_np(logl[src[p]], p > 0 ? logl[src[p - 1]] : -1.e300);
+}
+
+__global__ void __launch_bounds__(kT) mb_widen(long long n, const int* __restrict__ in, long long* __restrict__ out) {
+  const long long p = (long long)blockIdx.x * kT + threadIdx.x;
+  if (p < n) out[p] = in[p];
+}
+
+// the arena of one bootstrap call, carved for `cap` expanded positions
+struct BootBuf {
+  size_t cap = 0;
+  int *mult = nullptr, *off = nullptr, *E = nullptr, *src = nullptr, *n = nullptr;
+  long long* tot = nullptr;
+  void* part = nullptr;
+  double *lae = nullptr, *sums = nullptr, *partr = nullptr, *mpart = nullptr, *out = nullptr;  // batch
+  double *step = nullptr, *logvol = nullptr, *logwt = nullptr, *logz = nullptr;                // per-point fields
+  long long* wide = nullptr;
+};
+
+int boot_carve(dh_ctx* ctx, BootBuf& b, size_t cap, bool fields, bool want_mean) {
+  const dh_merged& m = ctx->merged;
+  const size_t M = (size_t)m.M, S = (size_t)m.runs * m.nlive, D = (size_t)m.ndim;
+  const size_t nblk = blocks_for(M > cap ? M : cap, kChunk), nbx = blocks_for(cap, kChunk);
+  const size_t bytes = S * 4 + M * 8 + 64 + (nblk + 1) * sizeof(LsePair) + cap * 16 +
+                       (fields ? cap * 40 : (nbx * (1 + kPart + (want_mean ? D : 0)) + 3 + D) * 8) + 24 * 256;
+  arena_reset(ctx);
+  const int rc = arena_reserve(ctx, bytes);
+  if (rc) return rc;
+  b = BootBuf();
+  b.cap = cap;
+  b.mult = (int*)arena_get(ctx, S * 4);
+  b.off = (int*)arena_get(ctx, M * 4);
+  b.E = (int*)arena_get(ctx, M * 4);
+  b.tot = (long long*)arena_get(ctx, 64);
+  b.part = arena_get(ctx, (nblk + 1) * sizeof(LsePair));
+  b.src = (int*)arena_get(ctx, cap * 4);
+  b.n = (int*)arena_get(ctx, cap * 4);
+  b.lae = (double*)arena_get(ctx, cap * 8);
+  bool ok = b.mult && b.off && b.E && b.tot && b.part && b.src && b.n && b.lae;
+  if (fields) {
+    b.step = (double*)arena_get(ctx, cap * 8);
+    b.logvol = (double*)arena_get(ctx, cap * 8);
+    b.logwt = (double*)arena_get(ctx, cap * 8);
+    b.logz = (double*)arena_get(ctx, cap * 8);
+    b.wide = (long long*)arena_get(ctx, cap * 8);
+    ok = ok && b.step && b.logvol && b.logwt && b.logz && b.wide;
+  } else {
+    b.sums = (double*)arena_get(ctx, nbx * 8);
+    b.partr = (double*)arena_get(ctx, nbx * kPart * 8);
+    b.mpart = want_mean ? (double*)arena_get(ctx, nbx * D * 8) : nullptr;
+    b.out = (double*)arena_get(ctx, (3 + D) * 8);
+    ok = ok && b.sums && b.partr && (!want_mean || b.mpart) && b.out;
+  }
+  return ok ? DH_OK : DH_ERR_NOMEM;
+}
+
+// the tie structure of the merged run, built by the first bootstrap call on it
+int boot_ties(dh_ctx* ctx) {
+  dh_merged& m = ctx->merged;
+  if (m.tie_n >= 0) return DH_OK;
+  const size_t M = (size_t)m.M, S = (size_t)m.runs * m.nlive;
+  arena_reset(ctx);
+  int rc = arena_reserve(ctx, (blocks_for(M, kChunk) + 1) * sizeof(LsePair) + 1024);
+  if (rc) return rc;
+  void* part = arena_get(ctx, (blocks_for(M, kChunk) + 1) * sizeof(LsePair));
+  if (!part) return DH_ERR_NOMEM;
+  int* buf = nullptr;
+  (void)hipSetDevice(ctx->device);
+  if (hipMalloc((void**)&buf, (M + 1 + S) * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, DH_ERR_NOMEM, "merged_bootstrap: %zu bytes for the tie structure", (M + 1 + S) * 4);
+  }
+  int tn = 0;
+  if (!run_scan(ctx, FTie{m.logl, m.fin, buf, buf + M + 1, m.M}, m.M, part) ||
+      !hip_ok(ctx, hipMemcpyAsync(&tn, buf + M, 4, hipMemcpyDeviceToHost, ctx->stream), "D2H ties"))
+    rc = DH_ERR_HIP;
+  const int rs = dh_sync(ctx);
+  if (rc || rs) {
+    (void)hipFree(buf);
+    return rc ? rc : rs;
+  }
+  m.tie_idx = buf;
+  m.tie_ep = buf + M + 1;
+  m.tie_n = tn;
+  return DH_OK;
+}
+
+int boot_need(dh_ctx* ctx, const char* what, int jitter, const int32_t* mult, int nboot) {
+  if (need_merged(ctx)) return DH_ERR_ARG;
+  const dh_merged& m = ctx->merged;
+  if (!m.have_pt) return fail(ctx, DH_ERR_ARG, "%s: the merge was not given id / it / nc (the strands' slots)", what);
+  if (jitter != 0 && jitter != 1) return fail(ctx, DH_ERR_ARG, "%s: jitter %d (0 or 1)", what, jitter);
+  if (mult) {
+    if (nboot != 1) return fail(ctx, DH_ERR_ARG, "%s: given multiplicities are one bootstrap (nboot %d)", what, nboot);
+    const long long S = (long long)m.runs * m.nlive;
+    for (long long u = 0; u < S; ++u)
+      if (mult[u] < 0) return fail(ctx, DH_ERR_ARG, "%s: mult[%lld] = %d is negative", what, u, mult[u]);
+  }
+  return DH_OK;
+}
+
+// Multiplicities, offsets and totals of bootstrap `boot`, then src and n' (growing the arena where M' exceeds the carve).
+// *Mx: M'.  Returns with the stream drained up to the scan.
+int boot_expand(dh_ctx* ctx, BootBuf& b, const char* what, uint64_t seed, long long boot, const int32_t* mult, bool fields,
+                bool want_mean, long long* Mx) {
+  const dh_merged& m = ctx->merged;
+  const size_t S = (size_t)m.runs * m.nlive;
+  hipStream_t st = ctx->stream;
+  if (mult) {
+    if (!hip_ok(ctx, hipMemcpyAsync(b.mult, mult, S * 4, hipMemcpyHostToDevice, st), "H2D mult")) return DH_ERR_HIP;
+  } else {
+    if (!hip_ok(ctx, hipMemsetAsync(b.mult, 0, S * 4, st), "memset")) return DH_ERR_HIP;
+    hipLaunchKernelGGL(mb_draw, dim3(blocks_for(S, kT)), dim3(kT), 0, st, (int)S, seed, ((uint64_t)1 << 63) + (uint64_t)boot, b.mult);
+  }
+  long long tot[3];
+  if (!hip_ok(ctx, hipMemsetAsync(b.tot, 0, 24, st), "memset") ||
+      !run_scan(ctx, FBoot{m.run, m.id, m.fin, b.mult, m.nlive, m.M, b.off, b.E, b.tot}, m.M, b.part) ||
+      !hip_ok(ctx, hipMemcpyAsync(tot, b.tot, 24, hipMemcpyDeviceToHost, st), "D2H totals"))
+    return DH_ERR_HIP;
+  int rc = dh_sync(ctx);
+  if (rc) return rc;
+  if (tot[2]) return fail(ctx, DH_ERR_ARG, "%s: a point's slot lies outside [0, %d): these ids do not name strands", what, m.nlive);
+  if (tot[0] < 1 || tot[0] >= (1ll << 31))
+    return fail(ctx, DH_ERR_ARG, "%s: the resampled run has %lld points (1 to 2^31 - 1)", what, tot[0]);
+  *Mx = tot[0];
+  if ((size_t)tot[0] > b.cap) {  // the arena grows: the multiplicities travel through the host, the scan runs again
+    std::vector<int32_t> keep(S);
+    if (!mult) {
+      if (!down(ctx, keep.data(), (const int32_t*)b.mult, S)) return DH_ERR_HIP;
+      rc = dh_sync(ctx);
+      if (rc) return rc;
+    }
+    rc = boot_carve(ctx, b, (size_t)tot[0] + (size_t)tot[0] / 4 + kChunk, fields, want_mean);
+    if (rc) return rc;
+    if (!hip_ok(ctx, hipMemcpyAsync(b.mult, mult ? mult : keep.data(), S * 4, hipMemcpyHostToDevice, st), "H2D mult") ||
+        !hip_ok(ctx, hipMemsetAsync(b.tot, 0, 24, st), "memset") ||
+        !run_scan(ctx, FBoot{m.run, m.id, m.fin, b.mult, m.nlive, m.M, b.off, b.E, b.tot}, m.M, b.part))
+      return DH_ERR_HIP;
+    rc = dh_sync(ctx);  // (`keep` leaves scope)
+    if (rc) return rc;
+  }
+  XArgs x{m.M, tot[0], tot[1], m.nlive, m.logl, m.run, m.id, m.fin, b.mult, b.off, b.E, m.tie_idx, m.tie_ep, b.src, b.n};
+  const unsigned gx = blocks_for((size_t)tot[0], kT);
+  hipLaunchKernelGGL(mb_expand, dim3(gx), dim3(kT), 0, st, x);
+  hipLaunchKernelGGL(mb_lae, dim3(gx), dim3(kT), 0, st, tot[0], m.logl, (const int*)b.src, b.lae);
+  return hip_ok(ctx, hipGetLastError(), "bootstrap launch") ? DH_OK : DH_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dh_merged_bootstrap(dh_ctx* ctx, uint64_t seed, int64_t first, int nboot, int jitter, const int32_t* mult_or_null,
+                        int want_mean, double* logz, double* h, double* ess, double* mean, int64_t* npoints) {
+  DH_CHECK_CTX(ctx);
+  int rc = boot_need(ctx, "merged_bootstrap", jitter, mult_or_null, nboot);
+  if (rc) return rc;
+  if (nboot < 1 || nboot > kBootMax || first < 0 || first > INT64_MAX - nboot || !logz || (!!want_mean != !!mean))
+    return fail(ctx, DH_ERR_ARG, "merged_bootstrap: nboot %d (1 to %d), first %lld (>= 0), logz, and want_mean with mean", nboot,
+                kBootMax, (long long)first);
+  rc = boot_ties(ctx);
+  if (rc) return rc;
+  const dh_merged& m = ctx->merged;
+  const size_t M = (size_t)m.M, D = (size_t)m.ndim, W = 3 + D;
+  BootBuf b;
+  rc = boot_carve(ctx, b, M + M / 4 + kChunk, false, want_mean != 0);
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  const size_t lds = (size_t)(2 * kT * 3 + (want_mean ? kRealTile * kChunk + kSeg * kRealTile * kColTile : 0)) * 8;
+  if (!lds_limit(ctx, me_integrate<true>, lds)) return DH_ERR_HIP;
+  std::vector<double> host((size_t)nboot * W);
+  for (int i = 0; i < nboot; ++i) {
+    long long Mx = 0;
+    rc = boot_expand(ctx, b, "merged_bootstrap", seed, (long long)first + i, mult_or_null, false, want_mean != 0, &Mx);
+    if (rc) return rc;
+    if (npoints) npoints[i] = Mx;
+    RArgs a;
+    a.M = Mx;
+    a.first = (long long)first + i;
+    a.D = m.ndim;
+    a.nblk = (int)blocks_for((size_t)Mx, kChunk);
+    a.nreal = 1;
+    a.jitter = jitter;
+    a.want_mean = want_mean ? 1 : 0;
+    a.seed = seed;
+    a.logl = m.logl;
+    a.lae = b.lae;
+    a.rwt = nullptr;
+    a.v = m.v;
+    a.n = b.n;
+    a.map = b.src;
+    a.sums = b.sums;
+    a.part = b.partr;
+    a.mpart = b.mpart;
+    a.out = b.out;
+    const dim3 grid((unsigned)a.nblk, 1);
+    hipLaunchKernelGGL(me_step_sums, grid, dim3(kT), 0, st, a);
+    hipLaunchKernelGGL(me_step_carry, dim3(1), dim3(kT), 0, st, a);
+    hipLaunchKernelGGL(me_integrate<true>, grid, dim3(kT), lds, st, a);
+    hipLaunchKernelGGL(me_finish, dim3(1), dim3(kT), 0, st, a);
+    // (the row leaves before the next bootstrap's totals are waited for: one synchronisation per bootstrap)
+    if (!hip_ok(ctx, hipGetLastError(), "bootstrap launch") || !down(ctx, host.data() + (size_t)i * W, (const double*)b.out, W))
+      return DH_ERR_HIP;
+  }
+  rc = dh_sync(ctx);
+  if (rc) return rc;
+  for (size_t i = 0; i < (size_t)nboot; ++i) {
+    logz[i] = host[i * W];
+    if (h) h[i] = host[i * W + 1];
+    if (ess) ess[i] = host[i * W + 2];
+    if (mean)
+      for (size_t c = 0; c < D; ++c) mean[i * D + c] = host[i * W + 3 + c];
+  }
+  return DH_OK;
+}
+
+int dh_merged_bootstrap_run(dh_ctx* ctx, uint64_t seed, int64_t boot, int jitter, const int32_t* mult_or_null, int field,
+                            int64_t first, int64_t count, void* out, int64_t* npoints) {
+  DH_CHECK_CTX(ctx);
+  int rc = boot_need(ctx, "merged_bootstrap_run", jitter, mult_or_null, 1);
+  if (rc) return rc;
+  if (boot < 0 || first < 0 || count < 0 || (count && !out) ||
+      (field != DH_MERGED_LOGVOL && field != DH_MERGED_LOGWT && field != DH_MERGED_LOGZ && field != DH_MERGED_SAMPLES_N &&
+       field != DH_MERGED_SRC))
+    return fail(ctx, DH_ERR_ARG, "merged_bootstrap_run: boot %lld (>= 0), field %d (LOGVOL, LOGWT, LOGZ, SAMPLES_N or SRC), "
+                "first %lld, count %lld", (long long)boot, field, (long long)first, (long long)count);
+  rc = boot_ties(ctx);
+  if (rc) return rc;
+  const dh_merged& m = ctx->merged;
+  const size_t M = (size_t)m.M;
+  BootBuf b;
+  rc = boot_carve(ctx, b, M + M / 4 + kChunk, true, false);
+  if (rc) return rc;
+  long long Mx = 0;
+  rc = boot_expand(ctx, b, "merged_bootstrap_run", seed, (long long)boot, mult_or_null, true, false, &Mx);
+  if (rc) return rc;
+  if (first > Mx || count > Mx - first) {
+    (void)dh_sync(ctx);
+    return fail(ctx, DH_ERR_ARG, "merged_bootstrap_run: [%lld, %lld + %lld) of %lld points", (long long)first, (long long)first,
+                (long long)count, Mx);
+  }
+  if (npoints) *npoints = Mx;
+  if (!count) return dh_sync(ctx);
+  hipStream_t st = ctx->stream;
+  const size_t f = (size_t)first, c = (size_t)count;
+  bool ok = true;
+  if (field == DH_MERGED_SAMPLES_N) {
+    ok = down(ctx, (int*)out, (const int*)b.n + f, c);
+  } else if (field == DH_MERGED_SRC) {
+    hipLaunchKernelGGL(mb_widen, dim3(blocks_for((size_t)Mx, kT)), dim3(kT), 0, st, Mx, (const int*)b.src, b.wide);
+    ok = hip_ok(ctx, hipGetLastError(), "bootstrap launch") && down(ctx, (long long*)out, (const long long*)b.wide + f, c);
+  } else {
+    if (!run_scan(ctx, FRealVol{b.n, b.step, b.logvol, seed, (uint64_t)boot, jitter}, Mx, b.part)) return DH_ERR_HIP;
+    if (field != DH_MERGED_LOGVOL && !run_scan(ctx, FRealLogz{b.lae, nullptr, b.logvol, b.step, b.logwt, b.logz}, Mx, b.part))
+      return DH_ERR_HIP;
+    const double* src = field == DH_MERGED_LOGVOL ? b.logvol : field == DH_MERGED_LOGWT ? b.logwt : b.logz;
+    ok = down(ctx, (double*)out, src + f, c);
+  }
+  if (!ok) return DH_ERR_HIP;
   return dh_sync(ctx);
 }
 

@@ -13,7 +13,7 @@ is asked for them.
 """
 import numpy as np
 
-from .errors import Errors, realization_host, realize_host
+from .errors import Errors, bootstrap_host, bootstrap_run_host, realization_host, realize_host
 from .marginals import Marginals
 
 RECORD_FIELDS = ("run", "logz", "logzerr", "niter", "ncall", "h")
@@ -211,7 +211,10 @@ class MergedRun(dict, Marginals, Errors):
     (_lib.DeviceMergedRun) offers the same four computed where it lives.
     logz_realizations / logz_error / jitter_run / realization / reweight
     (errors.Errors) likewise: the same function of (seed, realization) here
-    in NumPy as there on the device."""
+    in NumPy as there on the device; so are the strand bootstrap's
+    bootstrap_realizations / resample_run / simulate_run /
+    logz_error_sampling / logz_error_total, which need samples_run and
+    samples_id."""
     __getattr__ = dict.get
 
     def _err_logl(self):
@@ -223,6 +226,26 @@ class MergedRun(dict, Marginals, Errors):
 
     def _err_field(self, seed, real, jitter, logrwt, field, first, count):
         return realization_host(self["logl"], self["samples_n"], seed, real, jitter, logrwt, field, first, count)
+
+    def _err_strands(self):
+        """(strand key run * nlive + slot, final-live flag, number of strands) of every point."""
+        if self.get("samples_run") is None or self.get("samples_id") is None:
+            raise ValueError("the strand bootstrap needs the points' bookkeeping: merge with dead_id / dead_it / "
+                             "dead_nc / live_it (samples_run and samples_id)")
+        n = np.asarray(self["samples_n"], dtype=np.int64)
+        run = np.asarray(self["samples_run"], dtype=np.int64)
+        S, R = int(n[0]), int(run.max()) + 1
+        final = np.concatenate([n[:-1] - n[1:], [1]]).astype(bool)  # the live count drops after a final point
+        return run * (S // R) + np.asarray(self["samples_id"], dtype=np.int64), final, S
+
+    def _err_bootstrap(self, seed, first, nboot, jitter, mult, means):
+        strand, final, S = self._err_strands()
+        return bootstrap_host(self["logl"], strand, final, S, self.get("samples"), seed, first, nboot, jitter, mult,
+                              means)
+
+    def _err_bootstrap_run(self, seed, boot, jitter, mult):
+        strand, final, S = self._err_strands()
+        return bootstrap_run_host(self["logl"], strand, final, S, seed, boot, jitter, mult)
 
     def importance_weights(self):
         """Normalised posterior weights exp(logwt - logz[-1])."""

@@ -16,11 +16,20 @@
 
 The ratios of consecutive uniform order statistics are independent Beta(j, 1) (Renyi / Malmquist), and a merged run's
 live count never drops by more than 1 per point, so the reference's exact form and its approx=True are this same
-distribution; the stream is not NumPy's Generator.beta.  u_k = 1 is a step of 0 and a weight of 0."""
+distribution; the stream is not NumPy's Generator.beta.  u_k = 1 is a step of 0 and a weight of 0.
+
+The strand bootstrap (utils.resample_run, utils.py:1495-1660) is on the same surface: a
+strand is a (run, live slot) pair, bootstrap b draws as many strands as there are from subsequence 2^63 + b
+(`strand_multiplicities`), the resampled run is every merged point repeated as often as its strand was drawn, in merged
+order, with the reference's live counts (`expand_host`), and its integrals are realization b of that sequence
+(jitter=False: utils.resample_run; jitter=True: a jitter_run after it, the documentation's simulate_run)."""
 import numpy as np
 
 MAX_REAL = 65536  # realizations per call (dh_merged_realize's cap)
+MAX_BOOT = 65536  # bootstraps per call (dh_merged_bootstrap's cap)
+BOOT_SEQ = 1 << 63  # bootstrap b draws its strands from subsequence BOOT_SEQ + b: realization indices stay below it
 FIELDS = ("logvol", "logwt", "logz")
+BOOT_FIELDS = ("idx", "samples_n", "logvol", "logwt", "logz")
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
 _MASK, _S32 = np.uint64(0xFFFFFFFF), np.uint64(32)
@@ -145,10 +154,119 @@ def realization_host(logl, samples_n, seed, real, jitter=True, logrwt=None, fiel
     return np.ascontiguousarray(out[first:first + count])
 
 
+def strand_multiplicities(seed, boot, S):
+    """m_u of bootstrap `boot`: the histogram of S strand draws.  Draw j takes words 2j and 2j + 1 of subsequence
+    2^63 + boot of the stream keyed by `seed`; with x = w0 | w1 << 32 the strand is the high 64 bits of x S (no
+    rejection: a bias below S 2^-64)."""
+    S, boot = int(S), int(boot)
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed: an unsigned 64-bit integer")
+    if not 0 <= boot < BOOT_SEQ:
+        raise ValueError("boot: a non-negative bootstrap index")
+    if not 1 <= S < 1 << 31:
+        raise ValueError(f"{S} strands")
+    w = philox_blocks(np.uint64(int(seed)), np.uint64(BOOT_SEQ + boot), np.arange((S + 1) // 2, dtype=np.uint64))
+    w = w.reshape(-1, 2)[:S].astype(np.uint64)  # draw j: (w0, w1)
+    lo, hi, s = w[:, 0], w[:, 1], np.uint64(S)
+    u = (hi * s + ((lo * s) >> _S32)) >> _S32  # the high 64 bits of (lo | hi << 32) S, S < 2^31
+    return np.bincount(u.astype(np.int64), minlength=S).astype(np.int64)
+
+
+def expand_host(logl, strand, final, mult):
+    """The resampled run of the multiplicities `mult` (per strand): merged point k repeated m_k = mult[strand[k]]
+    times in merged order (one valid result of the reference's unstable argsort; the stable one) and the live count
+    of every expanded position (utils.resample_run, utils.py:1601-1622).  With T = sum of m over the strands, E the
+    exclusive prefix over merged order of (final ? m_k : 0): a point alone at its ln L has n' = T - E for all its
+    copies, a final one T - E - c for copy c.  A group of equal ln L = L holding g expanded positions i = 0 .. g - 1:
+
+        n'(i) = T - (sum of m over final points with ln L <= L)
+                + sum over the group's final points with m > 0 of int((g - 1 - i) / (g / m)) + 1
+
+    the division in float64 as written.  Returns (idx, n'), int64."""
+    logl = np.asarray(logl, dtype=np.float64)
+    M = len(logl)
+    final = np.asarray(final).astype(bool)
+    mk = np.asarray(mult, dtype=np.int64)[np.asarray(strand, dtype=np.int64)]
+    off = np.concatenate([[0], np.cumsum(mk)])
+    mf = np.where(final, mk, 0)
+    E = np.concatenate([[0], np.cumsum(mf)])
+    T, Mx = int(E[-1]), int(off[-1])
+    if not 0 < Mx < 1 << 31:
+        raise ValueError(f"the resampled run has {Mx} points (1 to 2^31 - 1)")
+    idx = np.repeat(np.arange(M, dtype=np.int64), mk)
+    n = T - E[idx] - np.where(final[idx], np.arange(Mx, dtype=np.int64) - off[idx], 0)
+    head = np.flatnonzero(np.concatenate([[True], logl[1:] != logl[:-1], [True]]))
+    tied = np.flatnonzero(np.diff(head) >= 2)  # the groups of two or more merged points
+    for a, b in zip(head[tied], head[tied + 1]):
+        p0, g = int(off[a]), int(off[b] - off[a])
+        if g == 0:
+            continue
+        i = np.arange(g, dtype=np.int64)
+        acc = np.full(g, T - int(E[b]), dtype=np.int64)
+        for e in range(a, b):
+            if final[e] and mk[e] > 0:
+                acc += ((g - 1 - i) / (g / int(mk[e]))).astype(np.int64) + 1
+        n[p0:p0 + g] = acc
+    return idx, n
+
+
+def _check_boot(seed, first, nboot, mult, S):
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed: an unsigned 64-bit integer")
+    if not 1 <= int(nboot) <= MAX_BOOT:
+        raise ValueError(f"nboot {nboot} outside [1, {MAX_BOOT}]")
+    if int(first) < 0 or int(first) + int(nboot) > BOOT_SEQ:
+        raise ValueError("first: a non-negative bootstrap index")
+    if mult is None:
+        return None
+    mult = np.ascontiguousarray(mult)
+    if mult.shape != (S,) or mult.dtype.kind not in "iu":
+        raise ValueError(f"mult: {S} integers, one per strand (run * nlive + slot)")
+    if int(nboot) != 1:
+        raise ValueError("mult: given multiplicities are one bootstrap (nboot = 1)")
+    if (mult < 0).any() or (mult >= 1 << 31).any():
+        raise ValueError("mult: multiplicities are non-negative 32-bit integers")
+    return mult.astype(np.int64)
+
+
+def bootstrap_host(logl, strand, final, S, samples, seed, first, nboot, jitter=False, mult=None, means=False):
+    """dh_merged_bootstrap in NumPy: (logz, information, ess, mean or None, npoints) of the bootstraps
+    first .. first + nboot - 1: the strands' multiplicities (`mult` in their place), the expansion, then realization
+    `b` of the expanded sequence (realize_host: jitter=False is the expected volumes of the resampled run, the
+    reference's utils.resample_run; jitter=True its jitter after the resampling)."""
+    mult = _check_boot(seed, first, nboot, mult, int(S))
+    if means and samples is None:
+        raise ValueError("means: this merged run has no samples")
+    nboot, first = int(nboot), int(first)
+    logl = np.asarray(logl, dtype=np.float64)
+    logz, h, ess, npts = np.empty(nboot), np.empty(nboot), np.empty(nboot), np.empty(nboot, dtype=np.int64)
+    mean = np.empty((nboot, np.shape(samples)[1])) if means else None
+    for b in range(nboot):
+        m = strand_multiplicities(seed, first + b, S) if mult is None else mult
+        idx, n = expand_host(logl, strand, final, m)
+        r = realize_host(logl[idx], n, np.asarray(samples)[idx] if means else None, seed, first + b, 1, bool(jitter),
+                         None, means)
+        logz[b], h[b], ess[b], npts[b] = r[0][0], r[1][0], r[2][0], len(idx)
+        if means:
+            mean[b] = r[3][0]
+    return logz, h, ess, mean, npts
+
+
+def bootstrap_run_host(logl, strand, final, S, seed, boot, jitter=False, mult=None):
+    """dh_merged_bootstrap_run in NumPy: idx, samples_n, logvol, logwt and the cumulative logz of one bootstrap."""
+    mult = _check_boot(seed, boot, 1, mult, int(S))
+    logl = np.asarray(logl, dtype=np.float64)
+    idx, n = expand_host(logl, strand, final, strand_multiplicities(seed, boot, S) if mult is None else mult)
+    logvol, _, lw = _logwt(logl[idx], steps(seed, [int(boot)], n, bool(jitter)), None)
+    return dict(idx=idx, samples_n=n, logvol=logvol[0], logwt=lw[0], logz=np.logaddexp.accumulate(lw[0]))
+
+
 class Errors:
     """The methods both merged runs offer.  A class supplies `niter` (points), `_err_logl()`,
     `_err_realize(seed, first, nreal, jitter, logrwt, means)` -> (logz, information, ess, mean or None) and
-    `_err_field(seed, real, jitter, logrwt, field, first, count)`, which validate their own arguments."""
+    `_err_field(seed, real, jitter, logrwt, field, first, count)`, which validate their own arguments; for the strand
+    bootstrap `_err_bootstrap(seed, first, nboot, jitter, mult, means)` -> (logz, information, ess, mean or None,
+    npoints) and `_err_bootstrap_run(seed, boot, jitter, mult)` -> a dict of BOOT_FIELDS."""
 
     def logz_realizations(self, nreal, seed=0, first=0, logrwt=None, means=False, jitter=True):
         """Realizations first .. first + nreal - 1 of the prior volumes under `seed`: a dict of logz, information and
@@ -188,3 +306,40 @@ class Errors:
             logrwt = new - old
         lz, h, ess, mean = self._err_realize(0, 0, 1, False, logrwt, True)
         return dict(logz=float(lz[0]), information=float(h[0]), ess=float(ess[0]), mean=mean[0])
+
+    def bootstrap_realizations(self, nboot, seed=0, first=0, jitter=False, means=False):
+        """Strand bootstraps first .. first + nboot - 1 under `seed` (the reference's utils.resample_run; with
+        jitter=True followed by its utils.jitter_run, the documentation's simulate_run): a dict of logz, information,
+        ess and npoints (the resampled run's length), nboot each, and with means=True mean (nboot, ndim)."""
+        lz, h, ess, mean, npts = self._err_bootstrap(seed, first, nboot, bool(jitter), None, bool(means))
+        out = dict(logz=lz, information=h, ess=ess, npoints=npts)
+        if means:
+            out["mean"] = mean
+        return out
+
+    def resample_run(self, seed=0, boot=0, mult=None):
+        """utils.resample_run(res, return_idx=True)'s per-point results for bootstrap `boot`: a dict of idx (the
+        merged-run index of every point of the resampled run, the reference's samp_idx in the stable order),
+        samples_n, logvol, logwt and logz.  mult: multiplicities per strand (run * nlive + slot) in place of the
+        drawn ones."""
+        return self._err_bootstrap_run(seed, boot, False, mult)
+
+    def simulate_run(self, seed=0, boot=0):
+        """resample_run followed by jitter_run: position p of bootstrap `boot` takes the uniform of point p of
+        realization `boot`."""
+        return self._err_bootstrap_run(seed, boot, True, None)
+
+    def _boot_error(self, nboot, seed, jitter, what):
+        if int(nboot) < 2:
+            raise ValueError(f"{what}: at least 2 bootstraps")
+        lz = self.bootstrap_realizations(nboot, seed, jitter=jitter)["logz"]
+        return float(lz.mean()), float(lz.std(ddof=1))
+
+    def logz_error_sampling(self, nboot=256, seed=0):
+        """(mean, standard deviation with ddof = 1) of ln Z over `nboot` strand bootstraps: the sampling part of the
+        error (utils.resample_run)."""
+        return self._boot_error(nboot, seed, False, "logz_error_sampling")
+
+    def logz_error_total(self, nboot=256, seed=0):
+        """The same over bootstraps that are jittered too: the total error (simulate_run)."""
+        return self._boot_error(nboot, seed, True, "logz_error_total")

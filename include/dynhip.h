@@ -634,6 +634,9 @@ enum {
   DH_MERGED_IT = 14,
   DH_MERGED_NCALL = 15
 };
+/* Not a field of the merged run (dh_merged_fetch refuses it): for dh_merged_bootstrap_run, the merged-run index of
+ * every point of a resampled run, int64. */
+#define DH_MERGED_SRC 16
 
 /* `runs` static runs of equal nlive merged into one run that stays on the device -- ensemble.merge_static_runs, i.e.
  * the reference's utils.merge_runs for such runs.  Host pointers: niter (runs), dead_logl / dead_id / dead_it / dead_nc
@@ -722,6 +725,28 @@ int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int 
  * slice outside [0, M). */
 int dh_merged_realization(dh_ctx* ctx, uint64_t seed, int64_t real, int jitter, const double* logrwt_or_null, int field,
                           int64_t first, int64_t count, double* out);
+
+/* The strand bootstrap of the merged run (the reference's utils.resample_run, and with
+ * jitter = 1 its jitter_run after it).  A strand is a (run, live slot) pair, its key run * nlive + slot, S = runs *
+ * nlive of them.  Bootstrap b >= 0 draws S strands from subsequence 2^63 + b of the Philox4x32-10 stream keyed by
+ * `seed`: draw j takes words 2j and 2j + 1, the strand is the high 64 bits of (w0 | w1 << 32) S.  The resampled run is
+ * every merged point repeated as often as its strand was drawn, in merged order, M' points; its live counts follow the
+ * reference's rule (ties included), its integrals are dh_merged_realize's over the expanded sequence with realization
+ * index b (jitter = 0: the expected volumes).  Results of bootstraps first .. first + nboot - 1: logz, h, ess, npoints
+ * (M') of nboot each (h, ess, npoints may be NULL), mean [nboot][ndim] with want_mean.  A bootstrap's numbers depend on
+ * (seed, b) alone.  mult_or_null: S host values >= 0 in strand-key order that replace the drawn multiplicities
+ * (nboot = 1; their sum need not be S).
+ * DH_ERR_ARG (the merged run stays): no merged run, a merge without id / it / nc, nboot outside [1, 65536], first < 0,
+ * jitter not 0 or 1, mult with nboot != 1 or a negative entry, M' = 0 or M' >= 2^31, want_mean without mean or the
+ * reverse, no logz. */
+int dh_merged_bootstrap(dh_ctx* ctx, uint64_t seed, int64_t first, int nboot, int jitter, const int32_t* mult_or_null,
+                        int want_mean, double* logz, double* h, double* ess, double* mean, int64_t* npoints);
+/* `count` points from point `first` on of one per-point field of bootstrap `boot`: DH_MERGED_LOGVOL, DH_MERGED_LOGWT,
+ * DH_MERGED_LOGZ (cumulative) as doubles, DH_MERGED_SAMPLES_N as int32, DH_MERGED_SRC as int64.  npoints (may be NULL)
+ * receives M', also with count = 0: the way to size a fetch.  DH_ERR_ARG as above, another field, a slice outside
+ * [0, M'). */
+int dh_merged_bootstrap_run(dh_ctx* ctx, uint64_t seed, int64_t boot, int jitter, const int32_t* mult_or_null, int field,
+                            int64_t first, int64_t count, void* out, int64_t* npoints);
 
 #ifdef __cplusplus
 }

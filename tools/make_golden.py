@@ -721,6 +721,69 @@ def gen_merge_errors(out, merge_npz):
     print("wrote", out, len(g), "arrays")
 
 
+class _RecordingGenerator:
+    """A numpy Generator whose integers() draws are kept (utils.resample_run's strand draws)."""
+
+    def __init__(self, rng):
+        self._rng, self.draws = rng, []
+
+    def integers(self, *a, **kw):
+        d = self._rng.integers(*a, **kw)
+        self.draws.append(np.array(d))
+        return d
+
+    def __getattr__(self, k):
+        return getattr(self._rng, k)
+
+
+def gen_merge_bootstrap(out, merge_npz):
+    """The strand bootstrap (tests/test_merge_bootstrap_cpu.py, tests/test_gpu_merge_bootstrap.py).  For the golden
+    merged run and the cases of tests/bootstrap_cases.py, as a Results whose samples_id is the strand key
+    run * nlive + slot, with samples_batch = 0 and batch_logl_bounds = [(-inf, inf)] (every strand a base strand):
+    utils.resample_run(res, default_rng(i), return_idx=True) for i < 4 -- the strand indices it drew, samples_n,
+    samp_idx, logvol, logwt, logz and the information of utils.compute_integrals on the result's own logvol (the
+    dropped 'h', see gen_merge_errors).  For the golden run the last logz of 2000 such calls with
+    default_rng(20000 + i), and of 2000 calls of the documentation's simulate_run with default_rng(30000 + i): the
+    reference no longer ships that function; it is jitter_run(resample_run(res, rstate), rstate, approx=True), as its
+    documentation describes it."""
+    from dynesty import utils as dyu
+    import bootstrap_cases as bc
+    gm = np.load(merge_npz)
+    g = {}
+    for name in bc.NAMES:
+        m = bc.host_run(name, gm)
+        key, S = bc.strands(m)
+        M = len(key)
+        assert np.array_equal(np.unique(key), np.arange(S))
+        if name == "golden":
+            for k in ("logvol", "logwt", "logz", "samples_n"):
+                np.testing.assert_allclose(m[k], gm["ref/" + k], rtol=0, atol=1e-9)
+        res = dyu.Results(dict(samples_u=m.samples_u, samples_id=key, samples_it=m.samples_it, logl=m.logl,
+                               samples=m.samples, samples_n=m.samples_n, logvol=m.logvol, logwt=m.logwt, logz=m.logz,
+                               logzerr=m.logzerr, information=m.information, ncall=m.ncall, blob=np.zeros(M),
+                               samples_batch=np.zeros(M, dtype=int), batch_logl_bounds=np.array([(-np.inf, np.inf)])))
+        for i in range(bc.NCALLS):
+            rs = _RecordingGenerator(np.random.default_rng(i))
+            r, idx = dyu.resample_run(res, rstate=rs, return_idx=True)
+            assert len(rs.draws) == 1 and rs.draws[0].shape == (S,)
+            p = f"{name}/{i}/"
+            g[p + "draws"] = rs.draws[0].astype(np.int32)
+            g[p + "samples_n"], g[p + "samp_idx"] = np.asarray(r.samples_n, dtype=np.int32), idx.astype(np.int32)
+            g[p + "logvol"], g[p + "logwt"], g[p + "logz"] = (np.asarray(getattr(r, k)) for k in ("logvol", "logwt", "logz"))
+            g[p + "information"] = np.float64(dyu.compute_integrals(logl=np.asarray(r.logl), logvol=np.asarray(r.logvol))[3][-1])
+        if name == "golden":
+            n = 2000
+            g["golden/resample/logz"] = np.array([dyu.resample_run(res, rstate=np.random.default_rng(20000 + i)).logz[-1]
+                                                  for i in range(n)])
+            lz = np.empty(n)
+            for i in range(n):
+                rs = np.random.default_rng(30000 + i)
+                lz[i] = dyu.jitter_run(dyu.resample_run(res, rstate=rs), rstate=rs, approx=True).logz[-1]
+            g["golden/simulate/logz"] = lz
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(g), "arrays,", os.path.getsize(out), "bytes")
+
+
 def _ell_hp_one(key):
     import ell_hp_ref
     return key, ell_hp_ref.case_record(key)
@@ -846,5 +909,7 @@ if __name__ == "__main__":
         gen_merge_marginals(os.path.join(gdir, "merge_marginals.npz"), os.path.join(gdir, "merge.npz"))
     if "merge_errors" in which:  # not in the default list; reads merge.npz, which stays as it is
         gen_merge_errors(os.path.join(gdir, "merge_errors.npz"), os.path.join(gdir, "merge.npz"))
+    if "merge_bootstrap" in which:  # not in the default list; reads merge.npz, which stays as it is
+        gen_merge_bootstrap(os.path.join(gdir, "merge_bootstrap.npz"), os.path.join(gdir, "merge.npz"))
     if "livesets" in which:  # not in the default list: two partial reference runs (minutes)
         gen_livesets(os.path.join(gdir, "livesets.npz"))

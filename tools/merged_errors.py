@@ -9,12 +9,20 @@ kernel trace wants.  Then, alternating the two sides in one process, `--reps` of
   host    what there was before: the download of logl, samples_n and samples (timed apart), then the package's own
           NumPy form (ensemble.MergedRun.logz_realizations) on --host-real realizations, scaled to one; and, where a
           copy of the reference is importable, utils.jitter_run(approx=True) per realization
+With --bootstrap the strand bootstrap too (the synthetic runs then carry slot ids):
+  device  bootstrap_realizations(nboot) for nboot in 1, 64, 256, without and with jitter and means; resample_run()
+  host    the download of logl, samples_run, samples_id, final and samples (timed apart), then the package's NumPy form
+          (ensemble.MergedRun.bootstrap_realizations) on --host-boot bootstraps, scaled to one
+and `bootstrap_over_realization`: one bootstrap without means over one realization of the same merged run, each computed
+alone (nboot = 1 over nreal = 1), which is how a bootstrap is always computed (M' differs between bootstraps);
+`bootstrap_over_batched_realization`: per bootstrap of 64 over per realization of 64, where the realizations share
+their loads in tiles of 4.
 One JSON line at the end.  `f64_fraction_*`: the fp64 vector instructions of a call over the chip's measured rate
 (58.7 TFLOP/s = 29.35e12 v_fma_f64 lanes per second), with the instructions per point and realization
 counted in the kernels' code on the jitter path (me_step_sums 93, me_integrate 287: all v_*_f64 of the unrolled 8-point
 body / 8; with means 32 more, the mean sums' v_fma_f64 per point over a tile of 32 columns).
 
-    python tools/merged_errors.py [--runs 64] [--reps 5] [--host-real 8] [--device-only] [--synthetic]
+    python tools/merged_errors.py [--runs 64] [--reps 5] [--host-real 8] [--device-only] [--synthetic] [--bootstrap]
 """
 import argparse
 import json
@@ -55,6 +63,8 @@ def main():
     ap.add_argument("--device-only", action="store_true")
     ap.add_argument("--synthetic", action="store_true", help="drawn runs of --niter dead points each, no sampling")
     ap.add_argument("--niter", type=int, default=83438)
+    ap.add_argument("--bootstrap", action="store_true", help="time the strand bootstrap too")
+    ap.add_argument("--host-boot", type=int, default=2, help="bootstraps of the NumPy form per repetition")
     a = ap.parse_args()
     import inputs
     from dynesty_amd import _lib, backend, ensemble
@@ -64,7 +74,8 @@ def main():
     if a.synthetic:
         import merge_cases
         args = merge_cases.make(np.random.default_rng(1), [a.niter] * a.runs, a.nlive, prob.ndim)
-        d = ctx.merge_runs(prob, args["niter"], args["dead_logl"], args["live_logl"], args["dead_u"], args["live_u"])
+        pt = {k: args[k] for k in ("dead_id", "dead_it", "dead_nc", "live_it")} if a.bootstrap else {}
+        d = ctx.merge_runs(prob, args["niter"], args["dead_logl"], args["live_logl"], args["dead_u"], args["live_u"], **pt)
         del args
     else:
         d = ensemble.run_ensemble_merged(prob, a.runs, merge='device', nlive=a.nlive, queue_size=a.queue, entropy=(21,))
@@ -77,8 +88,16 @@ def main():
         dev[f"realize_{n}_means"] = lambda n=n: d.logz_realizations(n, seed=1, means=True)
     dev["reweight"] = lambda: d.reweight(logp_new)
     dev["jitter_run"] = lambda: d.jitter_run(seed=1, real=0)
+    if a.bootstrap:
+        for n in (1, 64, 256):
+            dev[f"bootstrap_{n}"] = lambda n=n: d.bootstrap_realizations(n, seed=1)
+            dev[f"bootstrap_{n}_jitter"] = lambda n=n: d.bootstrap_realizations(n, seed=1, jitter=True)
+            dev[f"bootstrap_{n}_means"] = lambda n=n: d.bootstrap_realizations(n, seed=1, means=True)
+            dev[f"bootstrap_{n}_jitter_means"] = lambda n=n: d.bootstrap_realizations(n, seed=1, jitter=True, means=True)
+        dev["resample_run"] = lambda: d.resample_run(seed=1, boot=0)
     t = {f"device_{k}": [] for k in dev}
-    t.update(download=[], host_realize=[], host_realize_means=[], reference_jitter_approx=[])
+    t.update(download=[], host_realize=[], host_realize_means=[], reference_jitter_approx=[], download_bootstrap=[],
+             host_bootstrap=[], host_bootstrap_jitter=[])
     res = {}
     try:
         from dynesty import utils as dyu
@@ -102,6 +121,14 @@ def main():
         t["host_realize"].append(dt / a.host_real)
         dt, res["host_means"] = timed(lambda: host.logz_realizations(a.host_real, seed=1, means=True))
         t["host_realize_means"].append(dt / a.host_real)
+        if a.bootstrap:
+            dt, f = timed(lambda: {k: d.field(k) for k in ("logl", "samples_run", "samples_id", "final", "samples", "samples_n")})
+            t["download_bootstrap"].append(dt)
+            hb = ensemble.MergedRun(niter=M, **{k: v for k, v in f.items() if k != "final"})
+            dt, res["host_boot"] = timed(lambda: hb.bootstrap_realizations(a.host_boot, seed=1))
+            t["host_bootstrap"].append(dt / a.host_boot)
+            dt, _ = timed(lambda: hb.bootstrap_realizations(a.host_boot, seed=1, jitter=True))
+            t["host_bootstrap_jitter"].append(dt / a.host_boot)
         if dyu is not None:
             full = d.to_merged_run()
             r = dyu.Results({k: full[k] for k in ("samples_u", "samples_id", "samples_it", "logl", "samples", "samples_n",
@@ -125,6 +152,19 @@ def main():
             out[f"download_over_device_{n}"] = out["download_s"]["median"] / out[f"device_realize_{n}_s"]["median"]
             out[f"host_route_over_device_{n}"] = (out["download_s"]["median"] + n * out["host_realize_s"]["median"]) / \
                 out[f"device_realize_{n}_s"]["median"]
+    if a.bootstrap:
+        out["bootstrap_over_realization"] = out["device_bootstrap_1_s"]["median"] / out["device_realize_1_s"]["median"]
+        out["bootstrap_jitter_over_realization"] = out["device_bootstrap_1_jitter_s"]["median"] / out["device_realize_1_s"]["median"]
+        out["bootstrap_over_batched_realization"] = out["device_bootstrap_64_s"]["median"] / out["device_realize_64_s"]["median"]
+        bz = res["bootstrap_256"]["logz"]
+        out["bootstrap_logz_mean_sd_256"] = [float(bz.mean()), float(bz.std(ddof=1))]
+        out["bootstrap_npoints_min_max_256"] = [int(res["bootstrap_256"]["npoints"].min()), int(res["bootstrap_256"]["npoints"].max())]
+        if "host_boot" in res:
+            out["host_boot"] = a.host_boot
+            out["logz_max_diff_device_host_bootstrap"] = float(np.max(np.abs(res["bootstrap_64"]["logz"][:a.host_boot] - res["host_boot"]["logz"])))
+            for n in (1, 64, 256):
+                out[f"host_bootstrap_route_over_device_{n}"] = (out["download_bootstrap_s"]["median"] + n * out["host_bootstrap_s"]["median"]) / \
+                    out[f"device_bootstrap_{n}_s"]["median"]
     lz = res["realize_256"]["logz"]
     out["logz_mean_sd_256"] = [float(lz.mean()), float(lz.std(ddof=1))]
     out["summary"] = dict(logz=d.summary["logz"], logzerr=d.summary["logzerr"])
