@@ -138,6 +138,9 @@ SIGNATURES = {
     "dh_merged_realization": (_i, [_vp, _u64, C.c_int64, _i, _vp, _i, C.c_int64, C.c_int64, _vp]),
     "dh_merged_bootstrap": (_i, [_vp, _u64, C.c_int64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "dh_merged_bootstrap_run": (_i, [_vp, _u64, C.c_int64, _i, _vp, _i, C.c_int64, C.c_int64, _vp, _vp]),
+    "dh_merged_kld": (_i, [_vp, _u64, C.c_int64, _i, _i, _vp, _vp, _vp, _vp]),
+    "dh_merged_weight_function": (_i, [_vp, _dbl, _dbl, C.c_int64, _vp, _vp]),
+    "dh_merged_weights": (_i, [_vp, _dbl, _i, C.c_int64, C.c_int64, _vp]),
     "dh_set_rwalk_items": (_i, [_vp, _i, C.c_longlong]),
     "dh_slice_batch_philox": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _dbl, _dbl, _i, _i, _u64, _u64, _u64,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -264,6 +267,7 @@ MERGED_FIELDS = dict(logl=(0, np.float64, False), logvol=(1, np.float64, False),
 # dh_merged_bootstrap_run: result name -> (DH_MERGED_* code, dtype)
 BOOT_RUN_FIELDS = dict(idx=(16, np.int64), samples_n=(11, np.int32), logvol=(1, np.float64), logwt=(2, np.float64),
                        logz=(3, np.float64))
+MERGED_KLD = 17  # DH_MERGED_KLD: the cumulative divergence (dh_merged_realization, dh_merged_bootstrap_run)
 SUMMARY_FIELDS = ("niter", "logz", "logzerr", "h", "ess", "ncall")
 
 
@@ -274,7 +278,9 @@ class DeviceMergedRun(dict, Marginals, Errors):
     corner_data (marginals.Marginals) are computed on the device too: dh_merged_quantile, _hist1d, _hist2d; so are
     logz_realizations / logz_error / jitter_run / realization / reweight (errors.Errors): dh_merged_realize,
     dh_merged_realization; and the strand bootstrap's bootstrap_realizations / resample_run / simulate_run /
-    logz_error_sampling / logz_error_total: dh_merged_bootstrap, dh_merged_bootstrap_run (a merge with id / it / nc)."""
+    logz_error_sampling / logz_error_total: dh_merged_bootstrap, dh_merged_bootstrap_run (a merge with id / it / nc);
+    and kld_realizations / kld_error / weight_function / stopping_function: dh_merged_kld, the KLD field of the two
+    per-point calls, dh_merged_weight_function, dh_merged_weights."""
 
     def __init__(self, ctx, summary, ndim, have_pt):
         super().__init__()
@@ -460,6 +466,72 @@ class DeviceMergedRun(dict, Marginals, Errors):
             ctx._check_merge(ctx.lib.dh_merged_bootstrap_run(ctx.handle, seed, int(boot), int(jitter), _ptr(mult), code,
                                                              0, int(npts[0]), _ptr(out[k]), None))
         return out
+
+    def _err_kld(self, seed, first, n, mode, mult):
+        ctx = self._live()
+        seed, n = self._err_seed(seed), int(n)
+        mult = self._err_mult(mult, n) if mode else None
+        if not 1 <= n <= MAX_BOOT or not 0 <= int(first) < (1 << 63) - n:
+            raise ValueError(f"n {n} outside [1, {MAX_BOOT}], or first {first} not an index")
+        kld, lz, npts = np.empty(n), np.empty(n), np.empty(n, dtype=np.int64)
+        ctx._check_merge(ctx.lib.dh_merged_kld(ctx.handle, seed, int(first), n, int(mode), _ptr(mult), _ptr(kld), _ptr(lz),
+                                               _ptr(npts)))
+        return kld, lz, npts
+
+    def _err_kld_run(self, seed, index, mode, mult, first, count):
+        ctx = self._live()
+        seed, first = self._err_seed(seed), int(first)
+        if not 0 <= int(index) < (1 << 63) - 1 or first < 0 or (count is not None and int(count) < 0):
+            raise ValueError(f"index {index}, first {first}, count {count}: non-negative")
+        if mode == 0:
+            count = self.niter - first if count is None else int(count)
+            if first + count > self.niter:
+                raise ValueError(f"[{first}, {first + count}) of {self.niter} points")
+            out = np.empty(count)
+            ctx._check_merge(ctx.lib.dh_merged_realization(ctx.handle, seed, int(index), 1, None, MERGED_KLD, first, count,
+                                                           _ptr(out)))
+            return out
+        mult = self._err_mult(mult, 1)
+        npts = np.zeros(1, dtype=np.int64)
+        if count is None:  # (a call without a slice sizes the fetch)
+            ctx._check_merge(ctx.lib.dh_merged_bootstrap_run(ctx.handle, seed, int(index), int(mode == 2), _ptr(mult),
+                                                             MERGED_KLD, 0, 0, None, _ptr(npts)))
+            count = int(npts[0]) - first
+            if count < 0:
+                raise ValueError(f"first {first} beyond the {int(npts[0])} points of this bootstrap")
+        out = np.empty(int(count))
+        ctx._check_merge(ctx.lib.dh_merged_bootstrap_run(ctx.handle, seed, int(index), int(mode == 2), _ptr(mult), MERGED_KLD,
+                                                         first, int(count), _ptr(out), None))
+        return out
+
+    def weights(self, pfrac=0.8, which="weight", first=0, count=None):
+        """`count` points from `first` on of 'pweight', 'zweight' or 'weight' of the weight function (dh_merged_weights)."""
+        ctx = self._live()
+        names = ("pweight", "zweight", "weight")
+        if which not in names:
+            raise ValueError(f"which {which!r}: one of {names}")
+        first = int(first)
+        count = self.niter - first if count is None else int(count)
+        if not 0. <= pfrac <= 1. or first < 0 or count < 0 or first + count > self.niter:
+            raise ValueError(f"weights: pfrac {pfrac} in [0, 1], [{first}, {first + count}) of {self.niter} points")
+        out = np.empty(count)
+        ctx._check_merge(ctx.lib.dh_merged_weights(ctx.handle, float(pfrac), names.index(which), first, count, _ptr(out)))
+        return out
+
+    def _err_weights(self, pfrac):
+        return tuple(self.weights(pfrac, w) for w in ("pweight", "zweight", "weight"))
+
+    def _err_weight_function(self, pfrac, maxfrac, pad):
+        ctx = self._live()
+        bounds, idx = np.empty(2), np.empty(2, dtype=np.int64)
+        rc = ctx.lib.dh_merged_weight_function(ctx.handle, pfrac, maxfrac, int(pad), _ptr(bounds), _ptr(idx))
+        if rc == ERR_VALUE:  # (no weight above maxfrac x the largest: the host form's ValueError)
+            raise ValueError(ctx.lib.dh_last_error(ctx.handle).decode())
+        ctx._check_merge(rc)
+        return (float(bounds[0]), float(bounds[1])), (int(idx[0]), int(idx[1]))
+
+    def _err_summary(self):
+        return self.summary["logzerr"], self.summary["ess"]
 
     def to_merged_run(self):
         """Everything downloaded into ensemble.MergedRun (merge_static_runs' field names)."""

@@ -1495,6 +1495,10 @@ struct RArgs {
   const int* n;
   const int* map;  // me_integrate<true> (the strand bootstrap): point k reads logl and v at map[k]; n and lae are per k
   double *sums, *part, *mpart, *out;  // [nreal][nblk], [nreal][nblk][kPart], [nreal][nblk][D], [nreal][3 + D]
+  // the divergence (me_integrate<., true>, me_finish<true>): the merged run's own ln w (read through map) and its last
+  // cumulative ln Z; the chunks' sums of w (ln w - LOGWT) [nreal][nblk].  The result takes the row's first mean slot.
+  const double *lwt0 = nullptr, *lz0 = nullptr;
+  double* kpart = nullptr;
 };
 
 __global__ void __launch_bounds__(kT) me_lae(long long M, const double* __restrict__ logl, double* __restrict__ lae) {
@@ -1547,7 +1551,9 @@ __global__ void __launch_bounds__(kT) me_step_carry(RArgs a) {
 
 // dynamic LDS: the scans' 2 kT Trip; with means kRealTile x kChunk weights and kSeg x kRealTile x kColTile partial sums
 // kMap: logl and the rows of v are read through a.map (the unmapped instantiation is the code it was before the map)
-template <bool kMap>
+// kKld: beside sum w the chunk's sum of w e, e = ln w - LOGWT_src, rescaled as sum w is: me_finish<true> turns the two into
+// the divergence from the merged run without any pass knowing ln Z (the instantiations without it keep their code)
+template <bool kMap, bool kKld>
 __global__ void __launch_bounds__(kT) me_integrate(RArgs a) {
   extern __shared__ double dyn[];
   double* wl = dyn + 2 * kT * 3;
@@ -1568,6 +1574,14 @@ __global__ void __launch_bounds__(kT) me_integrate(RArgs a) {
     l[j + 1] = a.logl[kMap ? (long long)a.map[k] : k];
     lae[j] = a.lae[k];
     rw[j] = 0.0;
+  }
+  double lq[kKld ? kItems : 1];
+  if constexpr (kKld) {
+#pragma unroll
+    for (int j = 0; j < kItems; ++j) {
+      const long long k = k0 + j < a.M ? k0 + j : a.M - 1;
+      lq[j] = a.lwt0[kMap ? (long long)a.map[k] : k];
+    }
   }
   if (a.rwt) {
 #pragma unroll
@@ -1600,9 +1614,11 @@ __global__ void __launch_bounds__(kT) me_integrate(RArgs a) {
     block_scan<Max2>(mx, (Pair2*)dyn, &mex, &mtot);
     const double mref = mtot.a == -INFINITY ? 0.0 : mtot.a, href = mtot.b == -INFINITY ? 0.0 : mtot.b;
     Trip sum = Sum3::id();
+    double sume = 0.0;
 #pragma unroll
     for (int j = 0; j < kItems; ++j) {
       const double w = exp(lw[j] - mref);
+      if constexpr (kKld) sume += w > 0 ? w * (lw[j] - lq[j]) : 0.0;  // (w = 0: nothing, also where e is inf - inf)
       const double w0 = exp(l[j] - href + ldv[j]), w1 = exp(l[j + 1] - href + ldv[j]);
       sum.a += w;
       sum.b = fma(w, w, sum.b);
@@ -1618,6 +1634,11 @@ __global__ void __launch_bounds__(kT) me_integrate(RArgs a) {
       p[2] = stot.a;
       p[3] = stot.b;
       p[4] = stot.c;
+    }
+    if constexpr (kKld) {  // (a scan of its own: one of four doubles in place of Sum3's measured slower)
+      double eex, etot;
+      block_scan<SumD>(sume, dyn, &eex, &etot);
+      if (t == 0) a.kpart[(size_t)(b0 + b) * a.nblk + blockIdx.x] = etot;
     }
   }
   if (!a.want_mean) return;
@@ -1658,6 +1679,8 @@ __global__ void __launch_bounds__(kT) me_integrate(RArgs a) {
 }
 
 // workgroup b: out[b] = {ln Z, H, ESS, mean_0 ..}: the chunks' sums in chunk order, each rescaled to the largest chunk
+// kKld (never with means): out[b][3] = (sum w' e) / (sum w') - (ln Z - LOGZ_{M-1}), the sum of kpart scaled as sum w' is
+template <bool kKld>
 __global__ void __launch_bounds__(kT) me_finish(RArgs a) {
   __shared__ Pair2 lds[2 * kT];
   __shared__ double res[3];
@@ -1668,7 +1691,7 @@ __global__ void __launch_bounds__(kT) me_finish(RArgs a) {
   Pair2 mex, mtot;
   block_scan<Max2>(mx, lds, &mex, &mtot);
   const double ms = mtot.a, hs = mtot.b;
-  const int nq = 3 + (a.want_mean ? a.D : 0);
+  const int nq = kKld ? 4 : 3 + (a.want_mean ? a.D : 0);
   double* out = a.out + (size_t)blockIdx.x * (3 + a.D);
   for (int q0 = 0; q0 < nq; q0 += kT) {
     const int q = q0 + t;
@@ -1678,7 +1701,13 @@ __global__ void __launch_bounds__(kT) me_finish(RArgs a) {
       const int mi = q == 2 ? 1 : 0;
       const double top = q == 2 ? hs : ms;
       const double* xs = q < 3 ? part + 2 + q : mcol;  // the chunks' sums of this quantity, xd apart
-      const size_t xd = q < 3 ? kPart : (size_t)a.D;
+      size_t xd = q < 3 ? kPart : (size_t)a.D;
+      if constexpr (kKld) {
+        if (q == 3) {
+          xs = a.kpart + (size_t)blockIdx.x * a.nblk;
+          xd = 1;
+        }
+      }
       for (int c0 = 0; c0 < a.nblk; c0 += kFinLoads) {  // (kFinLoads chunks in flight, added in chunk order)
         double m[kFinLoads], x[kFinLoads];
 #pragma unroll
@@ -1690,7 +1719,10 @@ __global__ void __launch_bounds__(kT) me_finish(RArgs a) {
 #pragma unroll
         for (int i = 0; i < kFinLoads; ++i) {
           const double sc = m[i] == -INFINITY || c0 + i >= a.nblk ? 0.0 : exp(q == 1 ? 2.0 * (m[i] - top) : m[i] - top);
-          acc = fma(sc, x[i], acc);
+          if constexpr (kKld)
+            acc = sc > 0 ? fma(sc, x[i], acc) : acc;  // (a chunk scaled to 0 adds nothing, also where its sum is inf)
+          else
+            acc = fma(sc, x[i], acc);
         }
       }
     }
@@ -1700,7 +1732,11 @@ __global__ void __launch_bounds__(kT) me_finish(RArgs a) {
     if (q == 0) out[0] = lz;
     if (q == 1) out[2] = res[0] * res[0] / res[1];
     if (q == 2) out[1] = exp(hs - lz) * res[2] - lz;
-    if (q >= 3 && q < nq) out[q] = acc / res[0];
+    if constexpr (kKld) {
+      if (q == 3) out[3] = acc / res[0] - (lz - a.lz0[0]);
+    } else {
+      if (q >= 3 && q < nq) out[q] = acc / res[0];
+    }
   }
 }
 
@@ -1732,6 +1768,22 @@ struct FRealLogz {
   __device__ void put(long long k, LsePair incl, LsePair) const { logz[k] = incl.m + log(incl.s); }
 };
 
+// the cumulative divergence of one realization from the merged run, after FRealLogz: term p =
+// exp(lw_p - Z) ((lw_p - LOGWT_src(p)) - (Z - LOGZ_{M-1})), Z the last cumulative ln Z the scan before wrote
+struct FRealKld {
+  typedef SumD Op;
+  const double *logwt, *logz, *lwt0, *lz0;
+  const int* map;  // null: src(p) = p
+  double* kld;
+  long long M;
+  __device__ double term(long long k) const {
+    const double lz = logz[M - 1], lw = logwt[k];
+    const double p = exp(lw - lz);
+    return p > 0 ? p * ((lw - lwt0[map ? (long long)map[k] : k]) - (lz - lz0[0])) : 0.0;
+  }
+  __device__ void put(long long k, double incl, double) const { kld[k] = incl; }
+};
+
 // logrwt: NaN and +inf are refused (-inf is a weight of 0)
 int check_logrwt(dh_ctx* ctx, const char* what, const double* rwt, long long M) {
   if (!rwt) return DH_OK;
@@ -1740,26 +1792,17 @@ int check_logrwt(dh_ctx* ctx, const char* what, const double* rwt, long long M) 
   return DH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int jitter, const double* logrwt_or_null,
-                      int want_mean, double* logz, double* h, double* ess, double* mean) {
-  DH_CHECK_CTX(ctx);
-  if (need_merged(ctx)) return DH_ERR_ARG;
+// dh_merged_realize after its argument checks; kld (or null): the realizations' divergence from the merged run too
+// (dh_merged_kld), through the instantiation of me_integrate that sums it
+int realize_core(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int jitter, const double* logrwt_or_null, int want_mean,
+                 double* logz, double* h, double* ess, double* mean, double* kld) {
   const dh_merged& m = ctx->merged;
-  if (nreal < 1 || nreal > kRealMax || (jitter != 0 && jitter != 1) || (!jitter && nreal != 1) || first < 0 ||
-      first > INT64_MAX - nreal || !logz || (!!want_mean != !!mean))
-    return fail(ctx, DH_ERR_ARG,
-                "merged_realize: nreal %d (1 to %d; 1 with jitter = 0), jitter %d (0 or 1), first %lld (>= 0), logz, and "
-                "want_mean with mean", nreal, kRealMax, jitter, (long long)first);
-  int rc = check_logrwt(ctx, "merged_realize", logrwt_or_null, m.M);
-  if (rc) return rc;
+  int rc;
   const size_t M = (size_t)m.M, D = (size_t)m.ndim, nblk = blocks_for(M, kChunk);
   const size_t tile = (size_t)(nreal < kRealLaunch ? nreal : kRealLaunch), W = 3 + D;
   arena_reset(ctx);
-  rc = arena_reserve(ctx, (M * 2 + tile * nblk * (1 + kPart + (want_mean ? D : 0)) + (size_t)nreal * W) * 8 + 16 * 256);
+  rc = arena_reserve(ctx, (M * 2 + tile * nblk * (1 + kPart + (want_mean ? D : 0) + (kld ? 1 : 0)) +
+                           (size_t)nreal * W) * 8 + 18 * 256);
   if (rc) return rc;
   RArgs a;
   a.M = m.M;
@@ -1779,10 +1822,16 @@ int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int 
   a.mpart = want_mean ? (double*)arena_get(ctx, tile * nblk * D * 8) : nullptr;
   double* d_out = (double*)arena_get(ctx, (size_t)nreal * W * 8);
   if (!lae || (logrwt_or_null && !a.rwt) || !a.sums || !a.part || (want_mean && !a.mpart) || !d_out) return DH_ERR_NOMEM;
+  if (kld) {
+    a.kpart = (double*)arena_get(ctx, tile * nblk * 8);
+    if (!a.kpart) return DH_ERR_NOMEM;
+    a.lwt0 = m.logwt;
+    a.lz0 = m.logz + (M - 1);
+  }
   a.lae = lae;
   hipStream_t st = ctx->stream;
   const size_t lds = (size_t)(2 * kT * 3 + (want_mean ? kRealTile * kChunk + kSeg * kRealTile * kColTile : 0)) * 8;
-  if (!lds_limit(ctx, me_integrate<false>, lds)) return DH_ERR_HIP;
+  if (!(kld ? lds_limit(ctx, me_integrate<false, true>, lds) : lds_limit(ctx, me_integrate<false, false>, lds))) return DH_ERR_HIP;
   hipLaunchKernelGGL(me_lae, dim3(blocks_for(M, kT)), dim3(kT), 0, st, m.M, m.logl, lae);
   for (int r0 = 0; r0 < nreal; r0 += kRealLaunch) {
     a.nreal = nreal - r0 < kRealLaunch ? nreal - r0 : kRealLaunch;
@@ -1791,8 +1840,13 @@ int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int 
     const dim3 grid((unsigned)nblk, blocks_for((size_t)a.nreal, kRealTile));
     hipLaunchKernelGGL(me_step_sums, grid, dim3(kT), 0, st, a);
     hipLaunchKernelGGL(me_step_carry, dim3(a.nreal), dim3(kT), 0, st, a);
-    hipLaunchKernelGGL(me_integrate<false>, grid, dim3(kT), lds, st, a);
-    hipLaunchKernelGGL(me_finish, dim3(a.nreal), dim3(kT), 0, st, a);
+    if (kld) {
+      hipLaunchKernelGGL((me_integrate<false, true>), grid, dim3(kT), lds, st, a);
+      hipLaunchKernelGGL(me_finish<true>, dim3(a.nreal), dim3(kT), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((me_integrate<false, false>), grid, dim3(kT), lds, st, a);
+      hipLaunchKernelGGL(me_finish<false>, dim3(a.nreal), dim3(kT), 0, st, a);
+    }
   }
   if (!hip_ok(ctx, hipGetLastError(), "realize launch")) return DH_ERR_HIP;
   std::vector<double> host((size_t)nreal * W);
@@ -1805,8 +1859,28 @@ int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int 
     if (ess) ess[b] = host[b * W + 2];
     if (mean)
       for (size_t c = 0; c < D; ++c) mean[b * D + c] = host[b * W + 3 + c];
+    if (kld) kld[b] = host[b * W + 3];
   }
   return DH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dh_merged_realize(dh_ctx* ctx, uint64_t seed, int64_t first, int nreal, int jitter, const double* logrwt_or_null,
+                      int want_mean, double* logz, double* h, double* ess, double* mean) {
+  DH_CHECK_CTX(ctx);
+  if (need_merged(ctx)) return DH_ERR_ARG;
+  const dh_merged& m = ctx->merged;
+  if (nreal < 1 || nreal > kRealMax || (jitter != 0 && jitter != 1) || (!jitter && nreal != 1) || first < 0 ||
+      first > INT64_MAX - nreal || !logz || (!!want_mean != !!mean))
+    return fail(ctx, DH_ERR_ARG,
+                "merged_realize: nreal %d (1 to %d; 1 with jitter = 0), jitter %d (0 or 1), first %lld (>= 0), logz, and "
+                "want_mean with mean", nreal, kRealMax, jitter, (long long)first);
+  const int rc = check_logrwt(ctx, "merged_realize", logrwt_or_null, m.M);
+  if (rc) return rc;
+  return realize_core(ctx, seed, first, nreal, jitter, logrwt_or_null, want_mean, logz, h, ess, mean, nullptr);
 }
 
 int dh_merged_realization(dh_ctx* ctx, uint64_t seed, int64_t real, int jitter, const double* logrwt_or_null, int field,
@@ -1815,9 +1889,10 @@ int dh_merged_realization(dh_ctx* ctx, uint64_t seed, int64_t real, int jitter, 
   if (need_merged(ctx)) return DH_ERR_ARG;
   const dh_merged& m = ctx->merged;
   if (real < 0 || (jitter != 0 && jitter != 1) ||
-      (field != DH_MERGED_LOGVOL && field != DH_MERGED_LOGWT && field != DH_MERGED_LOGZ))
-    return fail(ctx, DH_ERR_ARG, "merged_realization: real %lld (>= 0), jitter %d (0 or 1), field %d (LOGVOL, LOGWT or LOGZ)",
-                (long long)real, jitter, field);
+      (field != DH_MERGED_LOGVOL && field != DH_MERGED_LOGWT && field != DH_MERGED_LOGZ && field != DH_MERGED_KLD) ||
+      (field == DH_MERGED_KLD && logrwt_or_null))
+    return fail(ctx, DH_ERR_ARG, "merged_realization: real %lld (>= 0), jitter %d (0 or 1), field %d (LOGVOL, LOGWT, LOGZ, or "
+                "KLD without logrwt)", (long long)real, jitter, field);
   if (first < 0 || count < 0 || first > m.M || count > m.M - first || (count && !out))
     return fail(ctx, DH_ERR_ARG, "merged_realization: [%lld, %lld + %lld) of %lld points", (long long)first, (long long)first,
                 (long long)count, m.M);
@@ -1826,7 +1901,7 @@ int dh_merged_realization(dh_ctx* ctx, uint64_t seed, int64_t real, int jitter, 
   if (!count) return DH_OK;
   const size_t M = (size_t)m.M, nblk = blocks_for(M, kChunk);
   arena_reset(ctx);
-  rc = arena_reserve(ctx, M * 6 * 8 + (nblk + 1) * sizeof(LsePair) + 16 * 256);
+  rc = arena_reserve(ctx, M * 7 * 8 + (nblk + 1) * sizeof(LsePair) + 18 * 256);
   if (rc) return rc;
   double* lae = (double*)arena_get(ctx, M * 8);
   const double* rwt = logrwt_or_null ? arena_up(ctx, logrwt_or_null, M) : nullptr;
@@ -1835,14 +1910,18 @@ int dh_merged_realization(dh_ctx* ctx, uint64_t seed, int64_t real, int jitter, 
   double* logwt = (double*)arena_get(ctx, M * 8);
   double* logz = (double*)arena_get(ctx, M * 8);
   void* part = arena_get(ctx, (nblk + 1) * sizeof(LsePair));
-  if (!lae || (logrwt_or_null && !rwt) || !step || !logvol || !logwt || !logz || !part) return DH_ERR_NOMEM;
+  double* kld = field == DH_MERGED_KLD ? (double*)arena_get(ctx, M * 8) : logz;
+  if (!lae || (logrwt_or_null && !rwt) || !step || !logvol || !logwt || !logz || !part || !kld) return DH_ERR_NOMEM;
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(me_lae, dim3(blocks_for(M, kT)), dim3(kT), 0, st, m.M, m.logl, lae);
   if (!run_scan(ctx, FRealVol{m.n, step, logvol, seed, (uint64_t)real, jitter}, m.M, part)) return DH_ERR_HIP;
   if (field != DH_MERGED_LOGVOL &&
       !run_scan(ctx, FRealLogz{lae, rwt, logvol, step, logwt, logz}, m.M, part))
     return DH_ERR_HIP;
-  const double* src = field == DH_MERGED_LOGVOL ? logvol : field == DH_MERGED_LOGWT ? logwt : logz;
+  if (field == DH_MERGED_KLD &&
+      !run_scan(ctx, FRealKld{logwt, logz, m.logwt, m.logz + (M - 1), nullptr, kld, m.M}, m.M, part))
+    return DH_ERR_HIP;
+  const double* src = field == DH_MERGED_LOGVOL ? logvol : field == DH_MERGED_LOGWT ? logwt : field == DH_MERGED_KLD ? kld : logz;
   if (!down(ctx, out, src + first, (size_t)count)) return DH_ERR_HIP;
   return dh_sync(ctx);
 }
@@ -2002,6 +2081,7 @@ struct BootBuf {
   void* part = nullptr;
   double *lae = nullptr, *sums = nullptr, *partr = nullptr, *mpart = nullptr, *out = nullptr;  // batch
   double *step = nullptr, *logvol = nullptr, *logwt = nullptr, *logz = nullptr;                // per-point fields
+  double *kpart = nullptr, *kld = nullptr;  // the divergence: the chunks' sums (batch); per point (fields)
   long long* wide = nullptr;
 };
 
@@ -2010,7 +2090,7 @@ int boot_carve(dh_ctx* ctx, BootBuf& b, size_t cap, bool fields, bool want_mean)
   const size_t M = (size_t)m.M, S = (size_t)m.runs * m.nlive, D = (size_t)m.ndim;
   const size_t nblk = blocks_for(M > cap ? M : cap, kChunk), nbx = blocks_for(cap, kChunk);
   const size_t bytes = S * 4 + M * 8 + 64 + (nblk + 1) * sizeof(LsePair) + cap * 16 +
-                       (fields ? cap * 40 : (nbx * (1 + kPart + (want_mean ? D : 0)) + 3 + D) * 8) + 24 * 256;
+                       (fields ? cap * 48 : (nbx * (2 + kPart + (want_mean ? D : 0)) + 4 + D) * 8) + 27 * 256;
   arena_reset(ctx);
   const int rc = arena_reserve(ctx, bytes);
   if (rc) return rc;
@@ -2031,13 +2111,15 @@ int boot_carve(dh_ctx* ctx, BootBuf& b, size_t cap, bool fields, bool want_mean)
     b.logwt = (double*)arena_get(ctx, cap * 8);
     b.logz = (double*)arena_get(ctx, cap * 8);
     b.wide = (long long*)arena_get(ctx, cap * 8);
-    ok = ok && b.step && b.logvol && b.logwt && b.logz && b.wide;
+    b.kld = (double*)arena_get(ctx, cap * 8);
+    ok = ok && b.step && b.logvol && b.logwt && b.logz && b.wide && b.kld;
   } else {
     b.sums = (double*)arena_get(ctx, nbx * 8);
     b.partr = (double*)arena_get(ctx, nbx * kPart * 8);
     b.mpart = want_mean ? (double*)arena_get(ctx, nbx * D * 8) : nullptr;
     b.out = (double*)arena_get(ctx, (3 + D) * 8);
-    ok = ok && b.sums && b.partr && (!want_mean || b.mpart) && b.out;
+    b.kpart = (double*)arena_get(ctx, nbx * 8);
+    ok = ok && b.sums && b.partr && (!want_mean || b.mpart) && b.out && b.kpart;
   }
   return ok ? DH_OK : DH_ERR_NOMEM;
 }
@@ -2134,19 +2216,11 @@ int boot_expand(dh_ctx* ctx, BootBuf& b, const char* what, uint64_t seed, long l
   return hip_ok(ctx, hipGetLastError(), "bootstrap launch") ? DH_OK : DH_ERR_HIP;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dh_merged_bootstrap(dh_ctx* ctx, uint64_t seed, int64_t first, int nboot, int jitter, const int32_t* mult_or_null,
-                        int want_mean, double* logz, double* h, double* ess, double* mean, int64_t* npoints) {
-  DH_CHECK_CTX(ctx);
-  int rc = boot_need(ctx, "merged_bootstrap", jitter, mult_or_null, nboot);
-  if (rc) return rc;
-  if (nboot < 1 || nboot > kBootMax || first < 0 || first > INT64_MAX - nboot || !logz || (!!want_mean != !!mean))
-    return fail(ctx, DH_ERR_ARG, "merged_bootstrap: nboot %d (1 to %d), first %lld (>= 0), logz, and want_mean with mean", nboot,
-                kBootMax, (long long)first);
-  rc = boot_ties(ctx);
+// dh_merged_bootstrap after its argument checks; kld (or null): the bootstraps' divergence from the merged run too
+// (dh_merged_kld; logz may then be null)
+int bootstrap_core(dh_ctx* ctx, const char* what, uint64_t seed, int64_t first, int nboot, int jitter, const int32_t* mult_or_null,
+                   int want_mean, double* logz, double* h, double* ess, double* mean, int64_t* npoints, double* kld) {
+  int rc = boot_ties(ctx);
   if (rc) return rc;
   const dh_merged& m = ctx->merged;
   const size_t M = (size_t)m.M, D = (size_t)m.ndim, W = 3 + D;
@@ -2155,11 +2229,11 @@ int dh_merged_bootstrap(dh_ctx* ctx, uint64_t seed, int64_t first, int nboot, in
   if (rc) return rc;
   hipStream_t st = ctx->stream;
   const size_t lds = (size_t)(2 * kT * 3 + (want_mean ? kRealTile * kChunk + kSeg * kRealTile * kColTile : 0)) * 8;
-  if (!lds_limit(ctx, me_integrate<true>, lds)) return DH_ERR_HIP;
+  if (!(kld ? lds_limit(ctx, me_integrate<true, true>, lds) : lds_limit(ctx, me_integrate<true, false>, lds))) return DH_ERR_HIP;
   std::vector<double> host((size_t)nboot * W);
   for (int i = 0; i < nboot; ++i) {
     long long Mx = 0;
-    rc = boot_expand(ctx, b, "merged_bootstrap", seed, (long long)first + i, mult_or_null, false, want_mean != 0, &Mx);
+    rc = boot_expand(ctx, b, what, seed, (long long)first + i, mult_or_null, false, want_mean != 0, &Mx);
     if (rc) return rc;
     if (npoints) npoints[i] = Mx;
     RArgs a;
@@ -2184,8 +2258,16 @@ int dh_merged_bootstrap(dh_ctx* ctx, uint64_t seed, int64_t first, int nboot, in
     const dim3 grid((unsigned)a.nblk, 1);
     hipLaunchKernelGGL(me_step_sums, grid, dim3(kT), 0, st, a);
     hipLaunchKernelGGL(me_step_carry, dim3(1), dim3(kT), 0, st, a);
-    hipLaunchKernelGGL(me_integrate<true>, grid, dim3(kT), lds, st, a);
-    hipLaunchKernelGGL(me_finish, dim3(1), dim3(kT), 0, st, a);
+    if (kld) {
+      a.lwt0 = m.logwt;
+      a.lz0 = m.logz + (M - 1);
+      a.kpart = b.kpart;
+      hipLaunchKernelGGL((me_integrate<true, true>), grid, dim3(kT), lds, st, a);
+      hipLaunchKernelGGL(me_finish<true>, dim3(1), dim3(kT), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((me_integrate<true, false>), grid, dim3(kT), lds, st, a);
+      hipLaunchKernelGGL(me_finish<false>, dim3(1), dim3(kT), 0, st, a);
+    }
     // (the row leaves before the next bootstrap's totals are waited for: one synchronisation per bootstrap)
     if (!hip_ok(ctx, hipGetLastError(), "bootstrap launch") || !down(ctx, host.data() + (size_t)i * W, (const double*)b.out, W))
       return DH_ERR_HIP;
@@ -2193,13 +2275,59 @@ int dh_merged_bootstrap(dh_ctx* ctx, uint64_t seed, int64_t first, int nboot, in
   rc = dh_sync(ctx);
   if (rc) return rc;
   for (size_t i = 0; i < (size_t)nboot; ++i) {
-    logz[i] = host[i * W];
+    if (logz) logz[i] = host[i * W];
     if (h) h[i] = host[i * W + 1];
     if (ess) ess[i] = host[i * W + 2];
     if (mean)
       for (size_t c = 0; c < D; ++c) mean[i * D + c] = host[i * W + 3 + c];
+    if (kld) kld[i] = host[i * W + 3];
   }
   return DH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dh_merged_bootstrap(dh_ctx* ctx, uint64_t seed, int64_t first, int nboot, int jitter, const int32_t* mult_or_null,
+                        int want_mean, double* logz, double* h, double* ess, double* mean, int64_t* npoints) {
+  DH_CHECK_CTX(ctx);
+  const int rc = boot_need(ctx, "merged_bootstrap", jitter, mult_or_null, nboot);
+  if (rc) return rc;
+  if (nboot < 1 || nboot > kBootMax || first < 0 || first > INT64_MAX - nboot || !logz || (!!want_mean != !!mean))
+    return fail(ctx, DH_ERR_ARG, "merged_bootstrap: nboot %d (1 to %d), first %lld (>= 0), logz, and want_mean with mean", nboot,
+                kBootMax, (long long)first);
+  return bootstrap_core(ctx, "merged_bootstrap", seed, first, nboot, jitter, mult_or_null, want_mean, logz, h, ess, mean, npoints,
+                        nullptr);
+}
+
+// The divergence of realizations or bootstraps from the merged run (utils.kld_error,
+// utils.py:1932-1997): the batch form of the two calls above with one more chunk sum.
+int dh_merged_kld(dh_ctx* ctx, uint64_t seed, int64_t first, int n, int mode, const int32_t* mult_or_null, double* kld,
+                  double* logz_or_null, int64_t* npoints_or_null) {
+  DH_CHECK_CTX(ctx);
+  if (need_merged(ctx)) return DH_ERR_ARG;
+  if (mode != DH_KLD_JITTER && mode != DH_KLD_RESAMPLE && mode != DH_KLD_SIMULATE)
+    return fail(ctx, DH_ERR_ARG, "merged_kld: mode %d (JITTER, RESAMPLE or SIMULATE)", mode);
+  if (mode != DH_KLD_JITTER) {
+    const int rc = boot_need(ctx, "merged_kld", mode == DH_KLD_SIMULATE, mult_or_null, n);
+    if (rc) return rc;
+  }
+  const int cap = mode == DH_KLD_JITTER ? kRealMax : kBootMax;
+  if (n < 1 || n > cap || first < 0 || first > INT64_MAX - n || !kld || (mode == DH_KLD_JITTER && mult_or_null))
+    return fail(ctx, DH_ERR_ARG, "merged_kld: n %d (1 to %d), first %lld (>= 0), kld, and mult with a bootstrap mode only", n, cap,
+                (long long)first);
+  if (mode == DH_KLD_JITTER) {
+    std::vector<double> lz(logz_or_null ? 0 : (size_t)n);
+    const int rc = realize_core(ctx, seed, first, n, 1, nullptr, 0, logz_or_null ? logz_or_null : lz.data(), nullptr, nullptr,
+                                nullptr, kld);
+    if (rc) return rc;
+    if (npoints_or_null)
+      for (int i = 0; i < n; ++i) npoints_or_null[i] = ctx->merged.M;
+    return DH_OK;
+  }
+  return bootstrap_core(ctx, "merged_kld", seed, first, n, mode == DH_KLD_SIMULATE, mult_or_null, 0, logz_or_null, nullptr, nullptr,
+                        nullptr, npoints_or_null, kld);
 }
 
 int dh_merged_bootstrap_run(dh_ctx* ctx, uint64_t seed, int64_t boot, int jitter, const int32_t* mult_or_null, int field,
@@ -2209,8 +2337,8 @@ int dh_merged_bootstrap_run(dh_ctx* ctx, uint64_t seed, int64_t boot, int jitter
   if (rc) return rc;
   if (boot < 0 || first < 0 || count < 0 || (count && !out) ||
       (field != DH_MERGED_LOGVOL && field != DH_MERGED_LOGWT && field != DH_MERGED_LOGZ && field != DH_MERGED_SAMPLES_N &&
-       field != DH_MERGED_SRC))
-    return fail(ctx, DH_ERR_ARG, "merged_bootstrap_run: boot %lld (>= 0), field %d (LOGVOL, LOGWT, LOGZ, SAMPLES_N or SRC), "
+       field != DH_MERGED_SRC && field != DH_MERGED_KLD))
+    return fail(ctx, DH_ERR_ARG, "merged_bootstrap_run: boot %lld (>= 0), field %d (LOGVOL, LOGWT, LOGZ, KLD, SAMPLES_N or SRC), "
                 "first %lld, count %lld", (long long)boot, field, (long long)first, (long long)count);
   rc = boot_ties(ctx);
   if (rc) return rc;
@@ -2241,10 +2369,192 @@ int dh_merged_bootstrap_run(dh_ctx* ctx, uint64_t seed, int64_t boot, int jitter
     if (!run_scan(ctx, FRealVol{b.n, b.step, b.logvol, seed, (uint64_t)boot, jitter}, Mx, b.part)) return DH_ERR_HIP;
     if (field != DH_MERGED_LOGVOL && !run_scan(ctx, FRealLogz{b.lae, nullptr, b.logvol, b.step, b.logwt, b.logz}, Mx, b.part))
       return DH_ERR_HIP;
-    const double* src = field == DH_MERGED_LOGVOL ? b.logvol : field == DH_MERGED_LOGWT ? b.logwt : b.logz;
+    if (field == DH_MERGED_KLD &&
+        !run_scan(ctx, FRealKld{b.logwt, b.logz, m.logwt, m.logz + (M - 1), b.src, b.kld, Mx}, Mx, b.part))
+      return DH_ERR_HIP;
+    const double* src = field == DH_MERGED_LOGVOL ? b.logvol : field == DH_MERGED_LOGWT ? b.logwt : field == DH_MERGED_KLD ? b.kld : b.logz;
     ok = down(ctx, (double*)out, src + f, c);
   }
   if (!ok) return DH_ERR_HIP;
+  return dh_sync(ctx);
+}
+
+}  // extern "C"
+
+// ---- the weight function of the merged run (dynamicsampler.py:48-170) -------------------------
+//
+// zweight: with Ztot = logaddexp(LOGZ_{M-1}, LOGL_{M-1} + LOGVOL_{M-1}) the remaining evidence of point k over its live
+// count, lzw_k = Ztot + log(-expm1(LOGZ_k - Ztot)) - log(n_k), normalised by one fixed-order log-sum-exp (the scans'
+// Lse pairs: a workgroup's chunk, then the chunks in scan_carry's order); 1 / M where the cumulative ln Z never moved.
+// weight = (1 - pfrac) zweight + pfrac pweight, pweight the WEIGHT field; its maximum and the first and last point above
+// maxfrac x maximum through integer atomics (a non-negative double orders as its bits do): exact in any order.
+namespace {
+
+struct FZw {
+  typedef Lse Op;
+  const double *logz, *logl, *logvol;
+  const int* n;
+  long long M;
+  __device__ double lzw(long long k) const {
+    const double ztot = logaddexp_np(logz[M - 1], logl[M - 1] + logvol[M - 1]);
+    return ztot + log(-expm1(logz[k] - ztot)) - log((double)n[k]);
+  }
+  __device__ LsePair term(long long k) const { return LsePair{lzw(k), 1.0}; }
+  __device__ void put(long long, LsePair, LsePair) const {}
+};
+
+// one workgroup: tot[0] = ln sum exp of the chunks' pairs, combined as scan_carry combines them
+__global__ void __launch_bounds__(kT) mw_lse_total(const LsePair* __restrict__ part, int nblk, double* __restrict__ tot) {
+  __shared__ LsePair lds[2 * kT];
+  LsePair carry = Lse::id();
+  for (int b0 = 0; b0 < nblk; b0 += kT) {
+    const int b = b0 + threadIdx.x;
+    const LsePair v = b < nblk ? part[b] : Lse::id();
+    LsePair ex, t;
+    block_scan<Lse>(v, lds, &ex, &t);
+    carry = Lse::op(carry, t);
+  }
+  if (threadIdx.x == 0) tot[0] = carry.m + log(carry.s);
+}
+
+// zw, wt (either may be null) and the maximum of wt as bits in wmax[0] (zeroed before the launch)
+__global__ void __launch_bounds__(kT) mw_weight(FZw f, double pfrac, const double* __restrict__ pw, const double* __restrict__ tot,
+                                                double* __restrict__ zw, double* __restrict__ wt, unsigned long long* wmax) {
+  __shared__ unsigned long long lds[kT];
+  const long long k = (long long)blockIdx.x * kT + threadIdx.x;
+  unsigned long long bits = 0;
+  if (k < f.M) {
+    const double z = f.logz[0] == f.logz[f.M - 1] ? 1.0 / (double)f.M : exp(f.lzw(k) - tot[0]);
+    const double w = __dadd_rn(__dmul_rn(1.0 - pfrac, z), __dmul_rn(pfrac, pw[k]));  // (as written: no contraction)
+    if (zw) zw[k] = z;
+    if (wt) wt[k] = w;
+    bits = w > 0 ? (unsigned long long)__double_as_longlong(w) : 0;  // (NaN and 0 are no maximum)
+  }
+  lds[threadIdx.x] = bits;
+  __syncthreads();
+  for (int d = kT / 2; d > 0; d >>= 1) {
+    if (threadIdx.x < d && lds[threadIdx.x + d] > lds[threadIdx.x]) lds[threadIdx.x] = lds[threadIdx.x + d];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && lds[0]) atomicMax(wmax, lds[0]);
+}
+
+// idx[0] / idx[1]: the first / last k with wt[k] > maxfrac max (set to M / -1 before the launch)
+__global__ void __launch_bounds__(kT) mw_bounds(long long M, double maxfrac, const double* __restrict__ wt,
+                                                const unsigned long long* __restrict__ wmax, int* idx) {
+  __shared__ int lo[kT], hi[kT];
+  const long long k = (long long)blockIdx.x * kT + threadIdx.x;
+  const double thr = __dmul_rn(maxfrac, __longlong_as_double((long long)wmax[0]));
+  const bool on = k < M && wt[k] > thr;
+  lo[threadIdx.x] = on ? (int)k : 0x7fffffff;
+  hi[threadIdx.x] = on ? (int)k : -1;
+  __syncthreads();
+  for (int d = kT / 2; d > 0; d >>= 1) {
+    if (threadIdx.x < d) {
+      lo[threadIdx.x] = min(lo[threadIdx.x], lo[threadIdx.x + d]);
+      hi[threadIdx.x] = max(hi[threadIdx.x], hi[threadIdx.x + d]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && hi[0] >= 0) {
+    atomicMin(&idx[0], lo[0]);
+    atomicMax(&idx[1], hi[0]);
+  }
+}
+
+struct WBuf {
+  double *tot = nullptr, *zw = nullptr, *wt = nullptr;
+  unsigned long long* wmax = nullptr;
+  int* idx = nullptr;
+};
+
+// zweight and weight of every point into the arena, the maximum's bits in wmax
+int weights_enqueue(dh_ctx* ctx, double pfrac, WBuf& w) {
+  const dh_merged& m = ctx->merged;
+  const size_t M = (size_t)m.M, nblk = blocks_for(M, kChunk);
+  arena_reset(ctx);
+  const int rc = arena_reserve(ctx, M * 16 + (nblk + 1) * sizeof(LsePair) + 8 * 256);
+  if (rc) return rc;
+  LsePair* part = (LsePair*)arena_get(ctx, (nblk + 1) * sizeof(LsePair));
+  w.tot = (double*)arena_get(ctx, 8);
+  w.wmax = (unsigned long long*)arena_get(ctx, 8);
+  w.idx = (int*)arena_get(ctx, 8);
+  w.zw = (double*)arena_get(ctx, M * 8);
+  w.wt = (double*)arena_get(ctx, M * 8);
+  if (!part || !w.tot || !w.wmax || !w.idx || !w.zw || !w.wt) return DH_ERR_NOMEM;
+  hipStream_t st = ctx->stream;
+  const FZw f{m.logz, m.logl, m.logvol, m.n, m.M};
+  if (!hip_ok(ctx, hipMemsetAsync(w.wmax, 0, 8, st), "memset")) return DH_ERR_HIP;
+  hipLaunchKernelGGL(scan_reduce<FZw>, dim3((unsigned)nblk), dim3(kT), 0, st, f, m.M, part);
+  hipLaunchKernelGGL(mw_lse_total, dim3(1), dim3(kT), 0, st, (const LsePair*)part, (int)nblk, w.tot);
+  hipLaunchKernelGGL(mw_weight, dim3(blocks_for(M, kT)), dim3(kT), 0, st, f, pfrac, (const double*)m.w, (const double*)w.tot, w.zw,
+                     w.wt, w.wmax);
+  return hip_ok(ctx, hipGetLastError(), "weights launch") ? DH_OK : DH_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dh_merged_weight_function(dh_ctx* ctx, double pfrac, double maxfrac, int64_t pad, double* logl_bounds, int64_t* idx) {
+  DH_CHECK_CTX(ctx);
+  if (need_merged(ctx)) return DH_ERR_ARG;
+  if (!(pfrac >= 0.0 && pfrac <= 1.0) || !(maxfrac >= 0.0 && maxfrac <= 1.0) || pad < 0 || !logl_bounds)
+    return fail(ctx, DH_ERR_ARG, "merged_weight_function: pfrac %g and maxfrac %g in [0, 1], pad %lld >= 0, logl_bounds", pfrac,
+                maxfrac, (long long)pad);
+  const dh_merged& m = ctx->merged;
+  WBuf w;
+  int rc = weights_enqueue(ctx, pfrac, w);
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  const int init[2] = {0x7fffffff, -1};
+  int got[2] = {0, 0};
+  if (!hip_ok(ctx, hipMemcpyAsync(w.idx, init, 8, hipMemcpyHostToDevice, st), "H2D")) return DH_ERR_HIP;
+  hipLaunchKernelGGL(mw_bounds, dim3(blocks_for((size_t)m.M, kT)), dim3(kT), 0, st, m.M, maxfrac, (const double*)w.wt,
+                     (const unsigned long long*)w.wmax, w.idx);
+  if (!hip_ok(ctx, hipGetLastError(), "weights launch") || !down(ctx, got, (const int*)w.idx, 2)) return DH_ERR_HIP;
+  rc = dh_sync(ctx);
+  if (rc) return rc;
+  if (got[1] < 0) return fail(ctx, DH_ERR_VALUE, "merged_weight_function: no weight above %g x the largest", maxfrac);
+  if (idx) {
+    idx[0] = got[0];
+    idx[1] = got[1];
+  }
+  // the padding and overflow rules of dynamicsampler.py:147-166, as written
+  const long long ns = m.M;
+  long long b0 = (long long)got[0] - pad, b1 = (long long)got[1] + pad;
+  if (b1 > ns - 1) {
+    b0 = b0 - (b1 - (ns - 1));
+    b1 = ns - 1;
+  }
+  const long long at0 = b0 <= 0 ? -1 : b0, at1 = b0 <= 0 ? (b1 - b0 < ns - 1 ? b1 - b0 : ns - 1) : b1;
+  double l0 = -INFINITY, l1 = INFINITY;
+  if (at0 >= 0 && !down(ctx, &l0, (const double*)m.logl + at0, 1)) return DH_ERR_HIP;
+  if (b1 != ns - 1 && !down(ctx, &l1, (const double*)m.logl + at1, 1)) return DH_ERR_HIP;
+  rc = dh_sync(ctx);
+  if (rc) return rc;
+  logl_bounds[0] = l0;
+  logl_bounds[1] = l1;
+  return DH_OK;
+}
+
+int dh_merged_weights(dh_ctx* ctx, double pfrac, int which, int64_t first, int64_t count, double* out) {
+  DH_CHECK_CTX(ctx);
+  if (need_merged(ctx)) return DH_ERR_ARG;
+  const dh_merged& m = ctx->merged;
+  if (!(pfrac >= 0.0 && pfrac <= 1.0) || (which != DH_WEIGHT_P && which != DH_WEIGHT_Z && which != DH_WEIGHT_BOTH) || first < 0 ||
+      count < 0 || first > m.M || count > m.M - first || (count && !out))
+    return fail(ctx, DH_ERR_ARG, "merged_weights: pfrac %g in [0, 1], which %d (P, Z or BOTH), [%lld, %lld + %lld) of %lld points",
+                pfrac, which, (long long)first, (long long)first, (long long)count, m.M);
+  if (!count) return DH_OK;
+  const double* src = m.w;
+  if (which != DH_WEIGHT_P) {
+    WBuf w;
+    const int rc = weights_enqueue(ctx, pfrac, w);
+    if (rc) return rc;
+    src = which == DH_WEIGHT_Z ? w.zw : w.wt;
+  }
+  if (!down(ctx, out, src + first, (size_t)count)) return DH_ERR_HIP;
   return dh_sync(ctx);
 }
 

@@ -13,7 +13,8 @@ is asked for them.
 """
 import numpy as np
 
-from .errors import Errors, bootstrap_host, bootstrap_run_host, realization_host, realize_host
+from .errors import (Errors, bootstrap_host, bootstrap_run_host, kld_bootstrap_host, kld_bootstrap_run_host, kld_host,
+                     kld_run_host, realization_host, realize_host, weight_bounds, weight_indices, weights_host)
 from .marginals import Marginals
 
 RECORD_FIELDS = ("run", "logz", "logzerr", "niter", "ncall", "h")
@@ -214,7 +215,8 @@ class MergedRun(dict, Marginals, Errors):
     in NumPy as there on the device; so are the strand bootstrap's
     bootstrap_realizations / resample_run / simulate_run /
     logz_error_sampling / logz_error_total, which need samples_run and
-    samples_id."""
+    samples_id; and kld_realizations / kld_error / weight_function /
+    stopping_function."""
     __getattr__ = dict.get
 
     def _err_logl(self):
@@ -246,6 +248,41 @@ class MergedRun(dict, Marginals, Errors):
     def _err_bootstrap_run(self, seed, boot, jitter, mult):
         strand, final, S = self._err_strands()
         return bootstrap_run_host(self["logl"], strand, final, S, seed, boot, jitter, mult)
+
+    def _err_kld(self, seed, first, n, mode, mult):
+        if mode == 0:
+            kld, lz = kld_host(self["logl"], self["samples_n"], self["logwt"], self["logz"][-1], seed, first, n)
+            return kld, lz, np.full(len(kld), len(self["logl"]), dtype=np.int64)
+        strand, final, S = self._err_strands()
+        return kld_bootstrap_host(self["logl"], strand, final, S, self["logwt"], self["logz"][-1], seed, first, n,
+                                  mode == 2, mult)
+
+    def _err_kld_run(self, seed, index, mode, mult, first, count):
+        if mode == 0:
+            out = kld_run_host(self["logl"], self["samples_n"], self["logwt"], self["logz"][-1], seed, index)
+        else:
+            strand, final, S = self._err_strands()
+            out = kld_bootstrap_run_host(self["logl"], strand, final, S, self["logwt"], self["logz"][-1], seed, index,
+                                         mode == 2, mult)
+        first = int(first)
+        count = len(out) - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > len(out):
+            raise ValueError(f"[{first}, {first + count}) of {len(out)} points")
+        return np.ascontiguousarray(out[first:first + count])
+
+    def _err_weights(self, pfrac):
+        return weights_host(self["logl"], self["logvol"], self["logz"], self["samples_n"], self.importance_weights(),
+                            pfrac)
+
+    def _err_weight_function(self, pfrac, maxfrac, pad):
+        i0, i1 = weight_indices(self._err_weights(pfrac)[2], maxfrac)
+        logl = self["logl"]
+        return weight_bounds(i0, i1, pad, len(logl), lambda k: logl[k]), (i0, i1)
+
+    def _err_summary(self):
+        """(logzerr, Kish's effective sample size) of the run (the reference's get_neff_from_logwt)."""
+        w = np.exp(self["logwt"] - np.max(self["logwt"]))
+        return float(self["logzerr"][-1]), float(w.sum() ** 2 / (w * w).sum())
 
     def importance_weights(self):
         """Normalised posterior weights exp(logwt - logz[-1])."""

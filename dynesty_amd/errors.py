@@ -22,7 +22,19 @@ The strand bootstrap (utils.resample_run, utils.py:1495-1660; DESIGN.md section 
 strand is a (run, live slot) pair, bootstrap b draws as many strands as there are from subsequence 2^63 + b
 (`strand_multiplicities`), the resampled run is every merged point repeated as often as its strand was drawn, in merged
 order, with the reference's live counts (`expand_host`), and its integrals are realization b of that sequence
-(jitter=False: utils.resample_run; jitter=True: a jitter_run after it, the documentation's simulate_run)."""
+(jitter=False: utils.resample_run; jitter=True: a jitter_run after it, the documentation's simulate_run).
+
+Run-level analysis of a dynamic sampler, again one surface: the Kullback-Leibler divergence
+from the merged run to a realization or a bootstrap (utils.kld_error, utils.py:1932-1997), with e_p = ln w_p -
+LOGWT_src(p) and Z the realization's own ln Z
+
+  kld = sum_p w_p e_p / sum_p w_p - (Z - LOGZ_{M-1}),   cumulative: cumsum exp(ln w_p - Z) (e_p - (Z - LOGZ_{M-1}))
+
+(the difference form: ln w - lq sits near ln Z while the divergence is small); the weight function
+(dynamicsampler.weight_function, dynamicsampler.py:48-170: `weights_host`, `weight_bounds`) and the stopping function
+(dynamicsampler.py:173-297), which is composition only."""
+import warnings
+
 import numpy as np
 
 MAX_REAL = 65536  # realizations per call (dh_merged_realize's cap)
@@ -30,6 +42,7 @@ MAX_BOOT = 65536  # bootstraps per call (dh_merged_bootstrap's cap)
 BOOT_SEQ = 1 << 63  # bootstrap b draws its strands from subsequence BOOT_SEQ + b: realization indices stay below it
 FIELDS = ("logvol", "logwt", "logz")
 BOOT_FIELDS = ("idx", "samples_n", "logvol", "logwt", "logz")
+KLD_MODES = ("jitter", "resample", "simulate")  # dh_merged_kld's DH_KLD_JITTER, _RESAMPLE, _SIMULATE
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
 _MASK, _S32 = np.uint64(0xFFFFFFFF), np.uint64(32)
@@ -261,6 +274,120 @@ def bootstrap_run_host(logl, strand, final, S, seed, boot, jitter=False, mult=No
     return dict(idx=idx, samples_n=n, logvol=logvol[0], logwt=lw[0], logz=np.logaddexp.accumulate(lw[0]))
 
 
+def _kld_of(lw, lqw, lz0):
+    """(kld, ln Z) of the realizations lw [T, M'] against LOGWT_src `lqw` [M'] and the merged run's last ln Z."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        top = lw.max(axis=1, keepdims=True)
+        w = np.exp(lw - np.where(np.isfinite(top), top, 0.0))
+        we = np.where(w > 0, w * (lw - lqw), 0.0)  # (a weight of 0 adds nothing, also where e is inf - inf)
+        sw = w.sum(axis=1)
+        lz = top[:, 0] + np.log(sw)
+        return we.sum(axis=1) / sw - (lz - lz0), lz
+
+
+def _kld_cum(lw, lqw, lz0):
+    """The cumulative divergence of one realization lw [M']."""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        lz = np.logaddexp.accumulate(lw)[-1]
+        p = np.exp(lw - lz)
+        return np.cumsum(np.where(p > 0, p * ((lw - lqw) - (lz - lz0)), 0.0))
+
+
+def _check_kld(seed, first, n, cap):
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError("seed: an unsigned 64-bit integer")
+    if not 1 <= int(n) <= cap:
+        raise ValueError(f"n {n} outside [1, {cap}]")
+    if int(first) < 0 or int(first) + int(n) > 1 << 63:
+        raise ValueError("first: a non-negative index")
+
+
+def kld_host(logl, samples_n, logwt, logz_last, seed, first, n, jitter=True):
+    """dh_merged_kld(DH_KLD_JITTER) in NumPy: (kld, logz) of the realizations first .. first + n - 1 against the merged
+    run's own logwt and last logz.  jitter=False (n = 1): the expected volumes, whose divergence is 0 to rounding."""
+    logl = np.asarray(logl, dtype=np.float64)
+    M, first, n = len(logl), int(first), int(n)
+    _check_kld(seed, first, n, MAX_REAL)
+    if not jitter and n != 1:
+        raise ValueError("the expected volumes are one realization: n = 1 with jitter=False")
+    lqw = np.asarray(logwt, dtype=np.float64)
+    kld, logz = np.empty(n), np.empty(n)
+    tile = max(1, min(n, (1 << 21) // max(M, 1)))
+    for r0 in range(0, n, tile):
+        r1 = min(n, r0 + tile)
+        s = steps(seed, [first + r for r in range(r0, r1)], samples_n, jitter)
+        kld[r0:r1], logz[r0:r1] = _kld_of(_logwt(logl, s, None)[2], lqw, float(logz_last))
+    return kld, logz
+
+
+def kld_bootstrap_host(logl, strand, final, S, logwt, logz_last, seed, first, n, jitter=False, mult=None):
+    """dh_merged_kld(DH_KLD_RESAMPLE / _SIMULATE) in NumPy: (kld, logz, npoints) of the bootstraps first .. first + n - 1."""
+    mult = _check_boot(seed, first, n, mult, int(S))
+    logl, lqw = np.asarray(logl, dtype=np.float64), np.asarray(logwt, dtype=np.float64)
+    n, first = int(n), int(first)
+    kld, logz, npts = np.empty(n), np.empty(n), np.empty(n, dtype=np.int64)
+    for b in range(n):
+        idx, nx = expand_host(logl, strand, final, strand_multiplicities(seed, first + b, S) if mult is None else mult)
+        lw = _logwt(logl[idx], steps(seed, [first + b], nx, bool(jitter)), None)[2]
+        k, z = _kld_of(lw, lqw[idx], float(logz_last))
+        kld[b], logz[b], npts[b] = k[0], z[0], len(idx)
+    return kld, logz, npts
+
+
+def kld_run_host(logl, samples_n, logwt, logz_last, seed, real, jitter=True):
+    """The field DH_MERGED_KLD of dh_merged_realization in NumPy: the cumulative divergence of realization `real`."""
+    logl = np.asarray(logl, dtype=np.float64)
+    _check_kld(seed, real, 1, MAX_REAL)
+    lw = _logwt(logl, steps(seed, [int(real)], samples_n, jitter), None)[2][0]
+    return _kld_cum(lw, np.asarray(logwt, dtype=np.float64), float(logz_last))
+
+
+def kld_bootstrap_run_host(logl, strand, final, S, logwt, logz_last, seed, boot, jitter=False, mult=None):
+    """The same of dh_merged_bootstrap_run: the cumulative divergence of bootstrap `boot`."""
+    mult = _check_boot(seed, boot, 1, mult, int(S))
+    logl = np.asarray(logl, dtype=np.float64)
+    idx, nx = expand_host(logl, strand, final, strand_multiplicities(seed, boot, S) if mult is None else mult)
+    lw = _logwt(logl[idx], steps(seed, [int(boot)], nx, bool(jitter)), None)[2][0]
+    return _kld_cum(lw, np.asarray(logwt, dtype=np.float64)[idx], float(logz_last))
+
+
+def weights_host(logl, logvol, logz, samples_n, pweight, pfrac):
+    """(pweight, zweight, weight) of dynamicsampler.compute_weights / weight_function as dh_merged_weights forms them:
+    the remaining evidence through expm1 (the reference's signed logsumexp cancels at the end of the run)."""
+    logz, M = np.asarray(logz, dtype=np.float64), len(logl)
+    if logz[0] == logz[-1]:  # the reference's np.ptp(logz) == 0 (logz never decreases)
+        zw = np.full(M, 1.0 / M)
+    else:
+        with np.errstate(divide="ignore"):
+            ztot = np.logaddexp(logz[-1], logl[-1] + logvol[-1])
+            lzw = ztot + np.log(-np.expm1(logz - ztot)) - np.log(np.asarray(samples_n, dtype=np.float64))
+            top = lzw.max()
+            zw = np.exp(lzw - (top + np.log(np.exp(lzw - top).sum())))
+    pw = np.asarray(pweight, dtype=np.float64)
+    return pw, zw, (1.0 - pfrac) * zw + pfrac * pw
+
+
+def weight_indices(weight, maxfrac):
+    """The first and last point with weight > maxfrac max(weight)."""
+    on = np.flatnonzero(weight > maxfrac * np.max(weight))
+    if not len(on):
+        raise ValueError(f"weight_function: no weight above {maxfrac} x the largest")
+    return int(on[0]), int(on[-1])
+
+
+def weight_bounds(i0, i1, pad, M, logl_at):
+    """(logl_min, logl_max) from the two indices: the padding and overflow rules of dynamicsampler.py:147-166 as
+    written.  logl_at(k): ln L of point k (at most two are asked for)."""
+    b0, b1 = int(i0) - int(pad), int(i1) + int(pad)
+    if b1 > M - 1:  # overflow on the right: the left side moves
+        b0, b1 = b0 - (b1 - (M - 1)), M - 1
+    if b0 <= 0:  # overflow on the left: -inf, and the right side expands
+        logl_min, logl_max = -np.inf, None if b1 == M - 1 else float(logl_at(min(b1 - b0, M - 1)))
+    else:
+        logl_min, logl_max = float(logl_at(b0)), None if b1 == M - 1 else float(logl_at(b1))
+    return logl_min, np.inf if logl_max is None else logl_max
+
+
 class Errors:
     """The methods both merged runs offer.  A class supplies `niter` (points), `_err_logl()`,
     `_err_realize(seed, first, nreal, jitter, logrwt, means)` -> (logz, information, ess, mean or None) and
@@ -343,3 +470,85 @@ class Errors:
     def logz_error_total(self, nboot=256, seed=0):
         """The same over bootstraps that are jittered too: the total error (simulate_run)."""
         return self._boot_error(nboot, seed, True, "logz_error_total")
+
+    # Run-level analysis (DESIGN.md section 3.8.4).  A class supplies `_err_kld(seed, first, n, mode, mult)` ->
+    # (kld, logz, npoints), `_err_kld_run(seed, index, mode, mult, first, count)`, `_err_weights(pfrac)` -> (pweight,
+    # zweight, weight), `_err_weight_function(pfrac, maxfrac, pad)` -> ((logl_min, logl_max), (first, last)) and
+    # `_err_summary()` -> (logzerr, ess); mode is an index into KLD_MODES.
+
+    @staticmethod
+    def _kld_mode(error):
+        if error not in KLD_MODES:
+            raise ValueError(f"error {error!r}: one of {KLD_MODES}")
+        return KLD_MODES.index(error)
+
+    def kld_realizations(self, n, seed=0, first=0, error="jitter"):
+        """utils.kld_error's last value for the realizations (error='jitter': logz_realizations' stream) or strand
+        bootstraps ('resample': bootstrap_realizations; 'simulate': the same with jitter) first .. first + n - 1: a
+        dict of kld and logz, and npoints for the bootstrap modes.  The bootstrap modes may be negative, as the
+        reference's are."""
+        mode = self._kld_mode(error)
+        kld, lz, npts = self._err_kld(seed, first, n, mode, None)
+        out = dict(kld=kld, logz=lz)
+        if mode:
+            out["npoints"] = npts
+        return out
+
+    def kld_error(self, seed=0, index=0, error="jitter", mult=None, first=0, count=None):
+        """utils.kld_error: `count` points (None: to the end) from point `first` on of the cumulative divergence from
+        this run to realization or bootstrap `index`.  mult (bootstrap modes): multiplicities per strand in place of the
+        drawn ones."""
+        mode = self._kld_mode(error)
+        if mode == 0 and mult is not None:
+            raise ValueError("mult: multiplicities belong to the bootstrap modes")
+        return self._err_kld_run(seed, index, mode, mult, first, count)
+
+    @staticmethod
+    def _check_weight_args(pfrac, maxfrac, pad):
+        if not 0. <= pfrac <= 1.:
+            raise ValueError(f"The provided `pfrac` {pfrac} is not between 0. and 1.")
+        if not 0. <= maxfrac <= 1.:
+            raise ValueError(f"The provided `maxfrac` {maxfrac} is not between 0. and 1.")
+        if pad != int(pad) or pad < 0:
+            raise ValueError(f"`lpad` {pad} is less than zero (or no integer).")
+
+    def weight_function(self, pfrac=0.8, maxfrac=0.8, pad=1, return_weights=False):
+        """dynamicsampler.weight_function: (logl_min, logl_max), the ln L range of the points whose weight
+        (1 - pfrac) zweight + pfrac pweight lies above maxfrac x the largest, padded by `pad` points; with
+        return_weights=True also (pweight, zweight, weight)."""
+        self._check_weight_args(pfrac, maxfrac, pad)
+        bounds, _ = self._err_weight_function(float(pfrac), float(maxfrac), int(pad))
+        if return_weights:
+            return bounds, self._err_weights(float(pfrac))
+        return bounds
+
+    def stopping_function(self, pfrac=1.0, evid_thresh=0.1, target_n_effective=10000, n_mc=0, error="jitter", seed=0,
+                          return_vals=False):
+        """dynamicsampler.stopping_function: stop <= 1 with stop = pfrac stop_post + (1 - pfrac) stop_evid,
+        stop_post = target_n_effective / ESS, stop_evid = std(ln Z) / evid_thresh; the standard deviation (ddof 0) over
+        n_mc > 1 realizations ('jitter') or bootstraps ('resample', 'simulate') under `seed`, else the run's own
+        logzerr.  The divergences the reference computes there and drops are not computed.  return_vals: also
+        (stop_post, stop_evid, stop)."""
+        if not 0. <= pfrac <= 1.:
+            raise ValueError(f"The provided `pfrac` {pfrac} is not between 0. and 1.")
+        if pfrac < 1. and evid_thresh < 0.:
+            raise ValueError(f"The provided `evid_thresh` {evid_thresh} is not non-negative even though `pfrac` is {pfrac}.")
+        if pfrac > 0. and target_n_effective < 0.:
+            raise ValueError(f"The provided `target_n_effective` {target_n_effective} is not non-negative even though "
+                             f"`pfrac` is {pfrac}")
+        if n_mc < 0:
+            raise ValueError(f"The number of realizations {n_mc} must be greater or equal to zero.")
+        if 0 < n_mc < 20:
+            warnings.warn("Using a small number of realizations might result in excessively noisy stopping value estimates.")
+        mode = self._kld_mode(error)
+        logzerr, ess = self._err_summary()
+        if n_mc > 1:
+            lz = (self.logz_realizations(n_mc, seed) if mode == 0 else
+                  self.bootstrap_realizations(n_mc, seed, jitter=mode == 2))["logz"]
+            lnz_std = float(np.std(lz))
+        else:
+            lnz_std = float(logzerr)
+        stop_evid = lnz_std / evid_thresh
+        stop_post = target_n_effective / float(ess)
+        stop = pfrac * stop_post + (1. - pfrac) * stop_evid
+        return (stop <= 1., (stop_post, stop_evid, stop)) if return_vals else stop <= 1.

@@ -637,6 +637,9 @@ enum {
 /* Not a field of the merged run (dh_merged_fetch refuses it): for dh_merged_bootstrap_run, the merged-run index of
  * every point of a resampled run, int64. */
 #define DH_MERGED_SRC 16
+/* Nor is this one: for dh_merged_realization and dh_merged_bootstrap_run, the cumulative Kullback-Leibler divergence of
+ * one realization or bootstrap from the merged run (utils.kld_error, utils.py:1932-1997), a double per point. */
+#define DH_MERGED_KLD 17
 
 /* `runs` static runs of equal nlive merged into one run that stays on the device -- ensemble.merge_static_runs, i.e.
  * the reference's utils.merge_runs for such runs.  Host pointers: niter (runs), dead_logl / dead_id / dead_it / dead_nc
@@ -747,6 +750,39 @@ int dh_merged_bootstrap(dh_ctx* ctx, uint64_t seed, int64_t first, int nboot, in
  * [0, M'). */
 int dh_merged_bootstrap_run(dh_ctx* ctx, uint64_t seed, int64_t boot, int jitter, const int32_t* mult_or_null, int field,
                             int64_t first, int64_t count, void* out, int64_t* npoints);
+
+/* ---- divergence, weight function -----------------------------------------------------------
+ * utils.kld_error (utils.py:1932-1997) in batches: the Kullback-Leibler divergence from the merged run to realizations
+ * (DH_KLD_JITTER: realization r of dh_merged_realize under the same stream, no logrwt) or strand bootstraps
+ * (DH_KLD_RESAMPLE: bootstrap b of dh_merged_bootstrap with jitter = 0; DH_KLD_SIMULATE: with jitter = 1) first ..
+ * first + n - 1.  With lq_k = LOGWT_k - LOGZ_{M-1}, per-point ln w_p of the realization, Z = ln sum exp ln w_p and
+ * src(p) the merged index of position p (the identity for JITTER):
+ *   kld = sum_p exp(ln w_p - Z) ((ln w_p - Z) - lq_src(p)).
+ * A position of weight 0 adds 0 (the reference's 0 x inf is NaN there); a positive weight where lq is -inf makes the
+ * result +inf; the bootstrap modes may be negative, as the reference's are (lq[src] is not normalised over the resampled
+ * run).  kld: n values; logz_or_null: their ln Z (bit for bit dh_merged_realize's / dh_merged_bootstrap's);
+ * npoints_or_null: the realizations' lengths (M for JITTER).  mult_or_null: as dh_merged_bootstrap (bootstrap modes,
+ * n = 1).  A result depends on (seed, index) alone: bit-identical alone, in any batch, at any position.
+ * DH_ERR_ARG (the merged run stays): no merged run, another mode, n outside [1, 65536], first < 0, kld NULL, mult with
+ * JITTER, and what dh_merged_bootstrap refuses for the bootstrap modes.
+ * The cumulative form is the field DH_MERGED_KLD of dh_merged_realization (without logrwt) and
+ * dh_merged_bootstrap_run; its last value equals this call's to rounding. */
+enum { DH_KLD_JITTER = 0, DH_KLD_RESAMPLE = 1, DH_KLD_SIMULATE = 2 };
+int dh_merged_kld(dh_ctx* ctx, uint64_t seed, int64_t first, int n, int mode, const int32_t* mult_or_null, double* kld,
+                  double* logz_or_null, int64_t* npoints_or_null);
+/* dynamicsampler.weight_function (dynamicsampler.py:48-170) of the merged run.  zweight_k = exp(lzw_k - ln sum exp lzw),
+ * lzw_k = Ztot + log(-expm1(LOGZ_k - Ztot)) - log(n_k), Ztot = logaddexp(LOGZ_{M-1}, LOGL_{M-1} + LOGVOL_{M-1}): the
+ * reference's ln(exp(Ztot) - exp(logz_k)) without its cancellation; 1 / M where LOGZ_0 == LOGZ_{M-1} (its
+ * np.ptp(logz) == 0 branch).  pweight is the WEIGHT field, weight = (1 - pfrac) zweight + pfrac pweight.  idx (or NULL):
+ * the first and last point with weight > maxfrac x max(weight); logl_bounds: (logl_min, logl_max) after the padding and
+ * overflow rules of lines 147-166 (+-inf at the ends).  Only these four numbers leave the device.
+ * DH_ERR_ARG (the merged run stays): no merged run, pfrac or maxfrac outside [0, 1] or NaN, pad < 0, logl_bounds NULL.
+ * DH_ERR_VALUE: no weight lies above maxfrac x the largest (maxfrac = 1; the reference fails there too). */
+int dh_merged_weight_function(dh_ctx* ctx, double pfrac, double maxfrac, int64_t pad, double* logl_bounds, int64_t* idx);
+/* `count` points from point `first` on of pweight (DH_WEIGHT_P), zweight (DH_WEIGHT_Z) or weight (DH_WEIGHT_BOTH) above.
+ * DH_ERR_ARG: no merged run, pfrac outside [0, 1], another `which`, a slice outside [0, M). */
+enum { DH_WEIGHT_P = 0, DH_WEIGHT_Z = 1, DH_WEIGHT_BOTH = 2 };
+int dh_merged_weights(dh_ctx* ctx, double pfrac, int which, int64_t first, int64_t count, double* out);
 
 #ifdef __cplusplus
 }

@@ -784,6 +784,67 @@ def gen_merge_bootstrap(out, merge_npz):
     print("wrote", out, len(g), "arrays,", os.path.getsize(out), "bytes")
 
 
+DYN_PFRAC, DYN_MAXFRAC = (0.0, 0.5, 0.8, 1.0), (0.8, 0.3, 0.05)
+DYN_STOP = ({}, dict(pfrac=0.5, evid_thresh=0.05, target_n_effective=2000), dict(pfrac=0.0, evid_thresh=0.2))
+
+
+def gen_merge_dynamic(out, merge_npz):
+    """Run-level analysis of a dynamic sampler (tests/test_merge_dynamic_cpu.py, tests/test_gpu_merge_dynamic.py), on
+    the Results gen_merge_bootstrap builds for the golden merged run and the cases of tests/bootstrap_cases.py.
+    dynamicsampler.weight_function(res, args, return_weights=True) over pfrac in DYN_PFRAC, maxfrac in DYN_MAXFRAC and
+    pad in (0, 1, 5, 2 M): the bounds, the first and last index above the threshold (from the weights it returned), and
+    the three weight arrays at pfrac 0.8.  utils.kld_error(res, 'resample', rstate) with default_rng(i), i < NCALLS: the
+    strand draws and the cumulative divergence.  For the golden run the last divergence of 2000 calls each of
+    kld_error(res, 'jitter', default_rng(40000 + i), approx=True), of the exact form with default_rng(60000 + i) and of
+    'resample' with default_rng(50000 + i), and stopping_function(res, args, return_vals=True) with n_mc = 0 for
+    DYN_STOP."""
+    from dynesty import dynamicsampler as dys
+    from dynesty import utils as dyu
+    import bootstrap_cases as bc
+    gm = np.load(merge_npz)
+    g = dict(pfrac=np.array(DYN_PFRAC), maxfrac=np.array(DYN_MAXFRAC))
+    for name in bc.NAMES:
+        m = bc.host_run(name, gm)
+        key, S = bc.strands(m)
+        M = len(key)
+        res = dyu.Results(dict(samples_u=m.samples_u, samples_id=key, samples_it=m.samples_it, logl=m.logl,
+                               samples=m.samples, samples_n=m.samples_n, logvol=m.logvol, logwt=m.logwt, logz=m.logz,
+                               logzerr=m.logzerr, information=m.information, ncall=m.ncall, blob=np.zeros(M),
+                               samples_batch=np.zeros(M, dtype=int), batch_logl_bounds=np.array([(-np.inf, np.inf)])))
+        pads = (0, 1, 5, 2 * M)
+        g[f"{name}/pad"] = np.array(pads, dtype=np.int64)
+        bounds = np.empty((len(DYN_PFRAC), len(DYN_MAXFRAC), len(pads), 2))
+        idx = np.empty((len(DYN_PFRAC), len(DYN_MAXFRAC), 2), dtype=np.int64)
+        margin = np.inf
+        for i, pf in enumerate(DYN_PFRAC):
+            for j, mf in enumerate(DYN_MAXFRAC):
+                for k, pad in enumerate(pads):
+                    bounds[i, j, k], (pw, zw, w) = dys.weight_function(res, dict(pfrac=pf, maxfrac=mf, pad=pad), return_weights=True)
+                on = np.flatnonzero(w > mf * w.max())
+                idx[i, j] = on[0], on[-1]
+                margin = min(margin, float(np.min(np.abs(w - mf * w.max())) / w.max()))
+                if pf == 0.8:
+                    g[f"{name}/pweight"], g[f"{name}/zweight"], g[f"{name}/weight"] = pw, zw, w
+        g[f"{name}/bounds"], g[f"{name}/idx"] = bounds, idx
+        print(name, "M", M, "smallest |weight - maxfrac max| / max", margin)
+        for i in range(bc.NCALLS):
+            rs = _RecordingGenerator(np.random.default_rng(i))
+            kld = dyu.kld_error(res, "resample", rstate=rs)
+            assert len(rs.draws) == 1 and rs.draws[0].shape == (S,)
+            g[f"{name}/{i}/draws"], g[f"{name}/{i}/kld"] = rs.draws[0].astype(np.int32), np.asarray(kld)
+        if name == "golden":
+            n = 2000
+            rng = np.random.default_rng
+            g["golden/jitter_approx/kld"] = np.array([dyu.kld_error(res, "jitter", rstate=rng(40000 + i), approx=True)[-1] for i in range(n)])
+            g["golden/jitter_exact/kld"] = np.array([dyu.kld_error(res, "jitter", rstate=rng(60000 + i), approx=False)[-1] for i in range(n)])
+            g["golden/resample/kld"] = np.array([dyu.kld_error(res, "resample", rstate=rng(50000 + i))[-1] for i in range(n)])
+            for i, args in enumerate(DYN_STOP):
+                flag, vals = dys.stopping_function(res, dict(args, n_mc=0), return_vals=True)
+                g[f"golden/stop/{i}"] = np.array(vals + (float(flag),))
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(g), "arrays,", os.path.getsize(out), "bytes")
+
+
 def _ell_hp_one(key):
     import ell_hp_ref
     return key, ell_hp_ref.case_record(key)
@@ -911,5 +972,7 @@ if __name__ == "__main__":
         gen_merge_errors(os.path.join(gdir, "merge_errors.npz"), os.path.join(gdir, "merge.npz"))
     if "merge_bootstrap" in which:  # not in the default list; reads merge.npz, which stays as it is
         gen_merge_bootstrap(os.path.join(gdir, "merge_bootstrap.npz"), os.path.join(gdir, "merge.npz"))
+    if "merge_dynamic" in which:  # not in the default list; reads merge.npz, which stays as it is
+        gen_merge_dynamic(os.path.join(gdir, "merge_dynamic.npz"), os.path.join(gdir, "merge.npz"))
     if "livesets" in which:  # not in the default list: two partial reference runs (minutes)
         gen_livesets(os.path.join(gdir, "livesets.npz"))

@@ -17,12 +17,17 @@ and `bootstrap_over_realization`: one bootstrap without means over one realizati
 alone (nboot = 1 over nreal = 1), which is how a bootstrap is always computed (M' differs between bootstraps);
 `bootstrap_over_batched_realization`: per bootstrap of 64 over per realization of 64, where the realizations share
 their loads in tiles of 4.
+With --dynamic the run-level analysis of DESIGN section 3.8.4 in place of the lists above (the synthetic runs carry slot
+ids): kld_realizations(256) beside logz_realizations(256) without means, kld_realizations(64) of both bootstrap modes
+beside bootstrap_realizations(64), kld_error(), weight_function() without and with its three weight arrays; and the route
+weight_function replaces: the download of logl, logz, logvol, logwt and samples_n plus the NumPy form.
 One JSON line at the end.  `f64_fraction_*`: the fp64 vector instructions of a call over the chip's measured rate
 (58.7 TFLOP/s = 29.35e12 v_fma_f64 lanes per second), with the instructions per point and realization
 counted in the kernels' code on the jitter path (me_step_sums 93, me_integrate 287: all v_*_f64 of the unrolled 8-point
 body / 8; with means 32 more, the mean sums' v_fma_f64 per point over a tile of 32 columns).
 
     python tools/merged_errors.py [--runs 64] [--reps 5] [--host-real 8] [--device-only] [--synthetic] [--bootstrap]
+                                    [--dynamic]
 """
 import argparse
 import json
@@ -65,6 +70,7 @@ def main():
     ap.add_argument("--niter", type=int, default=83438)
     ap.add_argument("--bootstrap", action="store_true", help="time the strand bootstrap too")
     ap.add_argument("--host-boot", type=int, default=2, help="bootstraps of the NumPy form per repetition")
+    ap.add_argument("--dynamic", action="store_true", help="time the divergence and the weight function instead")
     a = ap.parse_args()
     import inputs
     from dynesty_amd import _lib, backend, ensemble
@@ -74,7 +80,7 @@ def main():
     if a.synthetic:
         import merge_cases
         args = merge_cases.make(np.random.default_rng(1), [a.niter] * a.runs, a.nlive, prob.ndim)
-        pt = {k: args[k] for k in ("dead_id", "dead_it", "dead_nc", "live_it")} if a.bootstrap else {}
+        pt = {k: args[k] for k in ("dead_id", "dead_it", "dead_nc", "live_it")} if a.bootstrap or a.dynamic else {}
         d = ctx.merge_runs(prob, args["niter"], args["dead_logl"], args["live_logl"], args["dead_u"], args["live_u"], **pt)
         del args
     else:
@@ -82,6 +88,8 @@ def main():
     M, D = d.niter, prob.ndim
     rng = np.random.default_rng(2)
     logp_new = d.field("logl") + 0.3 * rng.standard_normal(M)
+    if a.dynamic:
+        return dynamic(a, ctx, d)
     dev = {}
     for n in (1, 64, 256):
         dev[f"realize_{n}"] = lambda n=n: d.logz_realizations(n, seed=1)
@@ -168,6 +176,50 @@ def main():
     lz = res["realize_256"]["logz"]
     out["logz_mean_sd_256"] = [float(lz.mean()), float(lz.std(ddof=1))]
     out["summary"] = dict(logz=d.summary["logz"], logzerr=d.summary["logzerr"])
+    d.release()
+    print(json.dumps(out))
+
+
+def dynamic(a, ctx, d):
+    from dynesty_amd import ensemble
+    dev = dict(realize_256=lambda: d.logz_realizations(256, seed=1), kld_256=lambda: d.kld_realizations(256, seed=1),
+               bootstrap_64=lambda: d.bootstrap_realizations(64, seed=1),
+               kld_64_resample=lambda: d.kld_realizations(64, seed=1, error="resample"),
+               bootstrap_64_jitter=lambda: d.bootstrap_realizations(64, seed=1, jitter=True),
+               kld_64_simulate=lambda: d.kld_realizations(64, seed=1, error="simulate"),
+               kld_error=lambda: d.kld_error(seed=1, index=0), weight_function=lambda: d.weight_function(),
+               weight_function_weights=lambda: d.weight_function(return_weights=True))
+    t = {f"device_{k}": [] for k in dev}
+    t.update(download_weight_function=[], host_weight_function=[])
+    res = {}
+    for rep in range(a.reps + 1):
+        for k, fn in dev.items():
+            ctx.sync()
+            dt, res[k] = timed(fn)
+            if rep:
+                t[f"device_{k}"].append(dt)
+        if a.device_only or rep == 0:
+            continue
+        dt, f = timed(lambda: {k: d.field(k) for k in ("logl", "logz", "logvol", "logwt", "samples_n")})
+        t["download_weight_function"].append(dt)
+        host = ensemble.MergedRun(niter=d.niter, **f)
+        dt, res["host_wf"] = timed(lambda: host.weight_function())
+        t["host_weight_function"].append(dt)
+    out = dict(runs=a.runs, nlive=a.nlive, points=d.niter, reps=a.reps, synthetic=bool(a.synthetic), dynamic=True)
+    for k, v in t.items():
+        if v:
+            out[k + "_s"] = stat(v)
+    med = lambda k: out[f"device_{k}_s"]["median"]  # noqa: E731
+    out["kld_256_over_realize_256"] = med("kld_256") / med("realize_256")
+    out["kld_64_resample_over_bootstrap_64"] = med("kld_64_resample") / med("bootstrap_64")
+    out["kld_64_simulate_over_bootstrap_64_jitter"] = med("kld_64_simulate") / med("bootstrap_64_jitter")
+    if "host_wf" in res:
+        assert res["host_wf"] == res["weight_function"], (res["host_wf"], res["weight_function"])
+        out["host_route_over_device_weight_function"] = (out["download_weight_function_s"]["median"] +
+                                                          out["host_weight_function_s"]["median"]) / med("weight_function")
+    k = res["kld_256"]["kld"]
+    out["kld_mean_sd_256"] = [float(k.mean()), float(k.std(ddof=1))]
+    out["logl_bounds"] = [float(x) for x in res["weight_function"]]
     d.release()
     print(json.dumps(out))
 
