@@ -35,6 +35,9 @@ using namespace dh;
 namespace {
 
 constexpr int kT = 256;
+// Phase B of ns_consume sums a fill's weights relative to M, the largest of them: a ln Z_e more than this far below M
+// is lost to it (exp underflows at -745; the margin keeps every term that matters to H_e in the normal range)
+constexpr double kNsUnder = 600.0;
 enum : int { MODE_CUBE = 0, MODE_BOUND = 1, MODE_DONE = 2, MODE_FAILED = 3, MODE_WAIT = 4 /* run_mode only: sits this fill out */ };
 
 struct NsRun {
@@ -153,7 +156,8 @@ __device__ __forceinline__ double logaddexp_dev(double x, double y) {
   return x + y;
 }
 
-// progress_integration (utils.py:1470-1492), one dead point
+// progress_integration (utils.py:1470-1492), one dead point.  ns_consume's phase B does not run it (see there) except
+// for var[ln Z] of a fill with a plateau death whose ln Z_e is out of its linear sums' reach (kNsUnder).
 __device__ __forceinline__ void integrate_step(double& logz, double& h, double& logzvar, double lprev,
                                                double lnew, double logvol, double dlv) {
   const double logdvol = logvol + log(0.5 * expm1(dlv));
@@ -697,8 +701,9 @@ __host__ __device__ inline size_t ns_consume_lds(int N, int K) {
 // The serial part of the queue consumption (sampler.py:741-776), run by wave 0: stale test, death record,
 // replacement.  The live points are NOT kept in a priority queue: the run's slots are sorted once per fill by
 // (log-likelihood, slot) -- `sidx` -- and the worst live point is then either the next unconsumed entry of that order
-// or the smallest of the replacements made during this fill.  Of those only the ones below theta = the K-th smallest
-// original value can ever become the worst point within K deaths (K originals stand before any other), so they are
+// or the smallest of the replacements made during this fill.  Of those only the ones that stand before the original at
+// sorted position K (value theta; by value, then by slot: a replacement that equals theta in a lower slot does) can
+// ever become the worst point within K deaths (K + 1 originals stand before any other), so they are
 // the only ones kept, unsorted, in a buffer B whose minimum is re-scanned by the wave when it is consumed.  A step is
 // a few LDS words instead of two sift levels of a 64-ary heap (1 950 cycles).  Ties die lowest slot first, as the
 // reference's np.argmin picks them (sampler.py:1107).  Returns the number of deaths (wave-uniform); *newmin = the
@@ -715,7 +720,9 @@ __device__ __forceinline__ int consume_sorted(const double* skey, const unsigned
                                               double* newmin, int lane) {
   int ndead = 0, ptr = 0, nb = 0, bpos = -1;
   *jcap = -1;
+  // (theta with its slot: a replacement that EQUALS theta in a lower slot stands before that original too)
   const double theta = K < N ? skey[sidx[K]] : INFINITY;
+  const int theta_slot = K < N ? (int)sidx[K] : 0x7fffffff;
   // The queue and the sorted order are walked through registers: every lane holds one of the next 64 entries, the
   // current one comes by readlane (the index is wave-uniform) -- no LDS round trip on the serial chain.
   auto lane_d = [](double v, int l) {
@@ -792,13 +799,13 @@ __device__ __forceinline__ int consume_sorted(const double* skey, const unsigned
       dslot[ndead] = s;
       dsrc[ndead] = from;
       src[s] = j;
-      if (lj < theta) {  // may become the worst point again within this fill
+      if (key_before(lj, s, theta, theta_slot)) {  // may become the worst point again within this fill
         bkey[nb] = lj;
         bslot[nb] = s;
         bsrc[nb] = j;
       }
     }
-    if (lj < theta) {
+    if (key_before(lj, s, theta, theta_slot)) {
       if (nb == 0 || key_before(lj, s, bmin, bminslot)) {
         bmin = lj;
         bminslot = s;
@@ -1457,7 +1464,10 @@ __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
       // (compact: no death value exceeds the threshold, and the points left out are not below it)
       if (t == 0 && x == sel_v) ntail += sel_extra;
     }
-    if (t == 0) pl_int[2] = 0;
+    if (t == 0) {
+      pl_int[2] = 0;
+      pl_int[3] = 0;
+    }
     __syncthreads();
     if (ntail) atomicAdd(&pl_int[2], ntail);
     __syncthreads();
@@ -1663,12 +1673,14 @@ __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
     const double w0 = exp(logz0 - logz_E);
     const double g0 = w0 > 0.0 ? w0 * (h0 + logz0) : 0.0;
     double pbefore = ex, lzbefore = pz;
+    int under = 0;
 #pragma unroll
     for (int i = 0; i < kEPT; ++i) {
       const int e = t * EPT + i;
       if (i < EPT && e <= E) {
         const double delta = cd[i] - dlv;
         if (delta != 0.0) {
+          if (lw[i] < M - kNsUnder || (e > 0 && lzbefore < M - kNsUnder)) under = 1;
           const double hprev = e == 0 ? h0 : exp(logz_E - lzbefore) * (g0 + pbefore) - lzbefore;
           const double he = exp(logz_E - lw[i]) * (g0 + pbefore + tt[i]) - lw[i];
           corr += (he - hprev) * delta;
@@ -1677,6 +1689,35 @@ __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
         }
         pbefore += tt[i];
         lzbefore = lw[i];
+      }
+    }
+    // A plateau far below the values the same fill goes on to (a penalty floor outside the likelihood's support, with
+    // the first points of the support behind it): relative to M its deaths' weights are 0, ln Z_e = -inf and P_e = 0,
+    // and H_e above is inf * 0 + inf.  ln Z_E and H_E do not feel it (those deaths' share of them is below rounding),
+    // only the correction does: such a fill takes its var[ln Z] from the recurrence itself, death by death.
+    if (__syncthreads_or(under)) {
+      corr = 0.0;
+      if (t == 0) {
+        double sz = logz0, sh = h0, sv = 0.0, slv = logvol0, lprev = dead_prev0;
+        int jrun = 0, mrun = 0;
+        for (int e = 0; e <= E; ++e) {
+          double st;
+          if (e < pc0) {
+            st = -log1p(-rho0 / (1.0 - (double)e * rho0));
+          } else {
+            if (e == pc0 || dcur[e] != dcur[e - 1]) {
+              run_info(e, jrun, mrun);
+            } else {
+              ++jrun;
+            }
+            st = mrun > 1 ? -log1p(-1.0 / ((double)N + 2.0 - (double)jrun)) : dlv;
+          }
+          slv -= st;
+          integrate_step(sz, sh, sv, lprev, dcur[e], slv, st);
+          lprev = dcur[e];
+        }
+        pl_dbl[1] = sv;
+        pl_int[3] = 1;
       }
     }
   }
@@ -1718,6 +1759,7 @@ __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
     if (nkeep > 0) {
       const double w = exp(logz0 - logz_E);
       const double h_E = hsum + (w > 0.0 ? w * (h0 + logz0) : 0.0) - logz_E;
+      const double logzvar0 = r.logzvar;
       r.logzvar += (h_E - h0) * dlv;
       r.h = h_E;
       r.logz = logz_E;
@@ -1731,6 +1773,7 @@ __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
         r.var_a = (w > 0.0 ? r.var_a * w : 0.0) + (sred[1][0] + sred[1][1] + sred[1][2] + sred[1][3]);
         r.var_b = (w > 0.0 ? r.var_b * w : 0.0) + (sred[2][0] + sred[2][1] + sred[2][2] + sred[2][3]);
       }
+      if (has_tie && pl_int[3]) r.logzvar = logzvar0 + pl_dbl[1];  // (the recurrence's own sum, see kNsUnder)
       if (has_tie) {
         r.pcount = pl_int[0];
         r.plogdvol = pl_dbl[0];

@@ -69,12 +69,14 @@ def consume_queue(live_logl, queue_logl, queue_ncalls, state, dlogz, plateau=Tru
     queue entries popped).  With live_it ((N,) ints, modified in place: iteration at which the
     point in each slot was proposed, ref: sampler.py:1107, 1182 -- self.it starts at 1, :396) also
     dead_it ('it' of saved_run) and dead_nc ('nc': the calls of every entry popped for that
-    iteration, ref: sampler.py:1141-1142, 1176); nc_carry = calls popped after the last death."""
+    iteration, ref: sampler.py:1141-1142, 1176); nc_carry = calls popped after the last death.  dead_dlv: the
+    -d ln X every death took (the constant step or the plateau's), dead_pl: the plateau's ln volume step (plateau_logdvol)
+    for a death inside a plateau, nan otherwise."""
     live_logl = np.asarray(live_logl)
     K = len(queue_logl)
     s = state
     dead_logl, dead_slot, dead_src = [], [], []
-    dead_it, dead_nc = [], []
+    dead_it, dead_nc, dead_dlv, dead_pl = [], [], [], []
     nc = 0
     j = 0
     stopped = False
@@ -107,6 +109,8 @@ def consume_queue(live_logl, queue_logl, queue_ncalls, state, dlogz, plateau=Tru
             cur_dlv = s.dlv
         else:
             cur_dlv = -np.log1p(-np.exp(s.plateau_logdvol - s.logvol))  # ref: sampler.py:1125
+        dead_dlv.append(float(cur_dlv))
+        dead_pl.append(float(s.plateau_logdvol) if s.plateau_mode else math.nan)
         s.logvol -= cur_dlv  # ref: sampler.py:1129
         _, s.logz, s.logzvar, s.h = progress_integration(s.loglstar, loglstar_new, s.logz, s.logzvar,
                                                          s.logvol, cur_dlv, s.h)
@@ -127,7 +131,8 @@ def consume_queue(live_logl, queue_logl, queue_ncalls, state, dlogz, plateau=Tru
                 s.plateau_mode = False
     return dict(dead_logl=np.array(dead_logl), dead_slot=np.array(dead_slot, dtype=np.int64),
                 dead_src=np.array(dead_src, dtype=np.int64), stopped=stopped, used=j,
-                dead_it=np.array(dead_it, dtype=np.int64), dead_nc=np.array(dead_nc, dtype=np.int64), nc_carry=nc)
+                dead_it=np.array(dead_it, dtype=np.int64), dead_nc=np.array(dead_nc, dtype=np.int64), nc_carry=nc,
+                dead_dlv=np.array(dead_dlv, dtype=np.float64), dead_pl=np.array(dead_pl, dtype=np.float64))
 
 
 def add_live_points(live_logl, state):

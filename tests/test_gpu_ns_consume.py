@@ -7,6 +7,7 @@ real NestedSampler run: tests/test_oracle_nsloop_golden.py):
   * chains of synthetic fills over several runs vs oracle.consume_queue (incl. the dlogz stop)
   * a whole device run: the reported ln Z, error and information equal compute_integrals
     (what the reference's Results holds) over the run's own dead + live log-likelihoods to 1e-9
+All of it on log-likelihoods in about [-20, 0]; other value scales (offsets, floors, wide ranges): tests/test_gpu_ns_hp.py.
 """
 import os
 

@@ -928,10 +928,36 @@ def gen_proposal_hp(out):
     print("wrote", out, len(skeys), "one-step sets,", len(ekeys), "constructed sets,", len(ckeys), "chains,", len(g), "arrays")
 
 
+def _ns_hp_one(key):
+    import ns_hp_ref
+    return ns_hp_ref.golden_record(key)
+
+
+def gen_ns_hp(out):
+    """High-precision results (mpmath, 50 digits) of the run loop's evidence integration on the seeded fill chains of
+    tests/ns_cases.py (tests/test_ns_hp_cpu.py, tests/test_gpu_ns_hp.py): ln X, ln Z, H and var ln Z after every fill,
+    and where the `stop` cases stop.  Nothing of the reference project is involved: the reference here is
+    tests/ns_hp_ref.py.  Outputs only -- the inputs are regenerated from their seeds.  A few seconds on 16 processors."""
+    import multiprocessing
+    import ns_cases
+    keys = ns_cases.all_keys()
+    g = {}
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        for rec in pool.imap_unordered(_ns_hp_one, keys, chunksize=1):
+            g.update(rec)
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(keys), "cases,", len(g), "arrays,", os.path.getsize(out), "bytes")
+
+
 if __name__ == "__main__":
     gdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(gdir, exist_ok=True)
     which = sys.argv[1:] or ["bounding", "proposals", "rng", "runs", "friends", "wide", "nsloop"]
+    if "ns_hp" in which:  # not in the default list; needs no reference project (tests/ns_hp_ref.py is the reference)
+        gen_ns_hp(os.path.join(gdir, "ns_hp.npz"))
+        which = [w for w in which if w != "ns_hp"]
+        if not which:
+            sys.exit(0)
     if "proposal_hp" in which:  # not in the default list; needs no reference project (tests/proposal_hp_ref.py)
         gen_proposal_hp(os.path.join(gdir, "proposal_hp.npz"))
         which = [w for w in which if w != "proposal_hp"]
