@@ -518,6 +518,11 @@ __device__ __forceinline__ uint32_t sel_mask(uint64_t mask, uint32_t if_set, uin
   asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(if_clear), "v"(if_set), "s"(mask));
   return r;
 }
+// lane l takes lane l + 1's value, lane 63 keeps its own: v_mov_b32_dpp wave_shl:1 -- a vector move, where
+// __shfl_down is a ds_bpermute_b32 and a wait for the LDS on the round's dependent chain
+__device__ __forceinline__ uint32_t next_lane32(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
+}
 __device__ __forceinline__ uint32_t lo32(double x) { return (uint32_t)__double_as_longlong(x); }
 __device__ __forceinline__ uint32_t hi32(double x) { return (uint32_t)((uint64_t)__double_as_longlong(x) >> 32); }
 struct FrontOut {
@@ -550,6 +555,18 @@ __device__ __forceinline__ FrontOut itemgen_front(const Limbs128& G, const uint3
   o.rlo = sw ? rb : ra;
   o.rhi = sw ? ra : rb;
   return o;
+}
+// how many positions below the lane's yield an item (`dead`: the positions that yield none)
+__device__ __forceinline__ int item_offset(int lane, uint64_t dead) {
+  return lane - (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
+}
+// a round's items out: the lanes of `items` store their normal, or where umask says so the uniform's 53 random bits
+// (r >> 11: formed in every lane and selected, as in the common round), at out[off]: one store under one exec mask
+__device__ __forceinline__ void store_items(double* out, uint32_t off, uint64_t items, uint64_t umask, uint32_t rlo, uint32_t rhi,
+                                            double x) {
+  const uint32_t ulo = __builtin_amdgcn_alignbit(rhi, rlo, 11), uhi = rhi >> 11;
+  const uint64_t item = ((uint64_t)sel_mask(umask, uhi, hi32(x)) << 32) | sel_mask(umask, ulo, lo32(x));
+  if (__builtin_amdgcn_inverse_ballot_w64(items)) out[off] = __longlong_as_double((long long)item);
 }
 // d = S_1 - S_0 of two wave-uniform states (limbs): a scalar borrow chain
 __device__ __forceinline__ void sub128_limbs(const uint32_t (&A)[4], const uint32_t (&B)[4], uint32_t (&R)[4]) {
@@ -655,6 +672,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))
       uint32_t rlo, rhi, rabs_lo;
       int idx;
       double x;
+      float2 ff;
       uint64_t missmask, umask, m;
       // The common round (about one in two) is a loop of its own: no candidate missed and the walker needs all 63
       // positions -- lane p stores item W + p, the new S_0 / S_1 are the states of lanes 62 and 63; sixteen scalar
@@ -711,9 +729,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))
         const uint64_t rabs = ((uint64_t)rabs_hi << 32) | rabs_lo;
         const double rd = __longlong_as_double((long long)(((uint64_t)(rabs_hi | 0x43300000u) << 32) | rabs_lo)) - 4503599627370496.0;
         const ulonglong2 kw = z->kw[idx];
+        // the wedge test's pair rides behind kw in the same trip to the LDS (one more read in every round; read where
+        // the resolution needs it, it was a second dependent round trip in six rounds of ten)
+        ff = z->ff[idx];
         x = rd * __longlong_as_double((long long)kw.y);
         x = __longlong_as_double(__double_as_longlong(x) ^ (long long)((uint64_t)((rlo << 23) & 0x80000000u) << 32));
         missmask = __ballot(!(rabs < kw.x)) & 0x7fffffffffffffffull;  // position 63 is never consumed
+        asm volatile("" : "+v"(ff.x), "+v"(ff.y));  // (read here: not to be sunk into the resolution)
         const int c = (int)(W - (uint32_t)(((uint64_t)W * magic_n1) >> 32) * (uint32_t)n1);
         umask = U0 << (n - c);
         m = missmask & ~umask;
@@ -739,14 +761,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))
       uint64_t dead = 0;
       int endpos = 63, tailf = -1;
       if (m) {  // (the same resolution as wavegen_round's)
-        const float2 ff = z->ff[idx];
-        const uint32_t nhi = (uint32_t)__shfl_down((int)(rhi >> 8), 1);  // (r >> 40) of the next position
+        const uint32_t nhi = next_lane32(rhi >> 8);  // (r >> 40) of the next position; lane 63 never asks
         const float xf = (float)x;
         const float lhs = ff.x * ((float)nhi * 5.9604644775390625e-08f) + ff.y;
         const float ef = __expf(-0.5f * xf * xf);
         uint64_t accmask = __ballot(lhs < ef);
         const uint64_t zeromask = __ballot(idx == 0);
-        if (__ballot(fabsf(lhs - ef) <= 1e-5f) & m) {
+        uint64_t band = __ballot(fabsf(lhs - ef) <= 1e-5f) & m;
+        asm volatile("" : "+s"(band));  // (a test and a branch of its own: see below)
+        if (band != 0) {
           if (!have64) {
             uint32_t D2[4] = {Dv[0], Dv[1], Dv[2], Dv[3]};
             asm volatile("" : "+v"(D2[0]), "+v"(D2[1]), "+v"(D2[2]), "+v"(D2[3]));  // (a front of its own: not to be merged with the round's)
@@ -768,8 +791,45 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))
           }
           accmask = acc64;
           have64 = false;
+          // (keeps this a block of its own: folded into selects on the flag, it cost every general round eight scalar instructions)
+          asm volatile("" : "+s"(accmask));
         }
-        do {
+        // Two general rounds in three end after one miss that is neither the tail nor position 62: the loop's first
+        // turn in a straight line (one test for both special cases, which are left to the loop).  Where no miss is left
+        // behind it and the walker needs all of the round, the round ends here: all 63 positions are consumed, so the
+        // new S_0 / S_1 are the states of lanes 62 and 63 as in the common round -- lane numbers that do not wait for
+        // the resolution -- and the items are 61 + acc.  What this buys is the scalar control flow it leaves out, not
+        // its instructions: the resolution sits on the round's dependent chain (EXPERIMENTS.md, "itemgen: missed
+        // candidates").
+        {
+          const int f = (int)__ffsll((long long)m) - 1;
+          uint32_t special = (uint32_t)((zeromask | (1ull << 62)) >> f) & 1u;
+          asm volatile("" : "+s"(special));  // (compared as an integer: s_cmp + s_cbranch_scc, no detour through vcc)
+          if (special == 0) {
+            const uint64_t acc = (accmask >> f) & 1ull;
+            dead = (2ull | (acc ^ 1ull)) << f;
+            const int keep = f + 2;
+            const uint64_t low = umask & ((1ull << keep) - 1ull);
+            umask = low | ((umask >> (f + (int)acc)) << keep);
+            m = missmask & ~umask & (~0ull << keep);
+            if (m == 0) {
+              asm volatile("" : "+s"(W));  // (two tests, two branches: merged, they take a detour through vcc)
+              if ((int)W < Tfast) {
+                store_items(out, W + (uint32_t)item_offset(lane, dead), ~dead & 0x7fffffffffffffffull, umask, rlo, rhi, x);
+                uint32_t S1v[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                  S0v[q] = rl32(fr.st[q], 62);
+                  S1v[q] = rl32(fr.st[q], 63);
+                }
+                sub128_limbs(S1v, S0v, Dv);
+                W += 61u + (uint32_t)acc;
+                continue;
+              }
+            }
+          }
+        }
+        while (m) {
           const int f = (int)__ffsll((long long)m) - 1;
           if ((zeromask >> f) & 1ull) {
             tailf = f;
@@ -786,24 +846,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))
           const uint64_t low = umask & ((1ull << keep) - 1ull);
           umask = low | ((umask >> (f + (int)acc)) << keep);
           m = missmask & ~umask & (~0ull << keep);
-        } while (m);
+        }
       }
-      const int off = lane - (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32),
-                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
+      const int off = item_offset(lane, dead);
       int total = endpos - (int)__popcll(dead);
       const int need = T - (int)W;
-      const bool alive = !__builtin_amdgcn_inverse_ballot_w64(dead);
       if (total >= need) {
-        const uint64_t b = __ballot(alive && off == need - 1);
+        const uint64_t b = __ballot(!__builtin_amdgcn_inverse_ballot_w64(dead) && off == need - 1);
         endpos = (int)__ffsll((long long)b);
         total = need;
         tailf = -1;
       }
-      if (alive && off < total) {
-        // a step's uniform travels as its 53 random bits (r >> 11)
-        const uint64_t ubits = ((uint64_t)(rhi >> 11) << 32) | __builtin_amdgcn_alignbit(rhi, rlo, 11);
-        out[W + off] = __builtin_amdgcn_inverse_ballot_w64(umask) ? __longlong_as_double((long long)ubits) : x;
-      }
+      // the round's items are the positions below endpos that are not dead (the dead ones all lie below endpos): a scalar mask
+      store_items(out, W + (uint32_t)off, ~dead & ((1ull << endpos) - 1ull), umask, rlo, rhi, x);
       if (tailf >= 0) {
         const uint64_t sthi = ((uint64_t)rl32(fr.st[3], tailf) << 32) | rl32(fr.st[2], tailf),
                        stlo = ((uint64_t)rl32(fr.st[1], tailf) << 32) | rl32(fr.st[0], tailf);
