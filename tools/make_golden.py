@@ -949,10 +949,52 @@ def gen_ns_hp(out):
     print("wrote", out, len(keys), "cases,", len(g), "arrays,", os.path.getsize(out), "bytes")
 
 
+def _split_hp_one(key):
+    import split_hp_ref
+    return key, (split_hp_ref.boot_record(key) if key.startswith("boot/") else split_hp_ref.case_record(key))
+
+
+def gen_split_hp(out):
+    """High-precision results (mpmath, 50 digits; np.longdouble) of MultiEllipsoid.update's split tree on the seeded
+    clouds of tests/split_cases.py (tests/test_split_hp_cpu.py, tests/test_gpu_split_hp.py): the leaf of every point in
+    list order, nnodes, every leaf's ellipsoid record, every k-means node's decisions with margin / bound, and the
+    bootstrap expansion of the replicas.  Nothing of the reference project is involved: the reference here is
+    tests/split_hp_ref.py.  Outputs only -- the inputs are regenerated from their seeds.  Refuses to write a case with
+    an undecidable decision.  A minute on 8 processors."""
+    import multiprocessing
+    import split_cases
+    import split_hp_ref
+    bkeys = [c[0] for c in split_cases.BOOT_CASES]
+    # the long cases first
+    def cost(k):
+        p = k.split("/")[1:] if k.startswith("boot/") else k.split("/")
+        return -int(p[1])**3 * int(p[2])
+    order = sorted(split_cases.KEYS + bkeys, key=cost)
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        records = dict(pool.imap_unordered(_split_hp_one, order, chunksize=1))
+    for k in split_cases.KEYS:
+        r = split_hp_ref.decidability(records[k])
+        print(k, "nells", int(records[k]["head"][0]), "nnodes", int(records[k]["head"][1]), "smallest margin / bound %.3g" % r)
+        assert r > 1, f"{k}: a decision is within its bound of a tie (margin / bound = {r:.3g}): choose another cloud"
+    for k in bkeys:
+        print(k, "n_in", records[k]["nin"], "expand^2", records[k]["q2"], "bound", records[k]["q2b"])
+        assert np.all(records[k]["decid"] > 1), f"{k}: a replica's tree has an undecidable decision"
+    g = {"split/" + n: v for n, v in split_hp_ref.pack_fixture(records, split_cases.KEYS).items()}
+    g.update({"boot/" + n: v for n, v in split_hp_ref.pack_fixture(records, bkeys).items()})
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(split_cases.KEYS), "trees,", len(bkeys), "bootstrap cases,", len(g), "arrays,",
+          os.path.getsize(out), "bytes")
+
+
 if __name__ == "__main__":
     gdir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(gdir, exist_ok=True)
     which = sys.argv[1:] or ["bounding", "proposals", "rng", "runs", "friends", "wide", "nsloop"]
+    if "split_hp" in which:  # not in the default list; needs no reference project (tests/split_hp_ref.py)
+        gen_split_hp(os.path.join(gdir, "split_hp.npz"))
+        which = [w for w in which if w != "split_hp"]
+        if not which:
+            sys.exit(0)
     if "ns_hp" in which:  # not in the default list; needs no reference project (tests/ns_hp_ref.py is the reference)
         gen_ns_hp(os.path.join(gdir, "ns_hp.npz"))
         which = [w for w in which if w != "ns_hp"]
