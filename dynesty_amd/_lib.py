@@ -594,7 +594,7 @@ class Context:
             raise ValueError(self.lib.dh_last_error(self.handle).decode())
         return self._check(rc)
 
-    # -- the combiner on the device (csrc/merge.hip) ---------------------------
+    # -- the combiner on the device (csrc/merge*.hip) --------------------------
     def _merged(self, rc):
         """After a merge call: an argument error touched nothing (an earlier DeviceMergedRun stays valid); anything
         else, success included, replaced or dropped the context's merged run."""

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/dynhip.h"
+#include "merge_plan.h"
 #include "problem.h"
 
 // Walker / candidate state lives in registers, so the per-lane kernels are
@@ -49,16 +50,13 @@ struct dh_kept {
   std::vector<long long> niter;  // per run, from the records
 };
 
-// The merged run of the last dh_merge_runs / dh_merge_kept (merge.hip): one allocation, M points in merged order.
-struct dh_merged {
+// The merged run of the last dh_merge_runs / dh_merge_kept (merge.hip): one allocation, M points in merged order; its
+// arrays are merge_plan.h's MergedArrays, laid out by carve_merged.
+struct dh_merged : dh_merge::MergedArrays {
   char* base = nullptr;
   long long M = 0;
   int ndim = 0, runs = 0, nlive = 0;
   bool have_pt = false;  // id / it / nc were given
-  double *logl = nullptr, *logvol = nullptr, *logwt = nullptr, *logz = nullptr, *logzerr = nullptr, *h = nullptr;
-  double *w = nullptr, *cw = nullptr, *u = nullptr, *v = nullptr;
-  double* mom = nullptr;  // [sum w, sum w^2, ESS, sum w v_0 .. sum w v_{D-1}]
-  int *run = nullptr, *seq = nullptr, *id = nullptr, *it = nullptr, *nc = nullptr, *n = nullptr, *fin = nullptr;
   long long* idx = nullptr;  // indices of the last dh_merged_resample (an allocation of its own, grow-only)
   long long idx_cap = 0, idx_n = 0;
   // the strand bootstrap's tie structure (an allocation of its own, built by the first dh_merged_bootstrap*): the final
@@ -164,6 +162,28 @@ inline T* arena_up(dh_ctx* ctx, const T* host, size_t count) {
       return nullptr;
   }
   return d;
+}
+
+// The arena as one layout (merge_plan.h: a function of a Carver): reset, the size pass, that total reserved and taken
+// in one piece, the pointer pass.  No caller adds up bytes, and what the pointer pass hands out is what was reserved.
+template <class Layout>
+inline int arena_carve(dh_ctx* ctx, Layout&& layout) {
+  arena_reset(ctx);
+  dh_merge::Carver size;
+  layout(size);
+  const int rc = arena_reserve(ctx, size.off);
+  if (rc) return rc;
+  char* base = (char*)arena_get(ctx, size.off);
+  if (!base) return DH_ERR_NOMEM;
+  dh_merge::Carver place{base};
+  layout(place);
+  return DH_OK;
+}
+// host -> an array of such a layout
+template <typename T>
+inline bool arena_fill(dh_ctx* ctx, T* dev, const T* host, size_t count) {
+  if (!host || !count) return true;
+  return hip_ok(ctx, hipMemcpyAsync(dev, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream), "H2D");
 }
 
 template <typename T>

@@ -1,0 +1,370 @@
+// Internal: what the combiner's entry points launch and where their scratch lies (merge.hip, merge_marginals.hip,
+// merge_errors.hip), as plain host arithmetic.
+//
+// The constants the sizes depend on, the launch arithmetic as functions of the shape alone, and one layout per scratch
+// user: THE list of that user's arrays -- element type, element count, wanted or not --, written once and walked twice
+// by a Carver, first without a base for the total, then with the block for the addresses (arena_carve of ctx.h,
+// device_carve of merge_dev.h).  Nothing here touches the device, so a host program holds it to its invariants
+// (tests/test_merge_plan_cpu.py).  Plain C++17: no HIP include.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace dh_merge {
+
+constexpr int kT = 256;
+constexpr int kItems = 8;              // consecutive points per thread of a scan
+constexpr int kChunk = kT * kItems;    // points per workgroup of a scan
+constexpr int kLiveTile = 1024;        // live keys staged in LDS per step of the rank sort
+constexpr long long kMomChunk = 2048;  // points per workgroup of the moment sums (at least)
+constexpr size_t kScanElem = 16;       // the widest element of a scan's chunk aggregates (LsePair, Pair2L)
+
+constexpr int kMT = 1024;         // threads per workgroup of the passes over the rows
+constexpr int kSelTile = 78;      // 256-bin histograms of u64 per workgroup: 156 KB + their states of the CU's 160 KB
+constexpr int kHistBins = 16384;  // 64-bit histogram bins per workgroup: 128 KB
+constexpr int kMaxCols = 512;     // requested columns per call (the staging tables of the passes)
+constexpr int kDigits = 12;       // 8 digits of the value's 64-bit image, 4 of the 32-bit point index
+
+constexpr int kRealTile = 4;         // realizations a workgroup carries through its chunk
+constexpr int kRealLaunch = 64;      // realizations per set of launches: the scratch is chunks x 64 x (6 + D) doubles
+constexpr int kRealMax = 65536;      // realizations per call
+constexpr int kSeg = kChunk / kT;    // a chunk's mean sums: kSeg segments of kT points, summed in segment order
+constexpr int kColTile = kT / kSeg;  // columns per step of the mean sums
+constexpr int kPart = 5;             // per (realization, chunk): max ln w, max ln w without logrwt, sum w, sum w^2, sum of H's terms
+constexpr int kBootMax = 65536;      // bootstraps per call
+
+// ---- launch arithmetic ----------------------------------------------------------------------------------------------
+
+inline unsigned blocks_for(size_t n, size_t per) { return (unsigned)((n + per - 1) / per); }
+
+// the moment sums: chunks of *chunk points, at most 1024 of them
+inline int moment_chunks(long long M, size_t cols, long long* chunk) {
+  long long n = (M + kMomChunk - 1) / kMomChunk;
+  const long long cap = (long long)(((size_t)8 << 20) / (cols ? cols : 1));  // at most 64 MB of partial sums
+  if (n > 1024) n = 1024;
+  if (n > cap) n = cap;
+  if (n < 1) n = 1;
+  *chunk = (M + n - 1) / n;
+  return (int)((M + *chunk - 1) / *chunk);
+}
+
+// rows per workgroup: at least 256, at most 2048 workgroups
+inline long long rows_per_group(long long M, unsigned* groups) {
+  long long rows = (M + 2047) / 2048;
+  if (rows < 256) rows = 256;
+  *groups = (unsigned)((M + rows - 1) / rows);
+  return rows;
+}
+
+// the quantile's tile over the requested columns: cpt columns (cpt * nq <= kSelTile selections) per step
+struct QuantTile {
+  int cpt;
+  size_t lds_digit, lds_succ;  // mq_pass<false, .> (256 bins per selection) and mq_pass<true, .> (one)
+  bool combine;                // 64 / columns lanes of a wavefront share a column
+};
+inline QuantTile quantile_tile(int nq, int ncol) {
+  QuantTile t;
+  t.cpt = kSelTile / nq;
+  const int tile_cols = t.cpt < ncol ? t.cpt : ncol, tile_sel = tile_cols * nq;
+  t.lds_digit = (size_t)tile_sel * (256 * 8 + 16) + (size_t)tile_cols * 4;
+  t.lds_succ = (size_t)tile_sel * (8 + 16) + (size_t)tile_cols * 4;
+  t.combine = tile_cols < 16;
+  return t;
+}
+
+// the histograms: tables of nb bins per tile of the workgroup's LDS, and that LDS for n tables
+inline int hist_per(size_t nb) {
+  const int per = (int)((size_t)kHistBins / nb);
+  return per > 1024 ? 1024 : per;  // (rows x tables of a tile are walked with a 32-bit index)
+}
+inline size_t hist_lds(int per, int n, size_t nb) { return (size_t)(per < n ? per : n) * nb * 8; }
+
+// me_integrate: the scans' 2 kT Trip; with means kRealTile x kChunk weights and kSeg x kRealTile x kColTile partial sums
+inline size_t integrate_lds(bool want_mean) {
+  return (size_t)(2 * kT * 3 + (want_mean ? kRealTile * kChunk + kSeg * kRealTile * kColTile : 0)) * 8;
+}
+
+// realizations a set of launches carries: the batch's scratch is sized for that many
+inline size_t real_tile(int nreal) { return (size_t)(nreal < kRealLaunch ? nreal : kRealLaunch); }
+
+// expanded positions the bootstrap's buffer is carved for: before the first M' is known, and for an M' beyond that
+inline size_t boot_cap_first(size_t M) { return M + M / 4 + kChunk; }
+inline size_t boot_cap_regrown(size_t Mx) { return Mx + Mx / 4 + kChunk; }
+
+// ---- layouts --------------------------------------------------------------------------------------------------------
+
+// One array of a walk, for the host test.
+struct Slot {
+  const char* name;
+  size_t off, bytes;  // bytes == 0: not wanted -- no room, a null pointer
+  bool null;
+};
+
+// Hands out consecutive 256-byte aligned arrays of a block; without a base it only adds up.
+struct Carver {
+  char* base = nullptr;
+  size_t off = 0;
+  Slot* log = nullptr;  // where the host test has the walk written down
+  int nlog = 0;
+  template <class T>
+  void operator()(T*& p, const char* name, size_t count, bool wanted = true) {
+    p = nullptr;
+    const size_t bytes = wanted ? count * sizeof(T) : 0;
+    if (wanted && base) p = (T*)(base + off);
+    if (log) log[nlog++] = Slot{name, off, bytes, p == nullptr};
+    off += (bytes + 255) & ~(size_t)255;
+  }
+};
+
+typedef unsigned long long u64;
+
+// the merged run: dh_merged's pointer block (ctx.h), M points in merged order
+struct MergedArrays {
+  double *logl = nullptr, *logvol = nullptr, *logwt = nullptr, *logz = nullptr, *logzerr = nullptr, *h = nullptr;
+  double *w = nullptr, *cw = nullptr, *u = nullptr, *v = nullptr;
+  double* mom = nullptr;  // [sum w, sum w^2, ESS, sum w v_0 .. sum w v_{D-1}]
+  int *run = nullptr, *seq = nullptr, *id = nullptr, *it = nullptr, *nc = nullptr, *n = nullptr, *fin = nullptr;
+};
+inline void carve_merged(Carver& c, MergedArrays& m, size_t M, size_t D, bool pt) {
+  c(m.logl, "logl", M);
+  c(m.logvol, "logvol", M);
+  c(m.logwt, "logwt", M);
+  c(m.logz, "logz", M);
+  c(m.logzerr, "logzerr", M);
+  c(m.h, "h", M);
+  c(m.w, "w", M);
+  c(m.cw, "cw", M);
+  c(m.u, "u", M * D);
+  c(m.v, "v", M * D);
+  c(m.mom, "mom", 3 + D);
+  c(m.run, "run", M);
+  c(m.seq, "seq", M);
+  c(m.n, "n", M);
+  c(m.fin, "fin", M);
+  c(m.id, "id", M, pt);
+  c(m.it, "it", M, pt);
+  c(m.nc, "nc", M, pt);
+}
+
+// the merge's scratch, freed when the merge returns
+struct MergeScratch {
+  long long *off, *nit, *src_row;
+  double *seq_l, *key_b, *step, *logdvol, *eval_l, *mom_part, *last, *summ;
+  int *seq_run, *org_a, *org_b, *live_slot, *flags;
+  u64* ncall;
+  char* part;  // a scan's chunk aggregates
+};
+inline void carve_scratch(Carver& c, MergeScratch& s, size_t M, size_t R, size_t N, size_t D) {
+  long long chunk;
+  const size_t nchunk = (size_t)moment_chunks((long long)M, D + 2, &chunk);
+  c(s.off, "off", R + 1);
+  c(s.nit, "nit", R);
+  c(s.src_row, "src_row", M);
+  c(s.seq_l, "seq_l", M);
+  c(s.key_b, "key_b", M);
+  c(s.step, "step", M);
+  c(s.logdvol, "logdvol", M);
+  c(s.eval_l, "eval_l", M);
+  c(s.mom_part, "mom_part", nchunk * (D + 2));
+  c(s.last, "last", 1);
+  c(s.summ, "summ", 8);
+  c(s.seq_run, "seq_run", M);
+  c(s.org_a, "org_a", M);
+  c(s.org_b, "org_b", M);
+  c(s.live_slot, "live_slot", R * N);
+  c(s.flags, "flags", 4);
+  c(s.ncall, "ncall", 1);
+  c(s.part, "part", (blocks_for(M, kChunk) + 1) * kScanElem);
+}
+
+// the inputs of dh_merge_runs, staged from the host: rows of S dead points per run (at least one)
+struct MergeStage {
+  double *dead_logl, *live_logl, *dead_u, *live_u;
+  int *dead_id, *dead_it, *dead_nc, *live_it;  // with id / it / nc only
+};
+inline void carve_stage(Carver& c, MergeStage& s, size_t R, size_t N, size_t D, size_t S, bool pt) {
+  c(s.dead_logl, "dead_logl", R * S);
+  c(s.live_logl, "live_logl", R * N);
+  c(s.dead_u, "dead_u", R * S * D);
+  c(s.live_u, "live_u", R * N * D);
+  c(s.dead_id, "dead_id", R * S, pt);
+  c(s.dead_it, "dead_it", R * S, pt);
+  c(s.dead_nc, "dead_nc", R * S, pt);
+  c(s.live_it, "live_it", R * N, pt);
+}
+
+// the covariance: the chunks' sums and their total
+struct CovBuf {
+  double *part, *cov;
+};
+inline void carve_cov(Carver& c, CovBuf& b, size_t M, size_t D) {
+  long long chunk;
+  c(b.part, "part", (size_t)moment_chunks((long long)M, D * D, &chunk) * D * D);
+  c(b.cov, "cov", D * D);
+}
+
+// dh_merged_gather: n rows out, their indices in where the caller names them
+struct GatherBuf {
+  long long* idx;
+  double* out;
+};
+inline void carve_gather(Carver& c, GatherBuf& b, size_t n, size_t D, bool given) {
+  c(b.idx, "idx", n, given);
+  c(b.out, "out", n * D);
+}
+
+// the histograms: n tables of nbx (x nby) bins over ncol = n (1-D) or 2 n (pairs) columns
+struct HistBuf {
+  int* cols;
+  double *xe, *ye;  // n sets of nbx + 1 (nby + 1) edges; ye with pairs only
+  u64* table;
+  double* out;
+};
+inline void carve_hist(Carver& c, HistBuf& b, bool two, size_t n, size_t nbx, size_t nby) {
+  const size_t total = n * (two ? nbx * nby : nbx);
+  c(b.cols, "cols", two ? 2 * n : n);
+  c(b.xe, "xe", n * (nbx + 1));
+  c(b.ye, "ye", n * (nby + 1), two);
+  c(b.table, "table", total);
+  c(b.out, "out", total);
+}
+
+// the quantiles: S = ncol x nq selections.  table | total | cmax | last | flags lie next to each other and are
+// cleared by one memset of zero_bytes from `table`; the kernels initialise the rest themselves.
+struct QuantBuf {
+  double* q;
+  int* cols;
+  u64 *table, *total, *cmax;  // S x 256 bins; the sum of all W; per column slot
+  unsigned* last;             // per column slot
+  int* flags;
+  size_t zero_bytes;
+  u64 *cmin, *pk, *cb, *wk, *ti, *succ;
+  double* frac;
+  unsigned* pi;
+  int* mode;
+  double* out;
+};
+inline void carve_quantile(Carver& c, QuantBuf& b, size_t nq, size_t ncol) {
+  const size_t S = ncol * nq;
+  c(b.q, "q", nq);
+  c(b.cols, "cols", ncol);
+  const size_t zero = c.off;
+  c(b.table, "table", S * 256);
+  c(b.total, "total", 1);
+  c(b.cmax, "cmax", ncol);
+  c(b.last, "last", ncol);
+  c(b.flags, "flags", 4);
+  b.zero_bytes = c.off - zero;
+  c(b.cmin, "cmin", ncol);
+  c(b.pk, "pk", S);
+  c(b.cb, "cb", S);
+  c(b.wk, "wk", S);
+  c(b.ti, "ti", S);
+  c(b.succ, "succ", S);
+  c(b.frac, "frac", S);
+  c(b.pi, "pi", S);
+  c(b.mode, "mode", S);
+  c(b.out, "out", S);
+}
+
+// a batch of realizations: per point lae (and logrwt), per (realization of a launch set, chunk) the sums, per
+// realization of the call its row [logz, h, ess, mean.. | kld]
+struct RealBuf {
+  double *lae, *rwt, *sums, *part, *mpart, *out, *kpart;
+};
+inline void carve_real(Carver& c, RealBuf& b, size_t M, size_t D, int nreal, bool rwt, bool want_mean, bool kld) {
+  const size_t cells = real_tile(nreal) * blocks_for(M, kChunk);
+  c(b.lae, "lae", M);
+  c(b.rwt, "rwt", M, rwt);
+  c(b.sums, "sums", cells);
+  c(b.part, "part", cells * kPart);
+  c(b.mpart, "mpart", cells * D, want_mean);
+  c(b.out, "out", (size_t)nreal * (3 + D));
+  c(b.kpart, "kpart", cells, kld);
+}
+
+// the per-point fields of one realization or bootstrap over n points
+struct FieldArrays {
+  double *step, *logvol, *logwt, *logz, *kld;
+};
+inline void carve_field_arrays(Carver& c, FieldArrays& f, size_t n, bool kld, bool wanted = true) {
+  c(f.step, "step", n, wanted);
+  c(f.logvol, "logvol", n, wanted);
+  c(f.logwt, "logwt", n, wanted);
+  c(f.logz, "logz", n, wanted);
+  c(f.kld, "kld", n, wanted && kld);
+}
+struct FieldBuf {
+  double *lae, *rwt;
+  FieldArrays f;
+  char* part;
+};
+inline void carve_fields(Carver& c, FieldBuf& b, size_t M, bool rwt, bool kld) {
+  c(b.lae, "lae", M);
+  c(b.rwt, "rwt", M, rwt);
+  carve_field_arrays(c, b.f, M, kld);
+  c(b.part, "part", (blocks_for(M, kChunk) + 1) * kScanElem);
+}
+
+// one bootstrap call, carved for `cap` expanded positions of a merged run of M points and S strands; `fields`: the
+// per-point form (dh_merged_bootstrap_run), else the batch form with one row of integrals
+struct BootBuf {
+  size_t cap;
+  int *mult, *off, *E, *src, *n;
+  long long* tot;
+  char* part;
+  double* lae;
+  double *sums, *partr, *mpart, *out, *kpart;  // batch
+  FieldArrays f;                               // per-point fields
+  long long* wide;
+};
+inline void carve_boot(Carver& c, BootBuf& b, size_t M, size_t S, size_t D, size_t cap, bool fields, bool want_mean) {
+  const size_t nbx = blocks_for(cap, kChunk);
+  b.cap = cap;
+  c(b.mult, "mult", S);
+  c(b.off, "off", M);
+  c(b.E, "E", M);
+  c(b.tot, "tot", 8);
+  c(b.part, "part", (blocks_for(M > cap ? M : cap, kChunk) + 1) * kScanElem);
+  c(b.src, "src", cap);
+  c(b.n, "n", cap);
+  c(b.lae, "lae", cap);
+  c(b.sums, "sums", nbx, !fields);
+  c(b.partr, "partr", nbx * kPart, !fields);
+  c(b.mpart, "mpart", nbx * D, !fields && want_mean);
+  c(b.out, "out", 3 + D, !fields);
+  c(b.kpart, "kpart", nbx, !fields);
+  carve_field_arrays(c, b.f, cap, true, fields);
+  c(b.wide, "wide", cap, fields);
+}
+
+// the tie structure of the merged run (an allocation of its own) and the scratch of the scan that builds it
+struct TieArrays {
+  int *tie_idx, *tie_ep;  // [M + 1]; at most one per strand
+};
+inline void carve_ties(Carver& c, TieArrays& t, size_t M, size_t S) {
+  c(t.tie_idx, "tie_idx", M + 1);
+  c(t.tie_ep, "tie_ep", S);
+}
+struct TieScratch {
+  char* part;
+};
+inline void carve_tie_scratch(Carver& c, TieScratch& t, size_t M) { c(t.part, "part", (blocks_for(M, kChunk) + 1) * kScanElem); }
+
+// the weight function: zweight and weight of every point, the maximum's bits, the bounds
+struct WeightBuf {
+  char* part;
+  double *tot, *zw, *wt;
+  u64* wmax;
+  int* idx;
+};
+inline void carve_weights(Carver& c, WeightBuf& w, size_t M) {
+  c(w.part, "part", (blocks_for(M, kChunk) + 1) * kScanElem);
+  c(w.tot, "tot", 1);
+  c(w.wmax, "wmax", 1);
+  c(w.idx, "idx", 2);
+  c(w.zw, "zw", M);
+  c(w.wt, "wt", M);
+}
+
+}  // namespace dh_merge

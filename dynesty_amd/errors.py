@@ -2,7 +2,7 @@
 (the reference's utils.jitter_run, utils.py:1317-1408) and reweighting (utils.reweight_run, utils.py:1663-1708).
 
 `ensemble.MergedRun` (merge='host') computes them in NumPy with the functions below, `_lib.DeviceMergedRun`
-(merge='device') where the run lives (csrc/merge.hip).  Both are the same function of
+(merge='device') where the run lives (csrc/merge_errors.hip).  Both are the same function of
 (seed, realization index):
 
   words      realization r uses subsequence r of the Philox4x32-10 stream keyed by `seed` (rocrand's stream model: the

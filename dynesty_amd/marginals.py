@@ -1,7 +1,7 @@
 """Credible intervals and the histograms of a corner plot, one surface for both merge routes.
 
 `ensemble.MergedRun` (merge='host') computes them in NumPy, `_lib.DeviceMergedRun` (merge='device') where the run
-lives (csrc/merge.hip).  This module holds what the two share: how `columns`, `bins` and
+lives (csrc/merge_marginals.hip).  This module holds what the two share: how `columns`, `bins` and
 `range` are read, and `corner_data`.  A class supplies `ndim`, `_quantile(q, cols)`, `_hist1d(cols, edges, weighted, ranges)`
 (ranges: the (lo, hi) the edges were spaced over, None for explicit edges) and `_hist2d(pairs, xedges, yedges, weighted)`,
 which validate their own arguments."""

@@ -606,7 +606,7 @@ int dh_unif_friends_batch(dh_ctx* ctx, int problem, int k, int ndim, int kind, c
                           double* v, double* logl, int32_t* ncalls, uint64_t* rng_out,
                           const uint64_t* rng32, uint64_t* rng32_out);
 
-/* ---- the combiner on the device (csrc/merge.hip) ---------------------------------------
+/* ---- the combiner on the device (csrc/merge*.hip) ---------------------------------------
  * dh_ns_keep(ctx, 1): the NEXT dh_ns_ensemble call (one-shot, like the options) stores the samples and the per-point
  * id / it / nc on the device whether or not their host pointers are given, downloads only what the host pointers ask
  * for, and leaves its allocation with the context as "the kept ensemble" (one per context).  A later keep,

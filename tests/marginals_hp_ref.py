@@ -18,7 +18,7 @@ apart in q, and a correctly rounded y is up to half of that from the q asked for
 
 Budgets, in units of q (cdf <= 1 and t <= 1 throughout).
 
-The device (csrc/merge.hip) replaces w_i by W_i 2^-62, W_i = llrint(w_i 2^62), |W_i 2^-62 - w_i| <= u = 2^-63, and
+The device (csrc/merge_marginals.hip) replaces w_i by W_i 2^-62, W_i = llrint(w_i 2^62), |W_i 2^-62 - w_i| <= u = 2^-63, and
 then works in exact integers.  With a = C_k + t w_(k) the exact cumulative weight at the returned point, r = Norm - a
 the rest, and a', r' their integer versions, |a' - a| <= n_a u and |r' - r| <= n_r u with n_a + n_r <= M points, and
 

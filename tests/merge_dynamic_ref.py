@@ -1,4 +1,4 @@
-"""The divergence and the weight function of a merged run (dynesty_amd/errors.py; csrc/merge.hip's me_integrate<., true>,
+"""The divergence and the weight function of a merged run (dynesty_amd/errors.py; csrc/merge_errors.hip's me_integrate<., true>,
 me_kld_finish, FRealKld, mw_*) restated in np.longdouble, and the bounds their float64
 evaluations are held to.  Built on tests/merge_errors_ref.py (one realization and its bounds b_wt, b_lnZ),
 tests/merge_bootstrap_ref.py (the expansion) and tests/merge_hp_ref.py (u, the scans' chains).  Nothing here is the

@@ -1,4 +1,4 @@
-"""One realization of a merged run's prior volumes (dynesty_amd/errors.py, csrc/merge.hip's me_* kernels) restated in
+"""One realization of a merged run's prior volumes (dynesty_amd/errors.py, csrc/merge_errors.hip's me_* kernels) restated in
 np.longdouble (64-bit mantissa on x86), and the bounds its float64 evaluations are held to -- derived as
 tests/merge_hp_ref.py derives the combiner's: c * 2^-53 * S with S the sum of absolute terms and c the longest chain of
 roundings.  The words are tests/philox_ref.py's, not the package's.

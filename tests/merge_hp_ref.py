@@ -9,7 +9,7 @@ U = 2.0 ** -53
 ETA = 2.0 ** -1074  # float64's underflow quantum (the smallest subnormal)
 LN2 = np.log(LD(2))
 
-# the device scans (csrc/merge.hip): 8 consecutive points per thread, 256 threads per workgroup
+# the device scans (csrc/merge_dev.h): 8 consecutive points per thread, 256 threads per workgroup
 SCAN_ITEMS, SCAN_THREADS = 8, 256
 
 

@@ -1,4 +1,4 @@
-"""The strand bootstrap of the merged run on the device (csrc/merge.hip, dh_merged_bootstrap / dh_merged_bootstrap_run;
+"""The strand bootstrap of the merged run on the device (csrc/merge_errors.hip, dh_merged_bootstrap / dh_merged_bootstrap_run;
 DESIGN.md section 3.8.3): the device against the host form for the same (seed, b); against the reference's
 utils.resample_run with its own draws injected (tests/golden/merge_bootstrap.npz); a bootstrap bit-identical alone and in
 any batch; the extremes of given multiplicities; the realizations of section 3.8.2 unchanged by bootstrap calls.

@@ -1,4 +1,4 @@
-"""Run-level analysis of the merged run on the device (csrc/merge.hip: dh_merged_kld, the KLD field of
+"""Run-level analysis of the merged run on the device (csrc/merge_errors.hip: dh_merged_kld, the KLD field of
 dh_merged_realization / dh_merged_bootstrap_run, dh_merged_weight_function, dh_merged_weights):
 the device against the long-double restatement (tests/merge_dynamic_ref.py), the host form and the reference's records
 (tests/golden/merge_dynamic.npz); a divergence bit-identical alone and in any batch; the existing calls unchanged.

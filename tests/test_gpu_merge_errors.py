@@ -1,4 +1,4 @@
-"""Statistical errors of the merged run on the device (csrc/merge.hip, dh_merged_realize / dh_merged_realization):
+"""Statistical errors of the merged run on the device (csrc/merge_errors.hip, dh_merged_realize / dh_merged_realization):
 per-point fields and the batch results against the long-double restatement (tests/merge_errors_ref.py) at the bounds it
 derives for the device's chains; a realization bit-identical alone and in any batch; the device against the host form;
 the distribution of ln Z against the reference's utils.jitter_run (tests/golden/merge_errors.npz); reweighting.

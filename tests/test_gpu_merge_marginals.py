@@ -1,4 +1,4 @@
-"""Marginals of the device's merged run (csrc/merge.hip: dh_merged_quantile, dh_merged_hist1d, dh_merged_hist2d).
+"""Marginals of the device's merged run (csrc/merge_marginals.hip: dh_merged_quantile, dh_merged_hist1d, dh_merged_hist2d).
 
 Quantiles are held to the exact quantile function of tests/marginals_hp_ref.py by their backward error in q, at the
 budget derived there (the weight quantisation M 2^-63 / Norm plus 8 roundings); q = 0 and q = 1 are the column's
