@@ -61,6 +61,7 @@ SIGNATURES = {
     "dh_event_record": (_i, [_vp, _vp]),
     "dh_event_elapsed_ms": (_i, [_vp, _vp, _vp, _pd]),
     "dh_problem_create": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i]),
+    "dh_problem_create_ex": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i]),
     "dh_problem_destroy": (_i, [_vp, _i]),
     "dh_problem_eval": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "dh_seed_children": (_i, [_vp, _vp, _i, _u32, _i, _vp]),
@@ -711,7 +712,7 @@ class Context:
             return self._problems[key][0]
         like_id, like_par, prior_id, prior_par = prob.device_spec()
         lp, pp = _f64(like_par), _f64(prior_par)
-        h = self._check(self.lib.dh_problem_create(
+        h = self._check(self.lib.dh_problem_create_ex(
             self.handle, prob.ndim, like_id, _ptr(lp), lp.size, prior_id,
             _ptr(pp) if pp.size else None, pp.size))
         self._problems[key] = (h, prob)  # keep prob alive: id() stays unique

@@ -6,6 +6,8 @@
 
 #include <stdlib.h>
 
+#include <cmath>
+
 #include "ctx.h"
 #include "npy_ziggurat_tables.h"
 #include "rng_pcg64.h"
@@ -66,6 +68,12 @@ bool get_problem(dh_ctx* ctx, int handle, ProblemDev* out) {
     return false;
   }
   const dh_problem_rec& r = ctx->problems[handle];
+  // every launcher takes its problem from here: an id the evaluators do not know never reaches a kernel
+  if (!problem_ids_known(r.like_id, r.prior_id)) {
+    fail(ctx, DH_ERR_ARG, "problem %d: likelihood id %d / prior id %d unknown to the evaluators", handle, r.like_id,
+         r.prior_id);
+    return false;
+  }
   out->like_id = r.like_id;
   out->prior_id = r.prior_id;
   out->ndim = r.ndim;
@@ -241,6 +249,75 @@ int dh_event_elapsed_ms(dh_ctx* ctx, void* ev0, void* ev1, double* ms) {
   return DH_OK;
 }
 
+// The store step of both entry points (the arguments are checked): what is kept, in which bits.
+// Matrices (GAUSS_PREC's P, a mixture's P_m): v^T P v only sees the symmetric part of P, and the evaluators read
+// different triangles of it (upper, lower, all of it), so every copy holds (P + P^T) / 2.  (a + a) / 2 == a: a
+// symmetric P is stored as given.
+// The lane kernels' copies (ndim <= 32), zero padded to their N: GAUSS_PREC's transposed matrix for the column-sweep
+// mat-vec (of the symmetrised P: its transpose is itself, bit for bit); a mixture's [mu_m (N), P_m (N x N)] per
+// component (loglike_mix_lds).  mix_m: the number of components, 0 for every other likelihood.
+static int problem_store(dh_ctx* ctx, int ndim, int like_id, const double* like_par, int n_like_par, int prior_id,
+                         const double* prior_par, int n_prior_par, int mix_m) {
+  const size_t nn = (size_t)ndim * ndim, blk_len = 1 + ndim + nn;
+  std::vector<double> lp(like_par, like_par + n_like_par);
+  const int nmat = like_id == DH_LIKE_GAUSS_MIX ? mix_m : like_id == DH_LIKE_GAUSS_PREC ? 1 : 0;
+  for (int m = 0; m < nmat; ++m) {
+    const size_t base = like_id == DH_LIKE_GAUSS_MIX ? 1 + (size_t)m * blk_len + 1 + ndim : 1;
+    for (int i = 0; i < ndim; ++i)
+      for (int j = 0; j < ndim; ++j) {
+        const size_t ij = base + (size_t)i * ndim + j, ji = base + (size_t)j * ndim + i;
+        lp[ij] = 0.5 * (like_par[ij] + like_par[ji]);
+      }
+  }
+  const bool want_t = nmat > 0 && ndim <= kMaxRegDim;
+  const int N = want_t ? pad_dim(ndim) : 0;
+  std::vector<double> pt((size_t)(like_id == DH_LIKE_GAUSS_MIX ? mix_m * (N + N * N) : N * N), 0.0);
+  if (want_t && like_id == DH_LIKE_GAUSS_PREC)
+    for (int i = 0; i < ndim; ++i)
+      for (int j = 0; j < ndim; ++j) pt[(size_t)j * N + i] = lp[1 + (size_t)i * ndim + j];
+  if (want_t && like_id == DH_LIKE_GAUSS_MIX)
+    for (int m = 0; m < mix_m; ++m) {
+      const double* blk = lp.data() + 1 + (size_t)m * blk_len + 1;  // mu_m, then P_m
+      double* out = pt.data() + (size_t)m * (N + N * N);
+      for (int i = 0; i < ndim; ++i) {
+        out[i] = blk[i];
+        for (int j = 0; j < ndim; ++j) out[N + (size_t)i * N + j] = blk[ndim + (size_t)i * ndim + j];
+      }
+    }
+  dh_problem_rec r;
+  r.live = true;
+  r.ndim = ndim;
+  r.like_id = like_id;
+  r.prior_id = prior_id;
+  r.n_like = n_like_par;
+  r.n_prior = n_prior_par;
+  r.mix_m = mix_m;
+  (void)hipSetDevice(ctx->device);
+  // an error below gives back what was allocated so far (hipFree(nullptr) does nothing)
+  auto give_up = [&r](int code) {
+    (void)hipFree(r.like_par);
+    (void)hipFree(r.prior_par);
+    (void)hipFree(r.prec_t);
+    return code;
+  };
+  if (!hip_ok(ctx, hipMalloc((void**)&r.like_par, sizeof(double) * (n_like_par + 1)), "hipMalloc") ||
+      !hip_ok(ctx, hipMalloc((void**)&r.prior_par, sizeof(double) * (n_prior_par + 2)), "hipMalloc") ||
+      (want_t && !hip_ok(ctx, hipMalloc((void**)&r.prec_t, sizeof(double) * pt.size()), "hipMalloc")))
+    return give_up(DH_ERR_NOMEM);
+  if (!hip_ok(ctx, hipMemcpy(r.like_par, lp.data(), sizeof(double) * n_like_par, hipMemcpyHostToDevice), "H2D like_par") ||
+      (n_prior_par && !hip_ok(ctx, hipMemcpy(r.prior_par, prior_par, sizeof(double) * n_prior_par, hipMemcpyHostToDevice),
+                              "H2D prior_par")) ||
+      (want_t && !hip_ok(ctx, hipMemcpy(r.prec_t, pt.data(), sizeof(double) * pt.size(), hipMemcpyHostToDevice), "H2D prec_t")))
+    return give_up(DH_ERR_HIP);
+  for (size_t i = 0; i < ctx->problems.size(); ++i)
+    if (!ctx->problems[i].live) {
+      ctx->problems[i] = r;
+      return (int)i;
+    }
+  ctx->problems.push_back(r);
+  return (int)ctx->problems.size() - 1;
+}
+
 int dh_problem_create(dh_ctx* ctx, int ndim, int like_id, const double* like_par, int n_like_par,
                       int prior_id, const double* prior_par, int n_prior_par) {
   DH_CHECK_CTX(ctx);
@@ -255,60 +332,63 @@ int dh_problem_create(dh_ctx* ctx, int ndim, int like_id, const double* like_par
                 n_prior_par);
   if (!like_par || (n_prior_par > 0 && !prior_par))
     return fail(ctx, DH_ERR_ARG, "problem_create: null pointer");
-  // GAUSS_PREC: v^T P v only sees the symmetric part of P, and the evaluators read different triangles
-  // of it (upper, lower, all of it), so every copy holds (P + P^T) / 2.  (a + a) / 2 == a: a symmetric
-  // P is stored as given.
-  std::vector<double> lp(like_par, like_par + n_like_par);
-  if (like_id == DH_LIKE_GAUSS_PREC)
-    for (int i = 0; i < ndim; ++i)
-      for (int j = 0; j < ndim; ++j) {
-        const size_t ij = 1 + (size_t)i * ndim + j, ji = 1 + (size_t)j * ndim + i;
-        lp[ij] = 0.5 * (like_par[ij] + like_par[ji]);
-      }
-  // transposed + zero-padded copy for the column-sweep mat-vec of the walk kernels (of the
-  // symmetrised P: its transpose is itself, bit for bit)
-  const bool want_t = like_id == DH_LIKE_GAUSS_PREC && ndim <= kMaxRegDim;
-  const int N = want_t ? pad_dim(ndim) : 0;
-  std::vector<double> pt((size_t)N * N, 0.0);
-  if (want_t)
-    for (int i = 0; i < ndim; ++i)
-      for (int j = 0; j < ndim; ++j) pt[(size_t)j * N + i] = lp[1 + (size_t)i * ndim + j];
-  dh_problem_rec r;
-  r.live = true;
-  r.ndim = ndim;
-  r.like_id = like_id;
-  r.prior_id = prior_id;
-  r.n_like = n_like_par;
-  r.n_prior = n_prior_par;
-  (void)hipSetDevice(ctx->device);
-  // an error below gives back what was allocated so far (hipFree(nullptr) does nothing)
-  auto give_up = [&r](int code) {
-    (void)hipFree(r.like_par);
-    (void)hipFree(r.prior_par);
-    (void)hipFree(r.prec_t);
-    return code;
-  };
-  if (!hip_ok(ctx, hipMalloc((void**)&r.like_par, sizeof(double) * (n_like_par + 1)), "hipMalloc") ||
-      !hip_ok(ctx, hipMalloc((void**)&r.prior_par, sizeof(double) * (n_prior_par + 2)), "hipMalloc") ||
-      (want_t && !hip_ok(ctx, hipMalloc((void**)&r.prec_t, sizeof(double) * N * N), "hipMalloc")))
-    return give_up(DH_ERR_NOMEM);
-  if (!hip_ok(ctx, hipMemcpy(r.like_par, lp.data(), sizeof(double) * n_like_par, hipMemcpyHostToDevice),
-              "H2D like_par"))
-    return give_up(DH_ERR_HIP);
-  if (n_prior_par &&
-      !hip_ok(ctx, hipMemcpy(r.prior_par, prior_par, sizeof(double) * n_prior_par, hipMemcpyHostToDevice),
-              "H2D prior_par"))
-    return give_up(DH_ERR_HIP);
-  if (want_t && !hip_ok(ctx, hipMemcpy(r.prec_t, pt.data(), sizeof(double) * N * N, hipMemcpyHostToDevice),
-                        "H2D prec_t"))
-    return give_up(DH_ERR_HIP);
-  for (size_t i = 0; i < ctx->problems.size(); ++i)
-    if (!ctx->problems[i].live) {
-      ctx->problems[i] = r;
-      return (int)i;
+  return problem_store(ctx, ndim, like_id, like_par, n_like_par, prior_id, prior_par, n_prior_par, 0);
+}
+
+// Every id 0..3 in any pairing.  A pair of the ids 0..2 IS dh_problem_create's (the same checks, the same stored
+// bits); a pair with DH_LIKE_GAUSS_MIX or DH_PRIOR_TABLE is checked here and stored by the same problem_store.
+// The parameters of an older id paired with a new one are checked as dh_problem_create checks them (at least the
+// count it needs, finite here besides): AFFINE's a and NORMAL's sigma are not required to be positive.
+int dh_problem_create_ex(dh_ctx* ctx, int ndim, int like_id, const double* like_par, int n_like_par, int prior_id,
+                         const double* prior_par, int n_prior_par) {
+  DH_CHECK_CTX(ctx);
+  if (like_id != DH_LIKE_GAUSS_MIX && prior_id != DH_PRIOR_TABLE)
+    return dh_problem_create(ctx, ndim, like_id, like_par, n_like_par, prior_id, prior_par, n_prior_par);
+  if (ndim < 1) return fail(ctx, DH_ERR_ARG, "ndim=%d", ndim);
+  if (like_id < 0 || like_id > DH_LIKE_GAUSS_MIX) return fail(ctx, DH_ERR_ARG, "likelihood id %d", like_id);
+  if (prior_id < 0 || prior_id > DH_PRIOR_TABLE) return fail(ctx, DH_ERR_ARG, "prior id %d", prior_id);
+  if (!like_par || n_like_par < 1 || (n_prior_par > 0 && !prior_par) || n_prior_par < 0)
+    return fail(ctx, DH_ERR_ARG, "problem_create_ex: null pointer or no likelihood parameter");
+  const long long nn = (long long)ndim * ndim;
+  int M = 0;
+  if (like_id == DH_LIKE_GAUSS_MIX) {
+    const double m = like_par[0];
+    if (!(m >= 1.0 && m <= (double)DH_MIX_MAX) || m != (double)(int)m)
+      return fail(ctx, DH_ERR_ARG, "Gaussian mixture: M = %g components, need an integer in 1..%d", m, DH_MIX_MAX);
+    M = (int)m;
+    const long long need = 1 + M * (1 + (long long)ndim + nn);
+    if ((long long)n_like_par != need)
+      return fail(ctx, DH_ERR_ARG, "Gaussian mixture of %d components in %d dimensions has %lld parameters, got %d", M,
+                  ndim, need, n_like_par);
+  } else {
+    const long long need = like_id == DH_LIKE_GAUSS_PREC ? 1 + nn : 1;
+    if ((long long)n_like_par < need)
+      return fail(ctx, DH_ERR_ARG, "likelihood id %d needs %lld parameters, got %d", like_id, need, n_like_par);
+  }
+  if (prior_id == DH_PRIOR_TABLE) {
+    if ((long long)n_prior_par != 3ll * ndim)
+      return fail(ctx, DH_ERR_ARG, "prior table of %d coordinates has %d parameters, got %d", ndim, 3 * ndim, n_prior_par);
+  } else if (n_prior_par < (prior_id == DH_PRIOR_IDENTITY ? 0 : 2)) {
+    return fail(ctx, DH_ERR_ARG, "prior id %d needs 2 parameters, got %d", prior_id, n_prior_par);
+  }
+  for (int i = 0; i < n_like_par; ++i)
+    if (!std::isfinite(like_par[i])) return fail(ctx, DH_ERR_ARG, "likelihood parameter %d is not finite", i);
+  for (int i = 0; i < n_prior_par; ++i)
+    if (!std::isfinite(prior_par[i])) return fail(ctx, DH_ERR_ARG, "prior parameter %d is not finite", i);
+  if (prior_id == DH_PRIOR_TABLE)
+    for (int i = 0; i < ndim; ++i) {
+      const double kind = prior_par[3 * i], p1 = prior_par[3 * i + 2];
+      if (kind != (double)DH_TABLE_UNIFORM && kind != (double)DH_TABLE_NORMAL && kind != (double)DH_TABLE_LOGUNIFORM)
+        return fail(ctx, DH_ERR_ARG, "prior table row %d: kind %g (0 uniform, 1 normal, 2 log-uniform)", i, kind);
+      if (kind != (double)DH_TABLE_LOGUNIFORM && !(p1 > 0.0))
+        return fail(ctx, DH_ERR_ARG, "prior table row %d: width / sigma %g is not positive", i, p1);
     }
-  ctx->problems.push_back(r);
-  return (int)ctx->problems.size() - 1;
+  if (like_id == DH_LIKE_GAUSS_MIX)
+    for (int m = 0; m < M; ++m)
+      for (int i = 0; i < ndim; ++i)
+        if (!(like_par[1 + (size_t)m * (1 + ndim + nn) + 1 + ndim + (size_t)i * ndim + i] > 0.0))
+          return fail(ctx, DH_ERR_ARG, "Gaussian mixture: component %d has a non-positive diagonal entry (%d)", m, i);
+  return problem_store(ctx, ndim, like_id, like_par, n_like_par, prior_id, prior_par, n_prior_par, M);
 }
 
 int dh_problem_destroy(dh_ctx* ctx, int problem) {

@@ -10,8 +10,23 @@
 
 namespace dh {
 
-enum : int { LIKE_GAUSS_IID = 0, LIKE_GAUSS_PREC = 1, LIKE_EGGBOX = 2 };
-enum : int { PRIOR_IDENTITY = 0, PRIOR_AFFINE = 1, PRIOR_NORMAL = 2 };
+enum : int { LIKE_GAUSS_IID = 0, LIKE_GAUSS_PREC = 1, LIKE_EGGBOX = 2, LIKE_GAUSS_MIX = 3 };
+enum : int { PRIOR_IDENTITY = 0, PRIOR_AFFINE = 1, PRIOR_NORMAL = 2, PRIOR_TABLE = 3 };
+// LIKE_GAUSS_MIX: like_par = [M, then per component c_m, mu_m (n), P_m (n x n row-major, symmetric)], 1 <= M <= MIX_MAX
+// PRIOR_TABLE:    prior_par = n rows [kind, p0, p1] (TABLE_* below)
+enum : int { MIX_MAX = 8 };
+enum : int { TABLE_UNIFORM = 0, TABLE_NORMAL = 1, TABLE_LOGUNIFORM = 2 };
+// the ids an evaluator knows; the launchers refuse every other (get_problem), so that no kernel meets one
+__host__ __device__ inline bool problem_ids_known(int like_id, int prior_id) {
+  return like_id >= LIKE_GAUSS_IID && like_id <= LIKE_GAUSS_MIX && prior_id >= PRIOR_IDENTITY && prior_id <= PRIOR_TABLE;
+}
+// The four-lanes-per-walker kernel (walkq.hip) stages the fragments of at most QMIX_MAX mixture components in LDS
+// (8 KB each at D = 32): a mixture of M <= QMIX_MAX components takes it at every ndim = 2..32, a larger one the
+// lane-per-walker kernel -- a function of (ndim, M) alone, never of the launch size or the device.
+enum : int { QMIX_MAX = 4 };
+__host__ __device__ inline bool problem_has_quad_form(int like_id, int prior_id, int mix_m) {
+  return problem_ids_known(like_id, prior_id) && (like_id != LIKE_GAUSS_MIX || (mix_m >= 1 && mix_m <= QMIX_MAX));
+}
 
 // Kernels are specialised on the (likelihood, prior) pair so the proposal loop
 // carries no dispatch; KIND_GENERIC keeps a runtime switch for other pairs.
@@ -21,7 +36,11 @@ enum : int {
   KIND_IID_AFFINE = 2,      // C1: iid Normal, uniform box prior
   KIND_EGGBOX_IDENTITY = 3, // C3
   KIND_IID_NORMAL = 4,      // C4: iid Normal, Normal prior (ndtri)
-  KIND_COUNT = 5
+  // any pair with LIKE_GAUSS_MIX or PRIOR_TABLE: a runtime switch like KIND_GENERIC's, plus the two evaluators.  An
+  // instance of its own, so that KIND_GENERIC's hold none of their code: with the two calls in it,
+  // rwalk_kernel<25, true, KIND_GENERIC, PCG64> spilled 10 VGPRs against none (tests/test_codegen_budget.py).
+  KIND_EXT = 5,
+  KIND_COUNT = 6
 };
 
 // periodic wrap and reflection of one unit-cube coordinate (utils.py:1053-1078 apply_reflect; np.mod(x, 1))
@@ -33,6 +52,7 @@ __device__ __forceinline__ double reflect01(double x) {
 }
 
 __host__ __device__ inline int problem_kind(int like_id, int prior_id) {
+  if (like_id == LIKE_GAUSS_MIX || prior_id == PRIOR_TABLE) return KIND_EXT;
   if (like_id == LIKE_GAUSS_PREC && prior_id == PRIOR_AFFINE) return KIND_PREC_AFFINE;
   if (like_id == LIKE_GAUSS_IID && prior_id == PRIOR_AFFINE) return KIND_IID_AFFINE;
   if (like_id == LIKE_EGGBOX && prior_id == PRIOR_IDENTITY) return KIND_EGGBOX_IDENTITY;
@@ -65,21 +85,22 @@ struct ProblemDev {
   int like_id;
   int prior_id;
   int ndim;
-  const double* like_par;   // [c, P row-major (n x n)] / [c] / [tmax]
-  const double* prior_par;  // [a, b] / [mu, sigma]
-  const double* prec_t;     // GAUSS_PREC: P transposed + zero padded to the kernel's N
+  const double* like_par;   // [c, P row-major (n x n)] / [c] / [tmax] / [M, M x (c_m, mu_m, P_m)]
+  const double* prior_par;  // [a, b] / [mu, sigma] / n rows [kind, p0, p1]
+  const double* prec_t;     // GAUSS_PREC: P transposed + zero padded to the kernel's N; GAUSS_MIX: per component
+                            // [mu_m, P_m] zero padded to N (ndim <= 32)
 };
 
 template <int KIND>
 __device__ __forceinline__ int like_of(const ProblemDev& P) {
-  return KIND == KIND_GENERIC         ? P.like_id
+  return (KIND == KIND_GENERIC || KIND == KIND_EXT) ? P.like_id
          : KIND == KIND_PREC_AFFINE   ? LIKE_GAUSS_PREC
          : KIND == KIND_EGGBOX_IDENTITY ? LIKE_EGGBOX
                                         : LIKE_GAUSS_IID;
 }
 template <int KIND>
 __device__ __forceinline__ int prior_of(const ProblemDev& P) {
-  return KIND == KIND_GENERIC           ? P.prior_id
+  return (KIND == KIND_GENERIC || KIND == KIND_EXT) ? P.prior_id
          : KIND == KIND_EGGBOX_IDENTITY ? PRIOR_IDENTITY
          : KIND == KIND_IID_NORMAL      ? PRIOR_NORMAL
                                         : PRIOR_AFFINE;
@@ -245,6 +266,80 @@ __device__ __forceinline__ void matvec_sgpr(cdptr MT, const double* xs, int lane
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// PRIOR_TABLE and LIKE_GAUSS_MIX, lane per walker.  Both are calls (the ndtri_far lesson): inlined, the rolled loops,
+// ocml's exp / log and erfcinv would share one register allocation with the proposal loop of every KIND_GENERIC
+// instance.  The arguments arrive in vector registers; the parameter pointers are wave-uniform (a lane is a walker)
+// and are pinned to SGPRs, so the rows and the matrices come through the scalar cache.
+// ---------------------------------------------------------------------------------------------------------
+// one coordinate of the table: the expressions of problems.py, in its order
+__device__ __forceinline__ double table_coord(double kind, double p0, double p1, double u) {
+  if (kind == (double)TABLE_UNIFORM) return fma(u, p1, p0);
+  if (kind == (double)TABLE_NORMAL) return p0 + p1 * ndtri_far(u);
+  return exp(fma(u, p1, p0));
+}
+
+// sv ([dim][64 lanes]) holds u on entry and v on return; entries n <= i < N become 0
+__device__ __attribute__((noinline)) void prior_table_lds(const double* prior_par, int n, int N, double* sv, int lane) {
+  cdptr pp = as_const_uniform(prior_par);
+#pragma unroll 1
+  for (int i = 0; i < N; ++i) {
+    double o = 0.0;
+    if (i < n) o = table_coord(pp[3 * i], pp[3 * i + 1], pp[3 * i + 2], sv[i * 64 + lane]);
+    sv[i * 64 + lane] = o;
+  }
+}
+
+// logl = a* + log(sum_m exp(a_m - a*)), a_m = c_m - (v - mu_m)^T P_m (v - mu_m) / 2 in the triangular order of
+// LIKE_GAUSS_PREC; M = 1 returns a_0 itself.  The a_m stay in registers (selects, no indexed array on the stack).
+__device__ __forceinline__ double mix_combine(const double (&a)[MIX_MAX], int M) {
+  if (M == 1) return a[0];
+  double amax = a[0];
+#pragma unroll
+  for (int k = 1; k < MIX_MAX; ++k) amax = fmax(amax, a[k]);  // (entries k >= M are -inf)
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < MIX_MAX; ++k)
+    if (k < M) s += exp(a[k] - amax);
+  return amax + log(s);
+}
+
+// `pad` (ProblemDev::prec_t of a mixture): per component [mu_m (N), P_m (N x N)] zero padded to the kernel's N, so
+// the difference vector stays in registers and the triangular form unrolls with static strides, as LIKE_GAUSS_PREC's
+// does (rolled over a runtime n, the same launch took twice as long: EXPERIMENTS.md).  Padded entries of sv are 0
+// (prior_to_lds), so are the padded d.  A scheduling barrier every four rows: see loglike_lds's SB.
+template <int N>
+__device__ __attribute__((noinline)) double loglike_mix_lds(const double* like_par, const double* pad, int n,
+                                                            const double* sv, int lane) {
+  cdptr lp = as_const_uniform(like_par);
+  cdptr pd = as_const_uniform(pad);
+  const int M = (int)lp[0];
+  double a[MIX_MAX];
+#pragma unroll
+  for (int k = 0; k < MIX_MAX; ++k) a[k] = -INFINITY;
+#pragma unroll 1
+  for (int m = 0; m < M; ++m) {
+    cdptr mu = pd + (size_t)m * (N + N * N);
+    cdptr A = mu + N;
+    double d[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) d[i] = sv[i * 64 + lane] - mu[i];
+    double q = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      double r = 0.5 * A[i * N + i] * d[i];
+#pragma unroll
+      for (int j = i + 1; j < N; ++j) r = fma(A[i * N + j], d[j], r);
+      q = fma(d[i], r, q);
+      if ((i % 4) == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+    const double am = lp[1 + (size_t)m * (1 + n + n * n)] - q;
+#pragma unroll
+    for (int k = 0; k < MIX_MAX; ++k) a[k] = k == m ? am : a[k];
+  }
+  return mix_combine(a, M);
+}
+
 // v = prior_transform(u), written to the per-lane LDS column `sv`
 // ([dim][64 lanes]); entries i >= n are 0.  The rolled loop keeps the
 // transcendental priors out of the unrolled register code.
@@ -265,9 +360,16 @@ __device__ __forceinline__ void prior_to_lds(const ProblemDev& P, const double (
 #pragma unroll 1
     for (int i = 0; i < N; ++i)
       sv[i * 64 + lane] = (FULL || i < n) ? mu + sg * ndtri_far(sv[i * 64 + lane]) : 0.0;  // (a call: see ndtri_far)
-  } else {
+  } else if (KIND == KIND_EXT && pid == PRIOR_TABLE) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) sv[i * 64 + lane] = u[i];
+    prior_table_lds(P.prior_par, n, N, sv, lane);
+  } else if (pid == PRIOR_IDENTITY) {
 #pragma unroll
     for (int i = 0; i < N; ++i) sv[i * 64 + lane] = (FULL || i < n) ? u[i] : 0.0;
+  } else {  // an id no evaluator knows (the launchers refuse it): never another problem's values
+#pragma unroll
+    for (int i = 0; i < N; ++i) sv[i * 64 + lane] = __builtin_nan("");
   }
 }
 
@@ -346,7 +448,9 @@ __device__ __forceinline__ double loglike_lds(const ProblemDev& P, int n, const 
     const double b = 2.0 + prod;
     const double b2 = b * b;
     return b2 * b2 * b;
-  } else {
+  } else if (KIND == KIND_EXT && lid == LIKE_GAUSS_MIX) {
+    return loglike_mix_lds<N>(P.like_par, P.prec_t, n, sv, lane);
+  } else if (lid == LIKE_GAUSS_IID) {
     double q0 = 0.0, q1 = 0.0;
 #pragma unroll
     for (int i = 0; i + 1 < N; i += 2) {  // padded entries are 0
@@ -359,6 +463,8 @@ __device__ __forceinline__ double loglike_lds(const ProblemDev& P, int n, const 
       q0 = fma(a, a, q0);
     }
     return lp[0] - 0.5 * (q0 + q1);
+  } else {
+    return __builtin_nan("");  // an id no evaluator knows (the launchers refuse it)
   }
 }
 

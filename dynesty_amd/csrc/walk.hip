@@ -294,7 +294,7 @@ __global__ void __launch_bounds__(64, DH_RW_OCC) rwalk_kernel(RwalkArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-template <int N>
+template <int N, int KIND>
 __global__ void __launch_bounds__(64)
     eval_kernel(ProblemDev prob, int k, const double* __restrict__ u, double* v, double* logl) {
   __shared__ double sx[N * 64];
@@ -305,8 +305,8 @@ __global__ void __launch_bounds__(64)
   double uu[N], acc[N];
 #pragma unroll
   for (int i = 0; i < N; ++i) uu[i] = (i < n) ? u[(size_t)wi * n + i] : 0.5;
-  prior_to_lds<N, false, KIND_GENERIC>(prob, uu, n, sx, lane);
-  const double ll = loglike_lds<N, false, KIND_GENERIC>(prob, n, sx, lane, acc);
+  prior_to_lds<N, false, KIND>(prob, uu, n, sx, lane);
+  const double ll = loglike_lds<N, false, KIND>(prob, n, sx, lane, acc);
   if (w >= k) return;
   logl[w] = ll;
 #pragma unroll
@@ -421,11 +421,14 @@ int dh::rwalk_launch_runs(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, 
   // (64 x 512 walkers: 0.27 ms against 0.86; 64 x 2000: 1.02 against 1.23), so form 0 takes it whenever it
   // applies -- a function of the problem alone, never of the launch size or the device, so that a run's
   // accept / reject sequence cannot depend on how many runs share a GPU (form 1: never, 2: same as 0).
+  // (LIKE_GAUSS_MIX: up to QMIX_MAX components -- problem_has_quad_form, again the problem alone)
+  const int mix_m = a.propose_only ? 0 : ctx->problems[problem].mix_m;
   const bool quad_ok = !a.propose_only && ndim == ncdim && ndim >= 2 && ndim <= kMaxRegDim &&
-                       (long long)walks * (ndim + 1) < (1ll << 24);
+                       (long long)walks * (ndim + 1) < (1ll << 24) &&
+                       problem_has_quad_form(a.prob.like_id, a.prob.prior_id, mix_m);
   if (quad_ok && ctx->rwalk_form != 1)
     return rwalkq_launch(ctx, a.prob, k, ndim, u0, axes, m, axes_idx, scale, loglstar, walks, rng, u, v, logl,
-                         naccept, nreject, rng_out, run_loglstar, run_scale, run_mode, wpr, my_mode, philox, bc);
+                         naccept, nreject, rng_out, run_loglstar, run_scale, run_mode, wpr, my_mode, philox, bc, mix_m);
   a.k = k;
   a.ndim = ndim;
   a.ncdim = ncdim;
@@ -471,7 +474,9 @@ int dh::rwalk_launch_runs(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, 
   a.axes_t = ctx->axes_t;
   const dim3 grid((k + 63) / 64), block(64);
   const bool full = (ndim == N && ncdim == N) && !a.propose_only;
-  const int kind = full ? problem_kind(a.prob.like_id, a.prob.prior_id) : KIND_GENERIC;
+  // (KIND_EXT: the padded form serves every ndim / ncdim)
+  const int pkind = a.propose_only ? KIND_GENERIC : problem_kind(a.prob.like_id, a.prob.prior_id);
+  const int kind = pkind == KIND_EXT ? KIND_EXT : full ? pkind : KIND_GENERIC;
 #define L(NN, FF, KK)                                                                            \
   do {                                                                                           \
     if (philox)                                                                                  \
@@ -481,7 +486,9 @@ int dh::rwalk_launch_runs(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, 
   } while (0)
 #define X(NN)                                       \
   if (N == NN) {                                    \
-    if (!full)                                      \
+    if (kind == KIND_EXT)                           \
+      L(NN, false, KIND_EXT);                       \
+    else if (!full)                                 \
       L(NN, false, KIND_GENERIC);                   \
     else if (kind == KIND_PREC_AFFINE)              \
       L(NN, true, KIND_PREC_AFFINE);                \
@@ -617,10 +624,14 @@ int dh::eval_launch_dev(dh_ctx* ctx, int problem, int k, const double* u, double
   const dim3 grid((k + 63) / 64), block(64);
   const int ndim = p.ndim;
   bool hit = false;
+  const bool ext = problem_kind(p.like_id, p.prior_id) == KIND_EXT;
 #define X(NN)                                                                  \
   if (!hit && ndim <= NN) {                                                    \
     hit = true;                                                                \
-    hipLaunchKernelGGL(eval_kernel<NN>, grid, block, 0, ctx->stream, p, k, u, v, logl); \
+    if (ext)                                                                   \
+      hipLaunchKernelGGL((eval_kernel<NN, KIND_EXT>), grid, block, 0, ctx->stream, p, k, u, v, logl); \
+    else                                                                       \
+      hipLaunchKernelGGL((eval_kernel<NN, KIND_GENERIC>), grid, block, 0, ctx->stream, p, k, u, v, logl); \
   }
   DH_DIM_LIST(X)
 #undef X
@@ -645,6 +656,7 @@ int dh_problem_eval(dh_ctx* ctx, int problem, int k, const double* u, double* v,
   if (!d_u || !d_v || !d_l) return DH_ERR_NOMEM;
   const dim3 grid((k + 63) / 64), block(64);
   bool hit = false;
+  const bool ext = problem_kind(p.like_id, p.prior_id) == KIND_EXT;
   if (ndim > kMaxRegDim) {
     hit = true;
     rc = wide_eval_launch(ctx, p, k, d_u, d_v, d_l);
@@ -653,7 +665,10 @@ int dh_problem_eval(dh_ctx* ctx, int problem, int k, const double* u, double* v,
 #define X(NN)                                                                      \
   if (!hit && ndim <= NN) {                                                        \
     hit = true;                                                                    \
-    hipLaunchKernelGGL(eval_kernel<NN>, grid, block, 0, ctx->stream, p, k, d_u, d_v, d_l); \
+    if (ext)                                                                       \
+      hipLaunchKernelGGL((eval_kernel<NN, KIND_EXT>), grid, block, 0, ctx->stream, p, k, d_u, d_v, d_l); \
+    else                                                                           \
+      hipLaunchKernelGGL((eval_kernel<NN, KIND_GENERIC>), grid, block, 0, ctx->stream, p, k, d_u, d_v, d_l); \
   }
   DH_DIM_LIST(X)
 #undef X

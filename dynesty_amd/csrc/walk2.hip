@@ -986,7 +986,9 @@ int dh::slice_launch_runs(dh_ctx* ctx, int problem, int k, int ndim, int mode, c
 #define LP(NN, KK) hipLaunchKernelGGL((slice_kernel<NN, KK, RNG_PHILOX>), grid, block, 0, ctx->stream, a)
 #define X(NN)                                        \
   if (philox && N == NN) {                           \
-    if (NN == 2 && kind == KIND_EGGBOX_IDENTITY)     \
+    if (kind == KIND_EXT)                            \
+      LP(NN, KIND_EXT);                              \
+    else if (NN == 2 && kind == KIND_EGGBOX_IDENTITY) \
       LP(2, KIND_EGGBOX_IDENTITY);                   \
     else                                             \
       LP(NN, KIND_GENERIC);                          \
@@ -1006,6 +1008,8 @@ int dh::slice_launch_runs(dh_ctx* ctx, int problem, int k, int ndim, int mode, c
       L(NN, KIND_EGGBOX_IDENTITY);         \
     else if (kind == KIND_IID_NORMAL)      \
       L(NN, KIND_IID_NORMAL);              \
+    else if (kind == KIND_EXT)             \
+      L(NN, KIND_EXT);                     \
     else                                   \
       L(NN, KIND_GENERIC);                 \
   }
@@ -1111,13 +1115,17 @@ int unif_dispatch(dh_ctx* ctx, const UnifArgs& a, int N, bool philox = false) {
   // ensemble form: whole wavefronts per run (a.wpr walkers each)
   const dim3 grid(a.run_mode ? (k / a.wpr) * ((a.wpr + 63) / 64) : (k + 63) / 64), block(64);
   const bool full = (ndim == N && ncdim == N);
-  const int kind = (full && !a.propose_only) ? problem_kind(a.prob.like_id, a.prob.prior_id) : KIND_GENERIC;
+  // (KIND_EXT: the padded form serves every ndim / ncdim)
+  const int pkind = a.propose_only ? KIND_GENERIC : problem_kind(a.prob.like_id, a.prob.prior_id);
+  const int kind = pkind == KIND_EXT ? KIND_EXT : full ? pkind : KIND_GENERIC;
   // throughput mode: the generic kind of every dimension, and the BASELINE configs' own
   // (C1 3-D iid Normal, C2 25-D correlated Normal, C3 2-D eggbox)
 #define LP(NN, FF, KK) hipLaunchKernelGGL((unif_kernel<NN, FF, KK, RNG_PHILOX>), grid, block, 0, ctx->stream, a)
 #define X(NN)                                                 \
   if (philox && N == NN) {                                    \
-    if (!full)                                                \
+    if (kind == KIND_EXT)                                     \
+      LP(NN, false, KIND_EXT);                                \
+    else if (!full)                                           \
       LP(NN, false, KIND_GENERIC);                            \
     else if (NN == 25 && kind == KIND_PREC_AFFINE)            \
       LP(25, true, KIND_PREC_AFFINE);                         \
@@ -1135,7 +1143,9 @@ int unif_dispatch(dh_ctx* ctx, const UnifArgs& a, int N, bool philox = false) {
 #define L(NN, FF, KK) hipLaunchKernelGGL((unif_kernel<NN, FF, KK, RNG_PCG64>), grid, block, 0, ctx->stream, a)
 #define X(NN)                              \
   if (N == NN) {                           \
-    if (!full)                             \
+    if (kind == KIND_EXT)                  \
+      L(NN, false, KIND_EXT);              \
+    else if (!full)                        \
       L(NN, false, KIND_GENERIC);          \
     else if (kind == KIND_PREC_AFFINE)     \
       L(NN, true, KIND_PREC_AFFINE);       \
@@ -1160,7 +1170,8 @@ namespace {
 int cube_quad_dispatch(dh_ctx* ctx, const CubeQArgs& a, int N, bool philox) {
   const dim3 grid((a.k + 15) / 16), block(64);
   const bool full = a.ndim == N;
-  const int kind = full ? problem_kind(a.prob.like_id, a.prob.prior_id) : KIND_GENERIC;
+  const int pkind = problem_kind(a.prob.like_id, a.prob.prior_id);
+  const int kind = pkind == KIND_EXT ? KIND_EXT : full ? pkind : KIND_GENERIC;
 #define LQ(NN, FF, KK)                                                                                         \
   do {                                                                                                         \
     if (philox)                                                                                                \
@@ -1170,7 +1181,9 @@ int cube_quad_dispatch(dh_ctx* ctx, const CubeQArgs& a, int N, bool philox) {
   } while (0)
 #define X(NN)                                         \
   if (N == NN) {                                      \
-    if (!full)                                        \
+    if (kind == KIND_EXT)                             \
+      LQ(NN, false, KIND_EXT);                        \
+    else if (!full)                                   \
       LQ(NN, false, KIND_GENERIC);                    \
     else if (NN == 25 && kind == KIND_PREC_AFFINE)    \
       LQ(25, true, KIND_PREC_AFFINE);                 \

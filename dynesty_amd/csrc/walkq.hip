@@ -1018,6 +1018,18 @@ __device__ __forceinline__ void frag_matvec(const double (&F)[MT][NR], const dou
     for (int mt = 0; mt < MT; ++mt) acc[mt] = DH_MFMA_F64(F[mt][s], x[s], acc[mt]);
 }
 
+// DH_LIKE_GAUSS_MIX / DH_PRIOR_TABLE in the four-lane form (KIND_EXT).  The transcendental parts are calls, as ndtri_far
+// is: inlined, ocml's exp / log / erfcinv would share the walk's register allocation.
+// QMIX_MAX components have their fragments staged in LDS (problem.h: problem_has_quad_form sends larger mixtures to the
+// lane kernel).
+__device__ __attribute__((noinline)) double mix_combine_call(double a0, double a1, double a2, double a3, int M) {
+  const double a[MIX_MAX] = {a0, a1, a2, a3, -INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  return mix_combine(a, M);
+}
+__device__ __attribute__((noinline)) double table_coord_call(double kind, double p0, double p1, double u) {
+  return table_coord(kind, p0, p1, u);
+}
+
 // log-likelihood of the walker's v (quarter vector per sub-lane); every sub-lane returns the same bits
 // R1 (n = 4 (NR - 1) + 1): the last K step holds ONE live column; it is added as w[row] += P[row][n - 1] v[n - 1] by
 // vector instructions (Cp: this lane's rows of that column) instead of a whole matrix instruction per row block
@@ -1049,6 +1061,46 @@ __device__ __forceinline__ double loglike_quad(const ProblemDev& P, int n, int t
         q0 = fma(v[r], w[r >> 2][r & 3], q0);
     }
     return lp[0] - 0.5 * grp_sum(q0 + q1);
+  } else if (KIND == KIND_EXT && lid == LIKE_GAUSS_MIX) {
+    // per component: d = v - mu_m (this sub-lane's coordinates 4 r + t), P_m d of the wave's 16 walkers as one chain
+    // of matrix instructions on the component's fragments, q = d . (P_m d) summed over the group; max / exp / log
+    // on the group sums, so the four sub-lanes return the same bits
+    const int M = (int)lp[0];
+    double am[QMIX_MAX];
+#pragma unroll
+    for (int k = 0; k < QMIX_MAX; ++k) am[k] = -INFINITY;
+#pragma unroll 1
+    for (int m = 0; m < M; ++m) {
+      const double* blk = P.like_par + 1 + (size_t)m * (1 + n + n * n);  // c_m, mu_m, P_m
+      const double* frag = sprec + m * (MT * NR * 64);
+      double d[NR];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const bool ok = r < NR - 1 || 4 * r + t < n;
+        const double mu = blk[1 + (ok ? 4 * r + t : 0)];
+        d[r] = ok ? v[r] - mu : 0.0;
+      }
+      mfma_acc w[MT];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) w[mt] = (mfma_acc){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s = 0; s < NR; ++s)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) w[mt] = DH_MFMA_F64(frag[(mt * NR + s) * 64 + lane], d[s], w[mt]);
+      double q0 = 0.0, q1 = 0.0;
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        if (r & 1)
+          q1 = fma(d[r], w[r >> 2][r & 3], q1);
+        else
+          q0 = fma(d[r], w[r >> 2][r & 3], q0);
+      }
+      const double a_m = lp[1 + (size_t)m * (1 + n + n * n)] - 0.5 * grp_sum(q0 + q1);
+#pragma unroll
+      for (int k = 0; k < QMIX_MAX; ++k) am[k] = k == m ? a_m : am[k];
+    }
+    if (M == 1) return am[0];
+    return mix_combine_call(am[0], am[1], am[2], am[3], M);
   } else if (lid == LIKE_EGGBOX) {
     const double tmax = lp[0];
     double prod = 1.0;
@@ -1058,7 +1110,7 @@ __device__ __forceinline__ double loglike_quad(const ProblemDev& P, int n, int t
     const double b = 2.0 + grp_prod(prod);
     const double b2 = b * b;
     return b2 * b2 * b;
-  } else {
+  } else if (lid == LIKE_GAUSS_IID) {
     double q0 = 0.0, q1 = 0.0;
 #pragma unroll
     for (int r = 0; r < NR; ++r) {  // padded entries are 0
@@ -1068,6 +1120,8 @@ __device__ __forceinline__ double loglike_quad(const ProblemDev& P, int n, int t
         q0 = fma(v[r], v[r], q0);
     }
     return lp[0] - 0.5 * grp_sum(q0 + q1);
+  } else {
+    return __builtin_nan("");  // no four-lane evaluator for this id (rwalkq_launch refuses it)
   }
 }
 
@@ -1088,14 +1142,31 @@ __device__ __forceinline__ void prior_quad(const ProblemDev& P, int n, int t, co
 #pragma unroll
       for (int q = 0; q < NR; ++q) v[q] = q == r ? o : v[q];
     }
+  } else if (KIND == KIND_EXT && pid == PRIOR_TABLE) {
+    // a sub-lane holds the coordinates 4 r + t: the kinds differ over the sub-lanes of a wavefront, each lane reads
+    // the rows of its own coordinates and the three transforms are divergent branches behind one call
+#pragma unroll 1
+    for (int r = 0; r < NR; ++r) {
+      double x = 0.5;
+#pragma unroll
+      for (int q = 0; q < NR; ++q) x = q == r ? u[q] : x;
+      const bool ok = r < NR - 1 || 4 * r + t < n;
+      const double* row = P.prior_par + 3 * (ok ? 4 * r + t : 0);
+      const double o = ok ? table_coord_call(row[0], row[1], row[2], x) : 0.0;
+#pragma unroll
+      for (int q = 0; q < NR; ++q) v[q] = q == r ? o : v[q];
+    }
   } else if (pid == PRIOR_AFFINE) {
     cdptr pp = as_const(P.prior_par);
     const double a = pp[0], b = pp[1];
 #pragma unroll
     for (int r = 0; r < NR; ++r) v[r] = (r < NR - 1 || 4 * r + t < n) ? a * (2.0 * u[r] - 1.0) + b : 0.0;
-  } else {
+  } else if (pid == PRIOR_IDENTITY) {
 #pragma unroll
     for (int r = 0; r < NR; ++r) v[r] = (r < NR - 1 || 4 * r + t < n) ? u[r] : 0.0;
+  } else {  // no four-lane evaluator for this id (rwalkq_launch refuses it)
+#pragma unroll
+    for (int r = 0; r < NR; ++r) v[r] = __builtin_nan("");
   }
 }
 
@@ -1140,7 +1211,8 @@ __global__ void __launch_bounds__(256) rwalkq_kernel(RwalkQArgs a) {
   constexpr int STRIDE = RingGeom<NR>::stride;
   __shared__ __attribute__((aligned(16))) char zig_mem[RNG == RNGQ_PCG64 ? sizeof(ZigQ) : 16];
   __shared__ double ring_all[(RNG == RNGQ_ITEMS || RNG == RNGQ_ITEMS32) ? 1 : 64 * STRIDE];  // [walker slot][ring position]: the walkers' next items
-  __shared__ double sprec[MT * NR * 64];       // MFMA fragments of the precision matrix
+  // MFMA fragments of the precision matrix; KIND_EXT: of up to QMIX_MAX mixture components (32 KB at NR = 8)
+  __shared__ double sprec[(KIND == KIND_EXT ? QMIX_MAX : 1) * MT * NR * 64];
   __shared__ WaveGenLds gen_all[RNG == RNGQ_PCG64 ? 4 : 1];
   ZigQ& zig = *reinterpret_cast<ZigQ*>(zig_mem);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1164,6 +1236,18 @@ __global__ void __launch_bounds__(256) rwalkq_kernel(RwalkQArgs a) {
       const int l = f & 63, s = (f >> 6) % NR, mt = (f >> 6) / NR;
       const int row = 16 * mt + (l & 15), col = 4 * s + (l >> 4);
       sprec[f] = (row < n && col < n) ? Pm[row * n + col] : 0.0;
+    }
+  }
+  if constexpr (KIND == KIND_EXT) {
+    if (a.prob.like_id == LIKE_GAUSS_MIX) {
+      const int M = min((int)a.prob.like_par[0], (int)QMIX_MAX);  // (the launcher admits M <= QMIX_MAX only)
+      for (int f = tid; f < M * MT * NR * 64; f += 256) {
+        const int m = f / (MT * NR * 64), g = f % (MT * NR * 64);
+        const int l = g & 63, s = (g >> 6) % NR, mt = (g >> 6) / NR;
+        const int row = 16 * mt + (l & 15), col = 4 * s + (l >> 4);
+        const double* Pm = a.prob.like_par + 1 + (size_t)m * (1 + n + n * n) + 1 + n;
+        sprec[f] = (row < n && col < n) ? Pm[row * n + col] : 0.0;
+      }
     }
   }
   __syncthreads();
@@ -1447,7 +1531,10 @@ int rwalkq_launch(dh_ctx* ctx, const ProblemDev& prob, int k, int ndim, const do
                   const int32_t* axes_idx, double scale, double loglstar, int walks, const uint64_t* rng, double* u,
                   double* v, double* logl, int32_t* naccept, int32_t* nreject, uint64_t* rng_out,
                   const double* run_loglstar, const double* run_scale, const int* run_mode, int wpr, int my_mode,
-                  const PhiloxKey* philox, const int8_t* bc) {
+                  const PhiloxKey* philox, const int8_t* bc, int mix_m) {
+  if (!problem_has_quad_form(prob.like_id, prob.prior_id, mix_m))
+    return fail(ctx, DH_ERR_ARG, "rwalk: likelihood id %d (M = %d) / prior id %d have no four-lane evaluator",
+                prob.like_id, mix_m, prob.prior_id);
   RwalkQArgs a;
   a.prob = prob;
   a.bc = bc;
@@ -1483,7 +1570,8 @@ int rwalkq_launch(dh_ctx* ctx, const ProblemDev& prob, int k, int ndim, const do
   a.items32 = nullptr;
   a.wbase = 0;
   const dim3 block(256);
-  const int kind = problem_kind(prob.like_id, prob.prior_id) == KIND_PREC_AFFINE ? KIND_PREC_AFFINE : KIND_GENERIC;
+  const int pkind = problem_kind(prob.like_id, prob.prior_id);
+  const int kind = pkind == KIND_PREC_AFFINE || pkind == KIND_EXT ? pkind : KIND_GENERIC;
   const int nr = (ndim + 3) / 4;  // 2 <= ndim <= 32: 1 .. 8
   // the last column by vector instructions where it is the only live one of its K step (DH_RWALKQ_R1=0: the matrix form)
   const bool r1 = ndim % 4 == 1 && ndim >= 5 && !(getenv("DH_RWALKQ_R1") && atoi(getenv("DH_RWALKQ_R1")) == 0);
@@ -1507,6 +1595,8 @@ int rwalkq_launch(dh_ctx* ctx, const ProblemDev& prob, int k, int ndim, const do
   if (nr == NRR) {                     \
     if (kind == KIND_PREC_AFFINE)      \
       L(NRR, KIND_PREC_AFFINE, GRID);  \
+    else if (kind == KIND_EXT)         \
+      L(NRR, KIND_EXT, GRID);          \
     else                               \
       L(NRR, KIND_GENERIC, GRID);      \
   }

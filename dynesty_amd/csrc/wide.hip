@@ -89,6 +89,56 @@ __device__ __forceinline__ double wave_max(double v) {
   return wave_bcast63(v);
 }
 
+// PRIOR_TABLE / LIKE_GAUSS_MIX of the wide form (the EXT = true instances of the kernels only: see wide_logl).
+// A lane reads the table rows of the coordinates it owns; kinds differ from lane to lane, so the three transforms
+// are divergent branches, the Normal rows by AS 241 with the far tail as a call (ndtri_n<1>).
+__device__ __forceinline__ void wide_prior_table(const double* prior_par, int D, const double* su, double* sv,
+                                                           int lane) {
+  for (int i = lane; i < D; i += 64) {
+    const double kind = prior_par[3 * i], p0 = prior_par[3 * i + 1], p1 = prior_par[3 * i + 2];
+    const double x = su[i];
+    double o;
+    if (kind == (double)TABLE_UNIFORM) {
+      o = fma(x, p1, p0);
+    } else if (kind == (double)TABLE_NORMAL) {
+      double p[1] = {x}, z[1];
+      ndtri_n<1>(p, z);
+      o = p0 + p1 * z[0];
+    } else {
+      o = exp(fma(x, p1, p0));
+    }
+    sv[i] = o;
+  }
+}
+
+// One component after the other like the LIKE_GAUSS_PREC branch of wide_logl: a lane sums its rows of
+// (v - mu_m)^T P_m (v - mu_m), the wave adds them up; max / exp / log on the wave sums, so every lane returns the
+// same bits.  Called by all 64 lanes (wave_sum).
+__device__ __forceinline__ double wide_loglike_mix(const double* like_par, int D, const double* sv, int lane) {
+  const int M = __builtin_amdgcn_readfirstlane((int)like_par[0]);
+  const size_t stride = 1 + (size_t)D + (size_t)D * D;
+  double a[MIX_MAX];
+#pragma unroll
+  for (int k = 0; k < MIX_MAX; ++k) a[k] = -INFINITY;
+#pragma unroll 1
+  for (int m = 0; m < M; ++m) {
+    const double* cm = like_par + 1 + m * stride;
+    const double* mu = cm + 1;
+    const double* A = cm + 1 + D;
+    double q = 0.0;
+    for (int i = lane; i < D; i += 64) {
+      double r = 0.0;
+      const double* row = A + (size_t)i * D;
+      for (int j = 0; j < D; ++j) r = fma(row[j], sv[j] - mu[j], r);
+      q = fma(sv[i] - mu[i], r, q);
+    }
+    const double am = cm[0] - 0.5 * wave_sum(q);
+#pragma unroll
+    for (int k = 0; k < MIX_MAX; ++k) a[k] = k == m ? am : a[k];
+  }
+  return mix_combine(a, M);
+}
+
 // prior_transform + loglikelihood for one walker spread over a wave:
 // lane owns dims lane, lane+64, ...; u in LDS row `su` (D), v written to `sv`.
 // For LIKE_GAUSS_PREC the precision matrix is read from global memory.
@@ -97,8 +147,13 @@ __device__ __forceinline__ double wave_max(double v) {
 // square root, second pair of polynomials) only for the ~15 % that need it, compacted over the lanes -- about one
 // pass of the tail code for a 200-D walker instead of the four that evaluating both halves for every coordinate
 // costs.  The same expressions either way: the same bits.
+// EXT: with the DH_PRIOR_TABLE / DH_LIKE_GAUSS_MIX branches.  Every kernel that evaluates a problem exists twice: the
+// EXT = false instance holds none of their code (with it -- even behind one call -- wide_walk_kernel<rslice> spilled
+// 86 VGPRs against 11; the register budgets of tests/test_codegen_budget.py are this instance's), the EXT = true
+// instance serves the problems with one of the two ids (wide_ext: the launchers choose).
+template <bool EXT>
 __device__ __forceinline__ double wide_logl(const ProblemDev& P, int D, const double* su, double* sv, int lane,
-                                            double* tails = nullptr) {
+                                                 double* tails = nullptr) {
   // prior
   if (P.prior_id == PRIOR_AFFINE) {
     const double a = P.prior_par[0], b = P.prior_par[1];
@@ -164,11 +219,16 @@ __device__ __forceinline__ double wide_logl(const ProblemDev& P, int D, const do
       for (int q = 0; q < 4; ++q)
         if (i0 + 64 * q < D) sv[i0 + 64 * q] = mu + sg * o[q];
     }
-  } else {
+  } else if (EXT && P.prior_id == PRIOR_TABLE) {
+    wide_prior_table(P.prior_par, D, su, sv, lane);
+  } else if (P.prior_id == PRIOR_IDENTITY) {
     for (int i = lane; i < D; i += 64) sv[i] = su[i];
+  } else {  // an id no evaluator knows (the launchers refuse it): never another problem's values
+    for (int i = lane; i < D; i += 64) sv[i] = __builtin_nan("");
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
+  if (EXT && P.like_id == LIKE_GAUSS_MIX) return wide_loglike_mix(P.like_par, D, sv, lane);
   if (P.like_id == LIKE_GAUSS_PREC) {
     const double* A = P.like_par + 1;
     double q = 0.0;
@@ -186,10 +246,12 @@ __device__ __forceinline__ double wide_logl(const ProblemDev& P, int D, const do
     for (int i = 0; i < D; ++i) prod *= cos((2.0 * tmax * sv[i] - tmax) / 2.0);
     const double b = 2.0 + prod, b2 = b * b;
     return b2 * b2 * b;
-  } else {
+  } else if (P.like_id == LIKE_GAUSS_IID) {
     double q = 0.0;
     for (int i = lane; i < D; i += 64) q = fma(sv[i], sv[i], q);
     return P.like_par[0] - 0.5 * wave_sum(q);
+  } else {
+    return __builtin_nan("");  // an id no evaluator knows (the launchers refuse it)
   }
 }
 
@@ -210,13 +272,14 @@ __device__ __attribute__((noinline)) double wide_logl_call(int like_id, int prio
   P.like_par = like_par;
   P.prior_par = prior_par;
   P.prec_t = nullptr;
-  return wide_logl(P, D, su, sv, lane, tails);
+  return wide_logl<true>(P, D, su, sv, lane, tails);
 }
+inline bool wide_ext(const ProblemDev& P) { return P.like_id == LIKE_GAUSS_MIX || P.prior_id == PRIOR_TABLE; }
 #ifdef DH_WIDE_F_CALL
 #define WIDE_F(prob, D, su, sv, lane) \
   wide_logl_call((prob).like_id, (prob).prior_id, (prob).like_par, (prob).prior_par, (D), (su), (sv), (lane), wtails)
 #else
-#define WIDE_F(prob, D, su, sv, lane) wide_logl((prob), (D), (su), (sv), (lane), wtails)
+#define WIDE_F(prob, D, su, sv, lane) wide_logl<EXT>((prob), (D), (su), (sv), (lane), wtails)
 #endif
 
 // F(x) = logl(ptform(u + x * dir)) of the slice samplers from REGISTERS (round 4): for the iid Normal likelihood
@@ -443,8 +506,8 @@ constexpr int kWalkMaxWaves = 4;  // walkers per workgroup: one wavefront per SI
 // frame product of every walker read the clock twice -- s_memtime and, with it, a wait for every outstanding LDS
 // operation of the wavefront -- whether anybody looked at the numbers or not.
 #define WCLK() (a.dbg ? clock64() : 0ll)
-template <int KIND, int RNG>
-__global__ void __launch_bounds__(64 * kWalkMaxWaves, 2) wide_walk_kernel(WideWalkArgs a) {
+template <int KIND, int RNG, bool EXT>
+__device__ __forceinline__ void wide_walk_impl(const WideWalkArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ ZigLds zig;
   __shared__ int sframe[16];
@@ -907,7 +970,16 @@ struct WideUnifArgs {
 };
 
 #undef WCLK
-template <int RNG>
+template <int KIND, int RNG>
+__global__ void __launch_bounds__(64 * kWalkMaxWaves, 2) wide_walk_kernel(WideWalkArgs a) {
+  wide_walk_impl<KIND, RNG, false>(a);
+}
+template <int KIND, int RNG>
+__global__ void __launch_bounds__(64 * kWalkMaxWaves, 2) wide_walk_ext_kernel(WideWalkArgs a) {
+  wide_walk_impl<KIND, RNG, true>(a);
+}
+
+template <int RNG, bool EXT>
 __global__ void __launch_bounds__(64) wide_unif_kernel(WideUnifArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ ZigLds zig;
@@ -944,7 +1016,7 @@ __global__ void __launch_bounds__(64) wide_unif_kernel(WideUnifArgs a) {
       g.doubles(sx, D, lane);
       lds_sync();
       if (a.propose_only) break;
-      const double ll0 = wide_logl(a.prob, D, sx, sv, lane);
+      const double ll0 = wide_logl<EXT>(a.prob, D, sx, sv, lane);
       lds_sync();
       ++ncall;
       if (ll0 > loglstar) {
@@ -1016,7 +1088,7 @@ __global__ void __launch_bounds__(64) wide_unif_kernel(WideUnifArgs a) {
       lds_sync();
     }
     if (a.propose_only) break;
-    const double ll = wide_logl(a.prob, D, sx, sv, lane);
+    const double ll = wide_logl<EXT>(a.prob, D, sx, sv, lane);
     lds_sync();
     ++ncall;
     if (ll > loglstar) {
@@ -1038,6 +1110,7 @@ __global__ void __launch_bounds__(64) wide_unif_kernel(WideUnifArgs a) {
   }
 }
 
+template <bool EXT>
 __global__ void __launch_bounds__(64)
     wide_eval_kernel(ProblemDev prob, int k, const double* __restrict__ u, double* v, double* logl) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1046,7 +1119,7 @@ __global__ void __launch_bounds__(64)
   double* sv = su + D;
   for (int i = lane; i < D; i += 64) su[i] = u[(size_t)w * D + i];
   lds_sync();
-  const double ll = wide_logl(prob, D, su, sv, lane);
+  const double ll = wide_logl<EXT>(prob, D, su, sv, lane);
   lds_sync();
   for (int i = lane; i < D; i += 64) v[(size_t)w * D + i] = sv[i];
   if (lane == 0) logl[w] = ll;
@@ -2485,13 +2558,19 @@ int wide_walk_launch(dh_ctx* ctx, int kind, int problem, int k, int ndim, int nc
   if (const char* e = getenv("DH_WIDE_WPW")) wpw = std::max(1, std::min(wpw, atoi(e)));
   wpw = std::max(1, std::min(wpw, k));
   const size_t lds = per_wave * wpw;
-  static size_t lds_attr_dev[kMaxDev][8] = {};
+  static size_t lds_attr_dev[kMaxDev][16] = {};
   size_t* lds_attr = lds_attr_dev[ctx->device & (kMaxDev - 1)];
-  const int kk = (kind < 0 || kind > 3 ? 3 : kind) + (philox ? 4 : 0);
-  const void* fns[8] = {(const void*)wide_walk_kernel<0, RNG_PCG64>,  (const void*)wide_walk_kernel<1, RNG_PCG64>,
-                        (const void*)wide_walk_kernel<2, RNG_PCG64>,  (const void*)wide_walk_kernel<3, RNG_PCG64>,
-                        (const void*)wide_walk_kernel<0, RNG_PHILOX>, (const void*)wide_walk_kernel<1, RNG_PHILOX>,
-                        (const void*)wide_walk_kernel<2, RNG_PHILOX>, (const void*)wide_walk_kernel<3, RNG_PHILOX>};
+  // (+ 8: the instances with the DH_PRIOR_TABLE / DH_LIKE_GAUSS_MIX evaluators)
+  const int kk = (kind < 0 || kind > 3 ? 3 : kind) + (philox ? 4 : 0) + (wide_ext(a.prob) ? 8 : 0);
+  const void* fns[16] = {
+      (const void*)wide_walk_kernel<0, RNG_PCG64>,      (const void*)wide_walk_kernel<1, RNG_PCG64>,
+      (const void*)wide_walk_kernel<2, RNG_PCG64>,      (const void*)wide_walk_kernel<3, RNG_PCG64>,
+      (const void*)wide_walk_kernel<0, RNG_PHILOX>,     (const void*)wide_walk_kernel<1, RNG_PHILOX>,
+      (const void*)wide_walk_kernel<2, RNG_PHILOX>,     (const void*)wide_walk_kernel<3, RNG_PHILOX>,
+      (const void*)wide_walk_ext_kernel<0, RNG_PCG64>,  (const void*)wide_walk_ext_kernel<1, RNG_PCG64>,
+      (const void*)wide_walk_ext_kernel<2, RNG_PCG64>,  (const void*)wide_walk_ext_kernel<3, RNG_PCG64>,
+      (const void*)wide_walk_ext_kernel<0, RNG_PHILOX>, (const void*)wide_walk_ext_kernel<1, RNG_PHILOX>,
+      (const void*)wide_walk_ext_kernel<2, RNG_PHILOX>, (const void*)wide_walk_ext_kernel<3, RNG_PHILOX>};
   if (lds > lds_attr[kk]) {
     if (!hip_ok(ctx, hipFuncSetAttribute(fns[kk], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
                 "hipFuncSetAttribute(wide_walk)"))
@@ -2499,16 +2578,8 @@ int wide_walk_launch(dh_ctx* ctx, int kind, int problem, int k, int ndim, int nc
     lds_attr[kk] = lds;
   }
   const dim3 grid((k + wpw - 1) / wpw), block(64 * wpw);
-  switch (kk) {
-    case 0: hipLaunchKernelGGL((wide_walk_kernel<0, RNG_PCG64>), grid, block, lds, ctx->stream, a); break;
-    case 1: hipLaunchKernelGGL((wide_walk_kernel<1, RNG_PCG64>), grid, block, lds, ctx->stream, a); break;
-    case 2: hipLaunchKernelGGL((wide_walk_kernel<2, RNG_PCG64>), grid, block, lds, ctx->stream, a); break;
-    case 3: hipLaunchKernelGGL((wide_walk_kernel<3, RNG_PCG64>), grid, block, lds, ctx->stream, a); break;
-    case 4: hipLaunchKernelGGL((wide_walk_kernel<0, RNG_PHILOX>), grid, block, lds, ctx->stream, a); break;
-    case 5: hipLaunchKernelGGL((wide_walk_kernel<1, RNG_PHILOX>), grid, block, lds, ctx->stream, a); break;
-    case 6: hipLaunchKernelGGL((wide_walk_kernel<2, RNG_PHILOX>), grid, block, lds, ctx->stream, a); break;
-    default: hipLaunchKernelGGL((wide_walk_kernel<3, RNG_PHILOX>), grid, block, lds, ctx->stream, a); break;
-  }
+  void* kargs[] = {(void*)&a};  // (one list of instances: the table above)
+  if (!hip_ok(ctx, hipLaunchKernel(fns[kk], grid, block, kargs, lds, ctx->stream), "wide walk launch")) return DH_ERR_HIP;
   return hip_ok(ctx, hipGetLastError(), "wide walk launch") ? DH_OK : DH_ERR_HIP;
 }
 
@@ -2572,17 +2643,26 @@ int wide_unif_launch(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, int m
   a.zki = ctx->zki();
   a.zwi = ctx->zwi();
   a.zfi = ctx->zfi();
-  if (philox)
-    hipLaunchKernelGGL(wide_unif_kernel<RNG_PHILOX>, dim3(k), dim3(64), (size_t)(ncdim + 2 * ndim) * 8, ctx->stream, a);
-  else
-    hipLaunchKernelGGL(wide_unif_kernel<RNG_PCG64>, dim3(k), dim3(64), (size_t)(ncdim + 2 * ndim) * 8, ctx->stream, a);
+  if (philox) {
+    if (wide_ext(a.prob))
+      hipLaunchKernelGGL((wide_unif_kernel<RNG_PHILOX, true>), dim3(k), dim3(64), (size_t)(ncdim + 2 * ndim) * 8, ctx->stream, a);
+    else
+      hipLaunchKernelGGL((wide_unif_kernel<RNG_PHILOX, false>), dim3(k), dim3(64), (size_t)(ncdim + 2 * ndim) * 8, ctx->stream, a);
+  } else {
+    if (wide_ext(a.prob))
+      hipLaunchKernelGGL((wide_unif_kernel<RNG_PCG64, true>), dim3(k), dim3(64), (size_t)(ncdim + 2 * ndim) * 8, ctx->stream, a);
+    else
+      hipLaunchKernelGGL((wide_unif_kernel<RNG_PCG64, false>), dim3(k), dim3(64), (size_t)(ncdim + 2 * ndim) * 8, ctx->stream, a);
+  }
   return hip_ok(ctx, hipGetLastError(), "wide unif launch") ? DH_OK : DH_ERR_HIP;
 }
 
 int wide_eval_launch(dh_ctx* ctx, const ProblemDev& p, int k, const double* u, double* v, double* logl) {
   if (p.ndim > kWideMaxD) return fail(ctx, DH_ERR_ARG, "ndim=%d exceeds the wide-D limit %d", p.ndim, kWideMaxD);
-  hipLaunchKernelGGL(wide_eval_kernel, dim3(k), dim3(64), (size_t)2 * p.ndim * 8, ctx->stream, p, k, u, v,
-                     logl);
+  if (wide_ext(p))
+    hipLaunchKernelGGL(wide_eval_kernel<true>, dim3(k), dim3(64), (size_t)2 * p.ndim * 8, ctx->stream, p, k, u, v, logl);
+  else
+    hipLaunchKernelGGL(wide_eval_kernel<false>, dim3(k), dim3(64), (size_t)2 * p.ndim * 8, ctx->stream, p, k, u, v, logl);
   return hip_ok(ctx, hipGetLastError(), "wide eval launch") ? DH_OK : DH_ERR_HIP;
 }
 

@@ -52,6 +52,21 @@ extern "C" {
 #define DH_PRIOR_IDENTITY 0  /* v = u                                            */
 #define DH_PRIOR_AFFINE 1    /* v = a (2u - 1) + b              par = [a, b]     */
 #define DH_PRIOR_NORMAL 2    /* v = mu + sigma ndtri(u)         par = [mu, sigma]*/
+/* The two ids below are created through dh_problem_create_ex only (dh_problem_create refuses them).
+ * DH_LIKE_GAUSS_MIX: logl = a* + log(sum_m exp(a_m - a*)), a* = max_m a_m,
+ *                    a_m = c_m - (v - mu_m)^T P_m (v - mu_m) / 2;  M = 1 gives a_0 itself (no exp, no log)
+ *   par = [M, then per component m: c_m, mu_m (ndim), P_m (ndim x ndim, row-major)],  1 <= M <= DH_MIX_MAX;
+ *   c_m = ln w_m + ln det P_m / 2 - (ndim / 2) ln 2 pi for a normalised mixture.  Every P_m is stored symmetrised.
+ * DH_PRIOR_TABLE: one row [kind, p0, p1] per coordinate, par = ndim rows
+ *   DH_TABLE_UNIFORM     v = fma(u, p1, p0)        p0 = lo,     p1 = hi - lo     (p1 > 0)
+ *   DH_TABLE_NORMAL      v = p0 + p1 ndtri(u)      p0 = mu,     p1 = sigma       (p1 > 0)
+ *   DH_TABLE_LOGUNIFORM  v = exp(fma(u, p1, p0))   p0 = ln lo,  p1 = ln(hi / lo) */
+#define DH_LIKE_GAUSS_MIX 3
+#define DH_PRIOR_TABLE 3
+#define DH_MIX_MAX 8
+#define DH_TABLE_UNIFORM 0
+#define DH_TABLE_NORMAL 1
+#define DH_TABLE_LOGUNIFORM 2
 
 /* per-dimension boundary flags (reference kwargs periodic / reflective,
  * utils.py:950-976 get_nonbounded) */
@@ -90,6 +105,15 @@ int dh_event_elapsed_ms(dh_ctx* ctx, void* ev0, void* ev1, double* ms); /* syncs
 int dh_problem_create(dh_ctx* ctx, int ndim, int like_id, const double* like_par,
                       int n_like_par, int prior_id, const double* prior_par,
                       int n_prior_par);
+/* Every id 0..3 in any pairing.  A pair of the ids 0..2 goes to dh_problem_create unchanged (same checks, same
+ * stored bits).  With DH_LIKE_GAUSS_MIX or DH_PRIOR_TABLE it answers DH_ERR_ARG (message in dh_last_error) for: M
+ * outside 1..DH_MIX_MAX or not an integer; n_like_par != 1 + M (1 + ndim + ndim^2); n_prior_par != 3 ndim; a table
+ * kind outside 0..2; a parameter that is not finite; p1 <= 0 in a uniform or normal row; a diagonal entry <= 0 of a
+ * P_m.  The parameters of an older id paired with a new one are held to dh_problem_create's rules (at least the count
+ * that id needs; DH_PRIOR_AFFINE's a and DH_PRIOR_NORMAL's sigma are not required to be positive), plus finiteness. */
+int dh_problem_create_ex(dh_ctx* ctx, int ndim, int like_id, const double* like_par,
+                         int n_like_par, int prior_id, const double* prior_par,
+                         int n_prior_par);
 int dh_problem_destroy(dh_ctx* ctx, int problem);
 /* logl/v for k points: the batched form of loglikelihood(prior_transform(u)) */
 int dh_problem_eval(dh_ctx* ctx, int problem, int k, const double* u, double* v,
