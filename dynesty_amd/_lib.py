@@ -125,6 +125,10 @@ SIGNATURES = {
     "dh_ns_set_boundary": (_i, [_vp, _i, _vp]),
     "dh_ns_keep": (_i, [_vp, _i]),
     "dh_ns_release": (_i, [_vp]),
+    "dh_ns_continue": (_i, [_vp, _dbl, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dh_ns_state_size": (_i, [_vp, _vp]),
+    "dh_ns_state_export": (_i, [_vp, _vp, _u64]),
+    "dh_ns_state_import": (_i, [_vp, _i, _vp, _u64, C.c_int64]),
     "dh_merge_runs": (_i, [_vp, _i, _i, _i, _i, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dh_merge_kept": (_i, [_vp, _i, _vp, _vp]),
     "dh_merged_fetch": (_i, [_vp, _i, C.c_int64, C.c_int64, _vp]),
@@ -566,6 +570,7 @@ class Context:
         self.device = int(device)
         self._problems = {}
         self._merge_serial = 0  # which merge the context's merged run is (DeviceMergedRun)
+        self._kept_shape = None  # (runs, nlive, ndim, max_iter) of the kept ensemble: ns_continue's host buffers
 
     def close(self):
         if getattr(self, "handle", None):
@@ -654,6 +659,7 @@ class Context:
 
     def release_kept(self):
         self._check(self.lib.dh_ns_release(self.handle))
+        self._kept_shape = None
 
     def set_rwalk_form(self, form):
         """0 (default) / 2: four lanes per walker + matrix cores (csrc/walkq.hip) wherever that kernel is
@@ -1309,6 +1315,8 @@ class Context:
                    nbound=rec[:, 5].astype(np.int64),
                    status=rec[:, 6].astype(np.int64), eff=rec[:, 7],
                    nfills=nf.value)
+        if keep:
+            self._kept_shape = (int(runs), int(nlive), nd, int(max_iter))
         if want_dead_logl:
             out["dead_logl"] = dead
             out["live_logl"] = livel
@@ -1317,6 +1325,81 @@ class Context:
             out["live_u"] = live_u
             out["dead_id"], out["dead_it"], out["dead_nc"], out["live_it"] = pid, pit, pnc, lit
         return out
+
+    def ns_continue(self, dlogz=0.01, max_fills=0, maxiter=None, maxcall=None, logl_max=None, add_live=True,
+                    want_dead_logl=False, want_samples=False):
+        """dh_ns_continue: takes the ensemble that ns_ensemble(keep=True) (or ns_load) left on the device further, as
+        calling run_nested again does in the reference.  dlogz, maxiter, maxcall, logl_max and add_live are this
+        call's; maxiter and maxcall are TOTALS of the run (iterations and calls since it began -- the reference counts
+        them per call: add the records' niter / ncall for a per-call budget).  Everything else is the first call's.
+        Runs the criteria already stop stay as they are (unchanged criteria: a no-op with nfills 0); runs that
+        max_fills stopped (status 1) go on; failed runs stay failed.  max_fills bounds the fills of THIS call.
+        Returns the dict of ns_ensemble (arrays over the whole run, dead rows runs x max_iter of the first call) plus
+        `rest`: per run, the queue entries behind the stop that the run took over.  The ensemble stays kept."""
+        if self._kept_shape is None:
+            raise ValueError("ns_continue: the context holds no kept ensemble (ns_ensemble(keep=True) or ns_load)")
+        runs, nlive, nd, max_iter = self._kept_shape
+        rec = np.empty((runs, 8))
+        want_dead_logl = want_dead_logl or want_samples
+        dead = np.empty((runs, max_iter)) if want_dead_logl else None
+        livel = np.empty((runs, nlive)) if want_dead_logl else None
+        dead_u = np.empty((runs, max_iter, nd)) if want_samples else None
+        live_u = np.empty((runs, nlive, nd)) if want_samples else None
+        pid = np.empty((runs, max_iter), dtype=np.int32) if want_samples else None
+        pit = np.empty((runs, max_iter), dtype=np.int32) if want_samples else None
+        pnc = np.empty((runs, max_iter), dtype=np.int32) if want_samples else None
+        lit = np.empty((runs, nlive), dtype=np.int32) if want_samples else None
+        rest = np.zeros(runs, dtype=np.int32)
+        nf = C.c_int64(0)
+        nan = float('nan')
+        # (only the four options a continuation takes are set: one of the others, set by the caller, is refused)
+        for key, val in ((3, nan if maxiter is None else float(maxiter)), (4, nan if maxcall is None else float(maxcall)),
+                         (5, nan if logl_max is None else float(logl_max)), (6, nan if add_live else 0.0)):
+            self._check(self.lib.dh_ns_set_option(self.handle, key, val))
+        self._check_merge(self.lib.dh_ns_continue(
+            self.handle, float(dlogz), int(max_fills), _ptr(rec), _ptr(dead), _ptr(livel), _ptr(dead_u), _ptr(live_u),
+            C.byref(nf), _ptr(pid), _ptr(pit), _ptr(pnc), _ptr(lit), _ptr(rest)))
+        out = dict(logz=rec[:, 0], logzerr=rec[:, 1], niter=rec[:, 2].astype(np.int64),
+                   ncall=rec[:, 3].astype(np.int64), h=rec[:, 4], nbound=rec[:, 5].astype(np.int64),
+                   status=rec[:, 6].astype(np.int64), eff=rec[:, 7], nfills=nf.value, rest=rest.astype(np.int64))
+        if want_dead_logl:
+            out["dead_logl"] = dead
+            out["live_logl"] = livel
+        if want_samples:
+            out["dead_u"] = dead_u
+            out["live_u"] = live_u
+            out["dead_id"], out["dead_it"], out["dead_nc"], out["live_it"] = pid, pit, pnc, lit
+        return out
+
+    def ns_state(self):
+        """dh_ns_state_export: the kept ensemble as one np.uint8 array -- a header, the first call's plan and the state
+        arrays, the dead points' by the rows each run produced (the size does not depend on max_iter)."""
+        n = C.c_uint64(0)
+        self._check_merge(self.lib.dh_ns_state_size(self.handle, C.byref(n)))
+        buf = np.empty(int(n.value), dtype=np.uint8)
+        self._check_merge(self.lib.dh_ns_state_export(self.handle, _ptr(buf), buf.size))
+        return buf
+
+    def ns_save(self, path):
+        """ns_state() written to `path` (through a temporary file beside it, renamed when complete)."""
+        tmp = f"{path}.tmp"
+        with open(tmp, "wb") as f:
+            f.write(self.ns_state().tobytes())
+        os.replace(tmp, path)
+
+    def ns_load(self, prob, path_or_array, max_iter=None):
+        """dh_ns_state_import: installs a saved ensemble as the context's kept one (ns_continue, merge_kept).  prob
+        must be the problem the ensemble was run on -- only its ndim can be checked; max_iter: the dead-point capacity,
+        None = as saved, else >= every run's niter.  A rejected image (ValueError) leaves the context as it was."""
+        if isinstance(path_or_array, (str, bytes, os.PathLike)):
+            buf = np.fromfile(path_or_array, dtype=np.uint8)
+        else:
+            buf = np.ascontiguousarray(path_or_array, dtype=np.uint8).reshape(-1)
+        self._check_merge(self.lib.dh_ns_state_import(self.handle, self.problem(prob), _ptr(buf), buf.size,
+                                                      0 if max_iter is None else int(max_iter)))
+        hdr = np.frombuffer(buf[:88].tobytes(), dtype=np.int32)  # csrc/ns_state.h: Header
+        cap = int(np.frombuffer(buf[40:48].tobytes(), dtype=np.int64)[0])
+        self._kept_shape = (int(hdr[6]), int(hdr[7]), int(hdr[8]), cap if max_iter is None else int(max_iter))
 
     # ---- RadFriends / SupFriends ------------------------------------------
     def bootstrap_expand(self, points, ent, bootstrap, multi, want_n_in=False):

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -49,6 +50,9 @@ struct dh_kept {
   const double *dead_logl = nullptr, *live_logl = nullptr, *dead_u = nullptr, *live_u = nullptr;
   const int *dead_id = nullptr, *dead_it = nullptr, *dead_nc = nullptr, *live_it = nullptr;
   std::vector<long long> niter;  // per run, from the records
+  // what dh_ns_continue / dh_ns_state_export need beyond the arrays (ns.hip: the first call's plan, its carved
+  // pointers, the fill counter); freed with the ensemble
+  std::shared_ptr<void> loop;
 };
 
 // The merged run of the last dh_merge_runs / dh_merge_kept (merge.hip): one allocation, M points in merged order; its

@@ -12,7 +12,9 @@
 //              ns_gather   (the walkers' start coordinates)
 //              ns_consume  (queue consumption per run: slots sorted once, deaths walk that
 //                           order; dead-point record, evidence integration, tuning)
-//   at the end: ns_finish  (append the final live points, write the record)
+//   at the end: ns_finish  (append the final live points, write the record; reads the state, changes nothing)
+//   dh_ns_continue (a kept ensemble taken further): ns_resume (which runs go on; a fill that a stop rule cut
+//              short is put back) and one ns_consume replay of those fills, then the fills as above
 //
 // All state (live points, dead points, integrals, RNG) stays in HBM; with
 // 288 GB there is room for the full dead-point history of thousands of runs.
@@ -27,6 +29,7 @@
 
 #include "ctx.h"
 #include "ns_sort.h"
+#include "ns_state.h"
 #include "rng_pcg64.h"
 
 using namespace dh;
@@ -54,7 +57,10 @@ struct NsRun {
   int pcount, sampler_failed;  // (sampler_failed: a uniform-sampler walker gave up, see ns_consume)
   // forced_exact: a start point of the run's CURRENT queue (selected, kept) lies outside its bound and the forced
   // update waits for the next fill that builds bounds; the run proposes and consumes nothing until then
-  int fpend, pad_;
+  // qstop (kept ensembles, dh_ns_continue): > 0 = a stop rule ended the run inside a fill after this many of the
+  // queue's entries, and what the fill found before it is saved (NsArgs::sv_*); -1 = ns_resume has put that state back
+  // and the fill is consumed again, whole, under the call's criteria; 0 otherwise
+  int fpend, qstop;
   double plogdvol, var_a, var_b;
 };
 
@@ -146,6 +152,18 @@ struct NsArgs {
   int* dead_id;  // like dead_logl: slot of the dead point                        ('id')
   int* dead_it;  //                 iteration at which it had been proposed        ('it')
   int* dead_nc;  //                 likelihood calls spent to replace it           ('nc')
+  // Kept ensembles (dh_ns_keep; null together otherwise): what the fill in which a stop rule ended a run found before
+  // it -- the run's state and the previous content of the slots the fill replaced -- so that dh_ns_continue can take
+  // the whole fill again under other criteria (ns_resume puts it back, `replay` consumes the same r_* rows)
+  NsRun* sv_st;      // runs
+  double* sv_u;      // runs x K x ndim
+  double* sv_v;      // runs x K x ndim
+  double* sv_logl;   // runs x K
+  int* sv_slot;      // runs x K
+  int* sv_it;        // runs x K   (live_it of the slot)
+  int* sv_n;         // runs: slots saved
+  int* rest;         // runs: queue entries the continuation took over (ns_resume)
+  int replay;        // 1: ns_consume serves the runs with qstop == -1 only; no tuning, no fill count
 };
 
 __device__ __forceinline__ double logaddexp_dev(double x, double y) {
@@ -201,7 +219,7 @@ __global__ void __launch_bounds__(kT)
     r.nbound = 0;
     r.nfill = 0;
     r.acc = r.rej = r.doubling = r.due = 0;
-    r.fpend = r.pad_ = 0;
+    r.fpend = r.qstop = 0;
     r.logzvar = 0.0;
     r.nc_carry = 0;
     r.pcount = r.sampler_failed = 0;
@@ -342,7 +360,8 @@ __global__ void __launch_bounds__(kT) ns_prepare(NsArgs a) {
       }
     }
     r.need_rebuild = need;
-    if (a.force) a.force[run] = 0;
+    // (a finished run keeps the flag of its last fill: a continuation's first ns_prepare reads it, dh_ns_continue)
+    if (a.force && r.mode != MODE_DONE) a.force[run] = 0;
     a.rebuild_mask[run] = need;
     a.run_mode[run] = (r.due || (r.fpend && !a.rebuild_fill)) ? MODE_WAIT : r.mode;
     if (a.fx_kind) a.fx_kind[run] = need ? 1 : 0;
@@ -1163,6 +1182,42 @@ __device__ int consume_parallel(const double* skey, const unsigned short* sidx, 
   return 1;
 }
 
+// Kept ensembles: a stop rule ended the run inside this fill.  What the fill found is put aside before ns_consume
+// changes it -- the run's state and what the slots the fill replaces (src[s] >= 0; compact slots translated by cslot)
+// hold now -- so that a continuation can take the fill again from its beginning (ns_resume).  All threads call it.
+// (the arrays one by one: a reference to NsArgs would put the whole argument block on the caller's stack)
+__device__ __attribute__((noinline)) void ns_save_fill(NsRun* sv_st, const NsRun* st, int* sv_slot, double* sv_logl,
+                                                       int* sv_it, const int* live_it, double* sv_u, double* sv_v,
+                                                       const double* live_u, const double* live_v, int* sv_n, int N,
+                                                       int D, int K, int run, const int* src, const double* skey,
+                                                       const unsigned short* cslot, int NC, int* list, int* count) {
+  const int t = threadIdx.x;
+  if (t == 0) {
+    sv_st[run] = st[run];
+    *count = 0;
+  }
+  __syncthreads();
+  for (int s = t; s < NC; s += kT)
+    if (src[s] >= 0) {
+      const int c = atomicAdd(count, 1), rs = cslot ? (int)cslot[s] : s;  // at most K slots change
+      const size_t o = (size_t)run * K + c;
+      list[c] = rs;
+      sv_slot[o] = rs;
+      sv_logl[o] = skey[s];
+      sv_it[o] = live_it ? live_it[(size_t)run * N + rs] : 0;
+    }
+  __syncthreads();
+  const int nsv = *count;
+  for (int x = t; x < nsv * D; x += kT) {
+    const int c = x / D, j = x - c * D;
+    const size_t from = ((size_t)run * N + list[c]) * D + j, to = ((size_t)run * K + c) * D + j;
+    sv_u[to] = live_u[from];
+    sv_v[to] = live_v[from];
+  }
+  if (t == 0) sv_n[run] = nsv;
+  __syncthreads();
+}
+
 template <int kEPT>
 __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1171,8 +1226,12 @@ __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
   NsRun& r = a.st[run];
   const int mode = r.mode;
   if (mode != MODE_CUBE && mode != MODE_BOUND) return;
-  if (a.run_mode && a.run_mode[run] == MODE_WAIT) return;
-  if (mode == MODE_BOUND && a.bstatus[run] != DH_OK) return;
+  if (a.replay) {
+    if (r.qstop != -1) return;  // (dh_ns_continue: only the runs whose last fill ns_resume has put back)
+  } else {
+    if (a.run_mode && a.run_mode[run] == MODE_WAIT) return;
+    if (mode == MODE_BOUND && a.bstatus[run] != DH_OK) return;
+  }
   long long pt_ = a.prof ? clock64() : 0;
   // NC = the slots the consumption works on: all of them, or the K + 1 smallest in slot order (ns_consume_compact)
   const bool compact = ns_consume_compact(N, K);
@@ -1753,6 +1812,11 @@ __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
     }
   }
   __syncthreads();
+  // (kept ensembles, once per run and call: behind a call of its own, so that the fills that do not stop carry
+  // nothing of it in their registers)
+  if (stopped && a.sv_st)
+    ns_save_fill(a.sv_st, a.st, a.sv_slot, a.sv_logl, a.sv_it, a.live_it, a.sv_u, a.sv_v, a.live_u, a.live_v, a.sv_n, N, D, K,
+                 run, src, skey, compact ? cslot : nullptr, NC, bslot, &misc[5]);
   if (t == 0) {
     const double hsum = wred[0][0] + wred[0][1] + wred[0][2] + wred[0][3];
     r.ncall += lred[0] + lred[1] + lred[2] + lred[3];
@@ -1780,7 +1844,8 @@ __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
       }
     }
     r.loglstar = bcast[2];
-    r.nfill += 1;
+    r.nfill += a.replay ? 0 : 1;
+    r.qstop = stopped ? dj[E] + 1 : 0;
     {
       // entries popped after the last kept death found no worse point to replace any more in this fill: the
       // reference goes on popping from the refilled queue within the same iteration, so their calls belong
@@ -1789,7 +1854,7 @@ __global__ void __launch_bounds__(kT) ns_consume(NsArgs a) {
       for (int j = nkeep > 0 ? dj[E] + 1 : 0; j <= jlast; ++j) c += qc[j];
       r.nc_carry = c;
     }
-    if (mode == MODE_BOUND && a.sampler != 3) {
+    if (mode == MODE_BOUND && a.sampler != 3 && !a.replay) {  // (a fill taken again was tuned from when it stopped)
       const int ta = racc[0], tr = rrej[0];
       if (a.sampler == 0) {
         // RWalkSampler.tune (internal_samplers.py:460-493), once per queue fill
@@ -2091,6 +2156,70 @@ __global__ void __launch_bounds__(kT) ns_finish(NsArgs a) {
   }
 }
 
+// ---- dh_ns_continue: which runs of a kept ensemble go on, one workgroup per run ------------------------------------
+// The reference's tests at the top of the loop (sampler.py:1071-1100, ns_state.h) on the state the last call left,
+// under THIS call's criteria.  A run for which one holds is MODE_DONE (again) with nothing new; a failed run stays
+// failed; a run that max_fills stopped simply goes on.  A run that a stop rule ended inside a fill gets back what
+// that fill found -- its state (NsArgs::sv_st; the scale tuned from that fill, the fill count and the sampler's
+// flags stay) and the previous content of the slots the fill replaced -- and is marked for ns_consume's replay,
+// which takes the fill's r_* rows again, whole: the entries behind the stop are not lost (the reference keeps its
+// queue), and the fill's evidence sums are those of the uninterrupted run to the last bit, which the sums of two
+// partial consumptions would not be.  ndone[0] / ndone[1] are counted anew.
+__global__ void __launch_bounds__(kT) ns_resume(NsArgs a) {
+  const int run = blockIdx.x, t = threadIdx.x, N = a.nlive, D = a.ndim, K = a.K;
+  NsRun& r = a.st[run];
+  __shared__ int back;
+  if (t == 0) {
+    int rest = 0, put_back = 0;
+    if (r.mode != MODE_FAILED) {
+      const dh_ns_state::StopState s = {r.logvol, r.logz, r.lmax, r.loglstar, r.dead_prev, r.it, r.ncall};
+      const dh_ns_state::StopRule c = {a.dlogz, a.logl_max, a.maxiter, a.maxcall};
+      if (dh_ns_state::stop_mask(s, c)) {
+        if (r.mode != MODE_DONE) r.qstop = 0;
+        r.mode = MODE_DONE;
+      } else if (r.mode == MODE_DONE) {
+        if (r.qstop > 0 && a.sv_st) {
+          NsRun b = a.sv_st[run];
+          rest = K - r.qstop;
+          b.scale = r.scale;
+          b.nfill = r.nfill;
+          b.doubling = r.doubling;
+          b.sampler_failed = r.sampler_failed;
+          b.qstop = -1;
+          r = b;
+          put_back = 1;
+        } else {
+          r.mode = r.nbound > 0 ? MODE_BOUND : MODE_CUBE;
+          r.qstop = 0;
+        }
+      }
+    }
+    a.rest[run] = rest;
+    back = put_back;
+    if (r.mode == MODE_DONE || r.mode == MODE_FAILED) atomicAdd(a.ndone, 1);
+    if (r.mode == MODE_CUBE) atomicOr(a.ndone + 1, 1);
+  }
+  __syncthreads();
+  if (!back) return;
+  // (the counts and slots come from ns_consume -- or from an imported image: nothing outside the run's rows is written)
+  int n = a.sv_n[run];
+  n = n < 0 ? 0 : n > K ? K : n;
+  for (int c = t; c < n; c += kT) {
+    const size_t o = (size_t)run * K + c;
+    if (a.sv_slot[o] < 0 || a.sv_slot[o] >= N) continue;
+    const size_t sl = (size_t)run * N + a.sv_slot[o];
+    a.live_logl[sl] = a.sv_logl[o];
+    if (a.live_it) a.live_it[sl] = a.sv_it[o];
+  }
+  for (int x = t; x < n * D; x += kT) {
+    const int c = x / D, j = x - c * D, slot = a.sv_slot[(size_t)run * K + c];
+    if (slot < 0 || slot >= N) continue;
+    const size_t from = ((size_t)run * K + c) * D + j, to = ((size_t)run * N + slot) * D + j;
+    a.live_u[to] = a.sv_u[from];
+    a.live_v[to] = a.sv_v[from];
+  }
+}
+
 }  // namespace
 
 namespace {
@@ -2128,6 +2257,11 @@ struct NsPlan {
   int64_t fills_cap;
   int n_frames;
   dh::PhiloxKey key;  // seed and first subsequence of the call (ns_philox_key)
+  // (set by dh_ns_ensemble, not by ns_plan) the ensemble is kept: the arrays of NsArgs::sv_st exist; the entropy
+  // words' count and whether boundary flags were installed -- with them ns_arrays is a function of the plan alone
+  bool keep;
+  int n_words;
+  bool have_bc;
 };
 
 // the arrays of the state allocation that no kernel takes through NsArgs
@@ -2301,11 +2435,16 @@ dh::PhiloxKey ns_philox_key(const NsPlan& p, NsStage stage, int64_t fill) {
 
 // Walks the list of state arrays: without a base it adds up their sizes (256-byte aligned), with one it hands out the
 // pointers and enqueues the initial fills.  An array that is not wanted takes no room and stays null.
+struct NsEntry {  // one array of the allocation: where it starts and its bytes
+  size_t off, bytes;
+};
 struct NsCarver {
   dh_ctx* ctx;
   char* base;
   size_t off = 0;
   bool ok = true;
+  std::vector<NsEntry>* list = nullptr;  // optional: the arrays handed out, in order (dh_ns_state_export / _import)
+  bool fills = true;                     // false: pointers only, the arrays are in use (a kept ensemble's own base)
   template <class T>
   void operator()(T*& p, size_t count, bool wanted = true, int fill = -1) {
     p = nullptr;
@@ -2313,8 +2452,9 @@ struct NsCarver {
     const size_t bytes = count * sizeof(T);
     if (base) {
       p = (T*)(base + off);
-      if (fill >= 0 && ok) ok = hip_ok(ctx, hipMemsetAsync(base + off, fill, bytes, ctx->stream), "memset");
+      if (fill >= 0 && ok && fills) ok = hip_ok(ctx, hipMemsetAsync(base + off, fill, bytes, ctx->stream), "memset");
     }
+    if (list && bytes) list->push_back({off, bytes});
     off += (bytes + 255) & ~(size_t)255;
   }
 };
@@ -2383,6 +2523,14 @@ void ns_arrays(NsCarver& c, const NsPlan& p, NsArgs& a, NsAux& x, int n_words, b
   c(x.frr, R);
   c(x.fnc, R);
   c(a.prof, 32, p.want_prof, 0);
+  c(a.sv_st, R, p.keep);
+  c(a.sv_u, R * K * D, p.keep);
+  c(a.sv_v, R * K * D, p.keep);
+  c(a.sv_logl, R * K, p.keep);
+  c(a.sv_slot, R * K, p.keep);
+  c(a.sv_it, R * K, p.keep);
+  c(a.sv_n, R, p.keep, 0);
+  c(a.rest, R, p.keep, 0);
   a.presort = x.presort;
 }
 
@@ -2588,6 +2736,50 @@ void ns_keep_arrays(dh_ctx* ctx, const NsArgs& a, int problem, char* base, const
   }
 }
 
+// What a kept ensemble needs to be taken further (dh_ns_continue) or saved (dh_ns_state_export): the first call's plan,
+// its arguments with the carved pointers, and the two things the host keeps between fills.  Owned by dh_kept::loop.
+struct NsLoop {
+  NsPlan p;
+  NsArgs a;
+  NsAux x;
+  int64_t fill;     // the ENSEMBLE's fill counter: rebuild fills and Philox offsets are keyed on it
+  bool cube_phase;
+};
+
+void ns_keep_loop(dh_ctx* ctx, const NsPlan& p, const NsArgs& a, const NsAux& x, int64_t fill, bool cube_phase) {
+  ctx->kept.loop = std::shared_ptr<void>(new NsLoop{p, a, x, fill, cube_phase}, [](void* q) { delete (NsLoop*)q; });
+}
+NsLoop* ns_kept_loop(dh_ctx* ctx) { return ctx->kept.base ? (NsLoop*)ctx->kept.loop.get() : nullptr; }
+
+// The fills from *fill up to fill_end, or until every run is over: the done-counter is read every eighth fill.
+// h_state: [runs done, any run still in the unit-cube phase], as the caller knows them on entry.
+int ns_fill_loop(dh_ctx* ctx, const NsPlan& p, NsArgs& a, const NsAux& x, int64_t* fill_io, int64_t fill_end,
+                 int* h_state, bool* cube_io) {
+  const int R = a.runs, K = a.K;
+  hipStream_t s = ctx->stream;
+  int64_t fill = *fill_io;
+  bool cube_phase = *cube_io;
+  int rc = DH_OK;
+  while (fill < fill_end && h_state[0] < R) {
+    for (int burst = 0; burst < 8 && fill < fill_end; ++burst, ++fill) {
+      a.rebuild_fill = fill % p.every == 0 ? 1 : 0;
+      hipLaunchKernelGGL(ns_prepare, dim3(1), dim3(kT), 0, s, a);
+      rc = a.forced_exact ? bounds_exact(ctx, p, a, x) : bounds_late(ctx, p, a, x);
+      if (!rc) rc = walk_stage(ctx, p, a, x, fill, cube_phase);
+      if (rc) return rc;
+      hipLaunchKernelGGL(ns_consume_for(K), dim3(R), dim3(kT), p.lds_cons, s, a);
+      a.presorted = 0;
+    }
+    if (!hip_ok(ctx, hipMemcpyAsync(h_state, a.ndone, 8, hipMemcpyDeviceToHost, s), "D2H ndone") ||
+        !hip_ok(ctx, hipStreamSynchronize(s), "sync"))
+      return DH_ERR_HIP;
+    if (!h_state[1]) cube_phase = false;  // (as of the last ns_prepare: every run has its first bound)
+  }
+  *fill_io = fill;
+  *cube_io = cube_phase;
+  return DH_OK;
+}
+
 void ns_prof_print(dh_ctx* ctx, const long long* prof, long long fills) {
   long long h[32];
   (void)hipStreamSynchronize(ctx->stream);
@@ -2775,6 +2967,9 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
                    dead_u_out != nullptr || shot.keep, ns_point_outputs(shot.keep != 0, !!dead_id_out + !!dead_it_out + !!dead_nc_out + !!live_it_out),
                    bootstrap, rebuild_every, &p);
   if (rc) return rc;
+  p.keep = shot.keep != 0;
+  p.n_words = n_words;
+  p.have_bc = !shot.bc.empty();
   if (shot.keep) kept_free(ctx);  // a later keep replaces the earlier one (before this call's allocation)
   NsArgs a = p.a;
   NsAux x;
@@ -2786,10 +2981,13 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
   (void)hipSetDevice(ctx->device);
   if (!hip_ok(ctx, hipMalloc((void**)&base, sizes.off), "hipMalloc(ns state)")) return DH_ERR_NOMEM;
   hipStream_t s = ctx->stream;
+  int64_t kept_fill = 0;
+  bool kept_cube = true;
   auto cleanup = [&](int rc) {
     (void)hipStreamSynchronize(ctx->stream);
     if (shot.keep && rc == DH_OK) {
       ns_keep_arrays(ctx, a, problem, base, records);
+      ns_keep_loop(ctx, p, a, x, kept_fill, kept_cube);
       return rc;
     }
     (void)hipFree(base);
@@ -2813,21 +3011,10 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
   int64_t fill = 0;
   int h_state[2] = {0, 1};  // [runs done, any run still in the unit-cube phase]
   bool cube_phase = true;
-  while (fill < p.fills_cap && h_state[0] < R) {
-    for (int burst = 0; burst < 8 && fill < p.fills_cap; ++burst, ++fill) {
-      a.rebuild_fill = fill % p.every == 0 ? 1 : 0;
-      hipLaunchKernelGGL(ns_prepare, dim3(1), dim3(kT), 0, s, a);
-      rc = a.forced_exact ? bounds_exact(ctx, p, a, x) : bounds_late(ctx, p, a, x);
-      if (!rc) rc = walk_stage(ctx, p, a, x, fill, cube_phase);
-      if (rc) return cleanup(rc);
-      hipLaunchKernelGGL(ns_consume_for(K), dim3(R), dim3(kT), p.lds_cons, s, a);
-      a.presorted = 0;
-    }
-    if (!hip_ok(ctx, hipMemcpyAsync(h_state, a.ndone, 8, hipMemcpyDeviceToHost, s), "D2H ndone") ||
-        !hip_ok(ctx, hipStreamSynchronize(s), "sync"))
-      return cleanup(DH_ERR_HIP);
-    if (!h_state[1]) cube_phase = false;  // (as of the last ns_prepare: every run has its first bound)
-  }
+  rc = ns_fill_loop(ctx, p, a, x, &fill, p.fills_cap, h_state, &cube_phase);
+  if (rc) return cleanup(rc);
+  kept_fill = fill;
+  kept_cube = cube_phase;
   hipLaunchKernelGGL(ns_finish, dim3(R), dim3(kT), p.lds_fin, s, a);
   if (!hip_ok(ctx, hipGetLastError(), "ns launch") ||
       !download(ctx, a, records, dead_logl_out, live_logl_out, dead_u_out, live_u_out, dead_id_out, dead_it_out,
@@ -2836,6 +3023,319 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
   if (n_fills_out) *n_fills_out = fill;
   if (a.prof) ns_prof_print(ctx, a.prof, (long long)fill);
   return cleanup(DH_OK);
+}
+
+}  // extern "C"
+
+// ---- a kept ensemble between two calls: dh_ns_continue, dh_ns_state_size / _export / _import (ns_state.h) ----------
+namespace {
+namespace nst = dh_ns_state;
+
+enum { ENT_FIXED, ENT_DEAD, ENT_SKIP };
+// How the image treats the array at `ptr`: the dead-point arrays by rows (*elem bytes each); not at all the workspaces
+// that a fill or ns_finish writes before it reads them; everything else whole.
+int ns_entry_kind(const NsArgs& a, const NsAux& x, const void* ptr, size_t* elem) {
+  *elem = 0;
+  if (ptr == a.dead_logl) return *elem = 8, ENT_DEAD;
+  if (ptr == a.dead_u) return *elem = 8 * (size_t)a.ndim, ENT_DEAD;
+  if (ptr == a.dead_id || ptr == a.dead_it || ptr == a.dead_nc) return *elem = 4, ENT_DEAD;
+  if (ptr == a.fin_ws || ptr == x.boot_ws || ptr == x.fr_ws || ptr == x.presort || ptr == a.prof || ptr == x.fr_mask ||
+      ptr == x.fr_scratch || ptr == a.records)
+    return ENT_SKIP;
+  return ENT_FIXED;
+}
+
+// the arrays of plan p at capacity scalars.cap, carved from `base` (null: the total size alone); fresh: a new
+// allocation, which takes the arrays' initial fills
+struct NsLayout {
+  NsArgs a;
+  NsAux x;
+  std::vector<NsEntry> list;
+  std::vector<int> kind;
+  std::vector<size_t> elem;
+  size_t bytes = 0, fixed_bytes = 0, row_bytes = 0;
+  bool ok = true;
+};
+void ns_layout(dh_ctx* ctx, const NsPlan& p, const NsArgs& scalars, char* base, bool fresh, NsLayout* out) {
+  out->a = scalars;
+  out->list.clear();
+  NsCarver c{ctx, base};
+  c.list = &out->list;
+  c.fills = fresh;  // (an ensemble in use keeps what its arrays hold)
+  ns_arrays(c, p, out->a, out->x, p.n_words, p.have_bc);
+  out->bytes = c.off;
+  out->ok = c.ok;
+  out->kind.clear();
+  out->elem.clear();
+  out->fixed_bytes = out->row_bytes = 0;
+  if (!base) return;  // (sizes alone: without pointers no array can be told from another)
+  for (const NsEntry& e : out->list) {
+    size_t el;
+    const int k = ns_entry_kind(out->a, out->x, base + e.off, &el);
+    out->kind.push_back(k);
+    out->elem.push_back(el);
+    if (k == ENT_FIXED) out->fixed_bytes += nst::pad8(e.bytes);
+    if (k == ENT_DEAD) out->row_bytes += el;
+  }
+}
+
+// the header and the rows of the kept ensemble as it stands (reads the runs' states back)
+int ns_image_header(dh_ctx* ctx, NsLoop* L, const NsLayout& lay, nst::Header* h, std::vector<int64_t>* rows) {
+  const NsArgs& a = L->a;
+  std::vector<NsRun> stv((size_t)a.runs);
+  if (!down(ctx, stv.data(), a.st, (size_t)a.runs) || !hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync"))
+    return DH_ERR_HIP;
+  rows->resize((size_t)a.runs);
+  for (int r = 0; r < a.runs; ++r) {
+    const long long it = stv[(size_t)r].it;
+    (*rows)[(size_t)r] = it < 0 ? 0 : it > a.cap ? a.cap : it;
+  }
+  memset(h, 0, sizeof *h);
+  h->magic = nst::kMagic;
+  h->version = DH_VERSION;
+  h->sizeof_run = sizeof(NsRun);
+  h->header_bytes = sizeof(nst::Header);
+  h->plan_bytes = sizeof(NsPlan);
+  h->runs = a.runs;
+  h->nlive = a.nlive;
+  h->ndim = a.ndim;
+  h->queue_size = a.K;
+  h->cap = a.cap;
+  h->fill = L->fill;
+  h->cube_phase = L->cube_phase ? 1 : 0;
+  h->n_words = L->p.n_words;
+  h->have_bc = L->p.have_bc ? 1 : 0;
+  h->row_bytes = (int32_t)lay.row_bytes;
+  h->fixed_bytes = lay.fixed_bytes;
+  std::vector<uint32_t> elems;
+  for (size_t i = 0; i < lay.list.size(); ++i)
+    if (lay.kind[i] == ENT_DEAD) elems.push_back((uint32_t)lay.elem[i]);
+  h->total_bytes = nst::image_bytes(*h, rows->data(), (int)elems.size(), elems.data());
+  return DH_OK;
+}
+
+// the plan as the image carries it: the call's scalars, no pointers
+NsPlan ns_plan_image(const NsLoop& L) {
+  NsPlan p = L.p;
+  p.a = L.a;
+  NsAux x;
+  NsCarver none{nullptr, nullptr};
+  ns_arrays(none, p, p.a, x, p.n_words, p.have_bc);  // (a carver without a base nulls every pointer)
+  p.a.prof = nullptr;
+  p.a.presort = nullptr;
+  return p;
+}
+}  // namespace
+
+extern "C" {
+
+int dh_ns_continue(dh_ctx* ctx, double dlogz, int64_t max_fills, double* records, double* dead_logl_out,
+                   double* live_logl_out, double* dead_u_out, double* live_u_out, int64_t* n_fills_out,
+                   int32_t* dead_id_out, int32_t* dead_it_out, int32_t* dead_nc_out, int32_t* live_it_out,
+                   int32_t* rest_out) {
+  DH_CHECK_CTX(ctx);
+  // one-shot, as for dh_ns_ensemble: the context forgets the options however this call ends
+  double opt[DH_NS_OPT_COUNT];
+  for (int i = 0; i < DH_NS_OPT_COUNT; ++i) {
+    opt[i] = ctx->ns_opt[i];
+    ctx->ns_opt[i] = __builtin_nan("");
+  }
+  const bool had_bc = !ctx->ns_bc.empty();
+  ctx->ns_bc.clear();
+  ctx->ns_keep = 0;  // (the ensemble stays kept; the switch is not left armed for a later dh_ns_ensemble)
+  NsLoop* L = ns_kept_loop(ctx);
+  if (!L) return fail(ctx, DH_ERR_ARG, "ns_continue: the context holds no kept ensemble (dh_ns_keep + dh_ns_ensemble)");
+  if (!records) return fail(ctx, DH_ERR_ARG, "ns_continue: records is required");
+  if (had_bc || !std::isnan(opt[DH_NS_OPT_UPDATE_INTERVAL]) || !std::isnan(opt[DH_NS_OPT_FIRST_MIN_NCALL]) ||
+      !std::isnan(opt[DH_NS_OPT_FIRST_MIN_EFF]) || !std::isnan(opt[DH_NS_OPT_FORCED_EXACT]))
+    return fail(ctx, DH_ERR_ARG, "ns_continue: the update interval, first_update, forced_exact and the boundary flags "
+                                 "are fixed by the ensemble's first call");
+  const NsPlan& p = L->p;
+  NsArgs a = L->a;
+  const NsAux& x = L->x;
+  const int R = a.runs, K = a.K;
+  a.dlogz = dlogz;
+  a.maxiter = a.maxcall = -1;
+  a.logl_max = INFINITY;
+  a.add_live = 1;
+  if (!std::isnan(opt[DH_NS_OPT_MAXITER])) a.maxiter = (long long)llround(opt[DH_NS_OPT_MAXITER]);
+  if (!std::isnan(opt[DH_NS_OPT_MAXCALL])) a.maxcall = (long long)llround(opt[DH_NS_OPT_MAXCALL]);
+  if (!std::isnan(opt[DH_NS_OPT_LOGL_MAX])) a.logl_max = opt[DH_NS_OPT_LOGL_MAX];
+  if (!std::isnan(opt[DH_NS_OPT_ADD_LIVE])) a.add_live = opt[DH_NS_OPT_ADD_LIVE] != 0.0 ? 1 : 0;
+  if (a.maxcall >= 0 && a.maxcall < a.nlive)
+    return fail(ctx, DH_ERR_ARG, "ns_continue: maxcall %lld below the %d calls of the initial live points", a.maxcall, a.nlive);
+  a.presorted = 0;
+  a.fx_pass = 0;
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = ctx->stream;
+  if (!ns_set_lds(ctx, K, p.lds_cons > p.lds_fin ? p.lds_cons : p.lds_fin, true)) return DH_ERR_HIP;
+  // which runs go on (ns_resume), then the fills that a stop rule cut short, once more and whole: ahead of the
+  // first ns_prepare, which must see the call count the uninterrupted run had at that fill's end
+  if (!hip_ok(ctx, hipMemsetAsync(a.ndone, 0, 64, s), "memset")) return DH_ERR_HIP;
+  hipLaunchKernelGGL(ns_resume, dim3(R), dim3(kT), 0, s, a);
+  a.replay = 1;
+  hipLaunchKernelGGL(ns_consume_for(K), dim3(R), dim3(kT), p.lds_cons, s, a);
+  a.replay = 0;
+  int h_state[2] = {0, 1};
+  std::vector<int> rest((size_t)R);
+  if (!hip_ok(ctx, hipGetLastError(), "ns_resume launch") || !down(ctx, h_state, a.ndone, 2) ||
+      !down(ctx, rest.data(), a.rest, (size_t)R) || !hip_ok(ctx, hipStreamSynchronize(s), "sync"))
+    return DH_ERR_HIP;
+  const int64_t fill0 = L->fill;
+  int64_t fill = fill0;
+  bool cube_phase = h_state[1] != 0;
+  const int64_t budget = max_fills > 0 ? max_fills : 1000000;
+  int rc = ns_fill_loop(ctx, p, a, x, &fill, fill0 + budget, h_state, &cube_phase);
+  // whatever happens below, the fills are spent: the ensemble's counter moves with them
+  L->fill = fill;
+  L->cube_phase = cube_phase;
+  L->a = a;
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  hipLaunchKernelGGL(ns_finish, dim3(R), dim3(kT), p.lds_fin, s, a);
+  if (!hip_ok(ctx, hipGetLastError(), "ns launch") ||
+      !download(ctx, a, records, dead_logl_out, live_logl_out, dead_u_out, live_u_out, dead_id_out, dead_it_out,
+                dead_nc_out, live_it_out) ||
+      !hip_ok(ctx, hipStreamSynchronize(s), "sync"))
+    return DH_ERR_HIP;
+  for (int r = 0; r < R; ++r) {
+    long long nit = (long long)records[(size_t)r * 8 + 2];
+    ctx->kept.niter[(size_t)r] = nit < 0 ? 0 : nit > a.cap ? a.cap : nit;
+    if (rest_out) rest_out[r] = rest[(size_t)r];
+  }
+  if (n_fills_out) *n_fills_out = fill - fill0;
+  return DH_OK;
+}
+
+int dh_ns_state_size(dh_ctx* ctx, uint64_t* bytes) {
+  DH_CHECK_CTX(ctx);
+  NsLoop* L = ns_kept_loop(ctx);
+  if (!L || !bytes) return fail(ctx, DH_ERR_ARG, "ns_state_size: no kept ensemble");
+  NsLayout lay;
+  ns_layout(ctx, L->p, L->a, ctx->kept.base, false, &lay);  // (the pointers it hands out are the ensemble's own: nothing is written)
+  nst::Header h;
+  std::vector<int64_t> rows;
+  const int rc = ns_image_header(ctx, L, lay, &h, &rows);
+  if (rc) return rc;
+  *bytes = h.total_bytes;
+  return DH_OK;
+}
+
+int dh_ns_state_export(dh_ctx* ctx, void* buf, uint64_t bytes) {
+  DH_CHECK_CTX(ctx);
+  NsLoop* L = ns_kept_loop(ctx);
+  if (!L || !buf) return fail(ctx, DH_ERR_ARG, "ns_state_export: no kept ensemble");
+  NsLayout lay;
+  ns_layout(ctx, L->p, L->a, ctx->kept.base, false, &lay);
+  nst::Header h;
+  std::vector<int64_t> rows;
+  int rc = ns_image_header(ctx, L, lay, &h, &rows);
+  if (rc) return rc;
+  if (bytes < h.total_bytes)
+    return fail(ctx, DH_ERR_ARG, "ns_state_export: %llu bytes given, the image takes %llu", (unsigned long long)bytes,
+                (unsigned long long)h.total_bytes);
+  char* out = (char*)buf;
+  memset(out, 0, (size_t)h.total_bytes);
+  size_t at = 0;
+  memcpy(out, &h, sizeof h);
+  at += sizeof h;
+  const NsPlan pi = ns_plan_image(*L);
+  memcpy(out + at, &pi, sizeof pi);
+  at += (size_t)nst::pad8(sizeof pi);
+  memcpy(out + at, rows.data(), rows.size() * 8);
+  at += rows.size() * 8;
+  const size_t cap = (size_t)L->a.cap;
+  hipStream_t s = ctx->stream;
+  for (size_t i = 0; i < lay.list.size(); ++i) {
+    const char* dev = ctx->kept.base + lay.list[i].off;
+    if (lay.kind[i] == ENT_FIXED) {
+      if (!hip_ok(ctx, hipMemcpyAsync(out + at, dev, lay.list[i].bytes, hipMemcpyDeviceToHost, s), "D2H state")) return DH_ERR_HIP;
+      at += (size_t)nst::pad8(lay.list[i].bytes);
+    } else if (lay.kind[i] == ENT_DEAD) {
+      const size_t el = lay.elem[i];
+      for (size_t r = 0; r < rows.size(); ++r) {
+        const size_t n = (size_t)rows[r] * el;
+        if (n && !hip_ok(ctx, hipMemcpyAsync(out + at, dev + r * cap * el, n, hipMemcpyDeviceToHost, s), "D2H rows")) return DH_ERR_HIP;
+        at += (size_t)nst::pad8(n);
+      }
+    }
+  }
+  if (!hip_ok(ctx, hipStreamSynchronize(s), "sync")) return DH_ERR_HIP;
+  if (at != h.total_bytes) return fail(ctx, DH_ERR_ARG, "ns_state_export: wrote %zu of %llu bytes", at, (unsigned long long)h.total_bytes);
+  return DH_OK;
+}
+
+int dh_ns_state_import(dh_ctx* ctx, int problem, const void* buf, uint64_t bytes, int64_t max_iter) {
+  DH_CHECK_CTX(ctx);
+  ProblemDev pd;
+  if (!get_problem(ctx, problem, &pd)) return DH_ERR_ARG;
+  if (max_iter < 0) return fail(ctx, DH_ERR_ARG, "ns_state_import: max_iter %lld", (long long)max_iter);
+  nst::Header h;
+  const int64_t* rows_p = nullptr;
+  int64_t cap = 0;
+  const int why = nst::validate(buf, bytes, DH_VERSION, sizeof(NsRun), sizeof(NsPlan), pd.ndim, max_iter, &h, &rows_p, &cap);
+  if (why != nst::IMG_OK) return fail(ctx, DH_ERR_ARG, "ns_state_import: %s", nst::reject_text(why));
+  const char* in = (const char*)buf;
+  NsPlan p;
+  memcpy((void*)&p, in + h.header_bytes, sizeof p);
+  std::vector<int64_t> rows((size_t)h.runs);
+  memcpy(rows.data(), rows_p, rows.size() * 8);
+  // the plan must be the header's, and the image exactly as long as its arrays say: all of it is known before the
+  // device or the context's kept ensemble is touched
+  if (p.a.runs != h.runs || p.a.nlive != h.nlive || p.a.ndim != h.ndim || p.a.K != h.queue_size || p.a.cap != h.cap ||
+      p.n_words != h.n_words || (p.have_bc ? 1 : 0) != h.have_bc || !p.keep || p.a.runs < 1 || p.a.nlive < 4 ||
+      p.a.K > kEPTMax * kT || p.a.max_ells < 1 || p.lds_cons > kNsLdsMax || p.lds_fin > kNsLdsMax || p.every < 1)
+    return fail(ctx, DH_ERR_ARG, "ns_state_import: the plan does not belong to the header");
+  p.problem = problem;
+  p.a.cap = cap;
+  NsLayout sizes;
+  ns_layout(ctx, p, p.a, nullptr, false, &sizes);
+  // (with a null base no kind can be told from the pointers: the sizes alone here, the kinds after the carving)
+  char* base = nullptr;
+  (void)hipSetDevice(ctx->device);
+  if (!hip_ok(ctx, hipMalloc((void**)&base, sizes.bytes), "hipMalloc(ns state)")) return DH_ERR_NOMEM;
+  NsLayout lay;
+  ns_layout(ctx, p, p.a, base, true, &lay);
+  hipStream_t s = ctx->stream;
+  auto give_up = [&](int rc) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(base);
+    return rc;
+  };
+  if (!lay.ok) return give_up(DH_ERR_HIP);
+  std::vector<uint32_t> elems;
+  for (size_t i = 0; i < lay.list.size(); ++i)
+    if (lay.kind[i] == ENT_DEAD) elems.push_back((uint32_t)lay.elem[i]);
+  if (lay.fixed_bytes != h.fixed_bytes || (size_t)h.row_bytes != lay.row_bytes ||
+      nst::image_bytes(h, rows.data(), (int)elems.size(), elems.data()) != h.total_bytes)
+    return give_up(fail(ctx, DH_ERR_ARG, "ns_state_import: the image's arrays are not those of its plan"));
+  size_t at = (size_t)h.header_bytes + (size_t)nst::pad8(h.plan_bytes) + rows.size() * 8;
+  for (size_t i = 0; i < lay.list.size(); ++i) {
+    char* dev = base + lay.list[i].off;
+    if (lay.kind[i] == ENT_FIXED) {
+      if (!hip_ok(ctx, hipMemcpyAsync(dev, in + at, lay.list[i].bytes, hipMemcpyHostToDevice, s), "H2D state")) return give_up(DH_ERR_HIP);
+      at += (size_t)nst::pad8(lay.list[i].bytes);
+    } else if (lay.kind[i] == ENT_DEAD) {
+      const size_t el = lay.elem[i];
+      for (size_t r = 0; r < rows.size(); ++r) {
+        const size_t n = (size_t)rows[r] * el;
+        if (n && !hip_ok(ctx, hipMemcpyAsync(dev + r * (size_t)cap * el, in + at, n, hipMemcpyHostToDevice, s), "H2D rows"))
+          return give_up(DH_ERR_HIP);
+        at += (size_t)nst::pad8(n);
+      }
+    }
+  }
+  if (!hip_ok(ctx, hipStreamSynchronize(s), "sync")) return give_up(DH_ERR_HIP);
+  // installed: the context's earlier kept ensemble goes, as with a later keep
+  kept_free(ctx);
+  std::vector<double> rec((size_t)h.runs * 8, 0.0);
+  for (int r = 0; r < h.runs; ++r) rec[(size_t)r * 8 + 2] = (double)rows[(size_t)r];
+  ns_keep_arrays(ctx, lay.a, problem, base, rec.data());
+  p.a = lay.a;
+  ns_keep_loop(ctx, p, lay.a, lay.x, h.fill, h.cube_phase != 0);
+  return DH_OK;
 }
 
 }  // extern "C"

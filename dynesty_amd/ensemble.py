@@ -425,7 +425,7 @@ def merge_logz(dead_logl, niter, live_logl):
 
 
 def run_ensemble_merged(prob, runs, nlive=2000, queue_size=512, entropy=(21,),
-                        max_iter=None, merge='host', **kw):
+                        max_iter=None, merge='host', release=True, **kw):
     """`runs` static runs on the device (dh_ns_ensemble) merged into one run
     with posterior samples: the single-process form of BASELINE C5's
     "gather of logZ / posterior samples".
@@ -438,6 +438,9 @@ def run_ensemble_merged(prob, runs, nlive=2000, queue_size=512, entropy=(21,),
     to_merged_run() -- with only what is asked for crossing to the host.
     The kept ensemble is released once merged; the merged run stays on the
     device until its release() or the context's next merge.
+    release=False (merge='device' only) keeps the ensemble instead, so that it
+    can be taken further (Context.ns_continue) and merged again
+    (Context.merge_kept); runs that are not over (status 1) are then no error.
     Either way the per-run records are under ["runs"]."""
     if merge not in ('host', 'device'):
         raise ValueError(f"run_ensemble_merged: merge={merge!r} (one of 'host', 'device')")
@@ -445,15 +448,20 @@ def run_ensemble_merged(prob, runs, nlive=2000, queue_size=512, entropy=(21,),
     be = get_backend()
     if max_iter is None:
         max_iter = 80 * nlive  # > nlive * (H + ln(1/dlogz)) for the benchmark problems
+    if not release and merge != 'device':
+        raise ValueError("run_ensemble_merged: release=False needs merge='device' (there is no kept ensemble otherwise)")
     if merge == 'device':
         r = be.ns_ensemble(prob, runs, nlive, queue_size, entropy=entropy,
                            max_iter=max_iter, want_samples=False, keep=True, **kw)
-        if (r["status"] != 0).any():
+        if ((r["status"] != 0) if release else (r["status"] < 0)).any():
+            if release:
+                be.release_kept()
             raise RuntimeError(f"ns_ensemble: runs failed, status {r['status']}")
         try:
             m = be.merge_kept(prob)
         finally:
-            be.release_kept()  # the merged run stands alone: the ensemble's own allocation goes back at once
+            if release:
+                be.release_kept()  # the merged run stands alone: the ensemble's own allocation goes back at once
         m["runs"] = r
         return m
     r = be.ns_ensemble(prob, runs, nlive, queue_size, entropy=entropy,
@@ -578,3 +586,41 @@ def run_ensemble_merged_sharded(prob, total_runs, base_seed=21, world=1, rank=0,
         return be.problem_eval(prob, u)[0]
     return gather_and_merge(rows, nlive, world, rank, dist=dist, device=device,
                             prior_transform=ptform, ncall=[ncall])
+
+
+def run_ensemble_checkpointed(prob, runs, nlive=2000, queue_size=512, checkpoint_file=None, checkpoint_fills=256,
+                              resume=False, max_legs=None, dlogz=0.01, maxiter=None, maxcall=None, logl_max=None,
+                              add_live=True, want_dead_logl=False, want_samples=False, **kw):
+    """Context.ns_ensemble in legs of `checkpoint_fills` fills with the ensemble saved to `checkpoint_file` after every
+    leg (Context.ns_save: written beside the file and renamed, so an interrupted save leaves the previous one) -- the
+    resident loop's form of run_nested(checkpoint_file=..., resume=True).  A leg ends by max_fills (its runs have
+    status 1 in between), the last one by the stop rules; with PCG64 streams, and with Philox streams too (the legs
+    end at fill boundaries), the result is bit for bit that of ONE ns_ensemble call with the same arguments.
+    resume=True starts from the file if it exists (the problem must be the one the file was written for; the other
+    arguments of the first leg then come from the file).  max_legs stops after that many legs (None: until every run
+    is over) -- what an interruption leaves behind, for tests and time-sliced jobs.  Returns what ns_ensemble returns;
+    the ensemble is released at the end unless max_legs cut the run short."""
+    import os
+    from .backend import get_backend
+    if checkpoint_file is None:
+        raise ValueError("run_ensemble_checkpointed: checkpoint_file is required")
+    if checkpoint_fills < 1:
+        raise ValueError("run_ensemble_checkpointed: checkpoint_fills must be at least 1")
+    be = get_backend()
+    crit = dict(dlogz=dlogz, maxiter=maxiter, maxcall=maxcall, logl_max=logl_max, add_live=add_live)
+    want = dict(want_dead_logl=want_dead_logl, want_samples=want_samples)
+    legs = 0
+    if resume and os.path.exists(checkpoint_file):
+        be.ns_load(prob, checkpoint_file)
+        r = None
+    else:
+        r = be.ns_ensemble(prob, runs, nlive, queue_size, max_fills=checkpoint_fills, keep=True, **crit, **want, **kw)
+        be.ns_save(checkpoint_file)
+        legs = 1
+    while (r is None or (r["status"] == 1).any()) and (max_legs is None or legs < max_legs):
+        r = be.ns_continue(max_fills=checkpoint_fills, **crit, **want)
+        be.ns_save(checkpoint_file)
+        legs += 1
+    if r is not None and not (r["status"] == 1).any():
+        be.release_kept()
+    return r

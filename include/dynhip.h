@@ -638,6 +638,66 @@ int dh_unif_friends_batch(dh_ctx* ctx, int problem, int k, int ndim, int kind, c
 int dh_ns_keep(dh_ctx* ctx, int on);
 int dh_ns_release(dh_ctx* ctx);
 
+/* ---- a kept ensemble taken further, saved and restored (csrc/ns.hip, csrc/ns_state.h) ----
+ * dh_ns_continue re-enters the loop of the ensemble that dh_ns_keep + dh_ns_ensemble (or dh_ns_state_import) left on
+ * the device, as calling run_nested again does in the reference (sampler.py:1038-1066).  The allocation, the plan, the
+ * streams and the ENSEMBLE's fill counter are the first call's.  Records and outputs are those of dh_ns_ensemble, over
+ * the whole run; the host buffers are runs x max_iter of the FIRST call: the dead-point capacity is chosen once, for the
+ * whole run (dh_ns_state_import can give a saved ensemble more).  The ensemble stays kept, and dh_merge_kept merges the
+ * continued runs.  max_fills (0: 10^6) bounds the fills of THIS call; n_fills_out counts them.
+ * Stop rules.  dlogz (the argument) and the one-shot options DH_NS_OPT_MAXITER / MAXCALL / LOGL_MAX / ADD_LIVE are taken
+ *   anew by each call (not set: none / add_live 1).  maxiter and maxcall are TOTALS of the run -- iterations and calls
+ *   since the run began, exactly as in the first call.  The reference's repeated run_nested counts them per call: a
+ *   deliberate difference; a caller who wants a per-call budget adds the records' niter / ncall.  Everything else is
+ *   fixed by the first call: sampler, bound, walks, enlarge, bootstrap, rebuild_every, the update interval, first_update,
+ *   forced_exact, the boundary flags and the resolved values of the environment switches.  Setting
+ *   DH_NS_OPT_UPDATE_INTERVAL / FIRST_MIN_NCALL / FIRST_MIN_EFF / FORCED_EXACT or dh_ns_set_boundary before
+ *   dh_ns_continue is DH_ERR_ARG, as is a context without a kept ensemble.  As for every call, the context forgets the
+ *   options however the call ends; an argument error leaves the kept ensemble as it was.
+ * Which runs go on.  Before the first fill the reference's top-of-loop tests (sampler.py:1071-1100: delta ln Z from
+ *   lmax, ln X, ln Z below dlogz; the last dead point above logl_max; it > maxiter; ncall > maxcall; the plateau stop)
+ *   are evaluated on every run's state.  A run for which one holds is done (status 0) with no new death; the others go
+ *   on in the mode they had (unit-cube phase or bound); a failed run (status -1) stays failed, its record as it was; a
+ *   run that max_fills stopped (status 1) simply goes on.  Continuing with unchanged criteria is therefore a no-op that
+ *   returns the same records and zero fills.
+ * The unspent queue.  A stop rule that ends a run inside a fill leaves queue entries behind the stopping one; the
+ *   reference keeps them and pops them first when the run goes on.  So does the continuation: the fill's proposals stay
+ *   on the device, the state the fill found is put back, and the fill is consumed again -- whole, under the new criteria,
+ *   ahead of the call's first regular fill, without a second tuning step and without counting as a fill.  rest_out
+ *   (optional, runs) reports how many entries behind its stop each run took over this way (0: none, or not stopped
+ *   inside a fill).
+ * What is exact.  PCG64 streams: a run's result depends on its own seed and its own sequence of events only, so any
+ *   chain of calls that ends under criteria C gives, run for run and bit for bit, what ONE dh_ns_ensemble call under C
+ *   gives (records, dead ln L / u / id / it / nc, final live ln L / u / it) -- whether the earlier calls were ended by
+ *   max_fills, maxiter, maxcall, logl_max or a looser dlogz (criteria that stop a run later than C would are the
+ *   caller's to avoid: a dead point does not come back), with or without an export / import in between, with
+ *   rebuild_sync = 0.  Philox streams: offsets are keyed on the ENSEMBLE's fill index.  Calls cut by max_fills are
+ *   bit-exact (all runs stop at the same fill boundary); after a criterion stop a run resumes at a later ensemble fill
+ *   than it would have reached uninterrupted, and its result is then a different, equally valid draw: deterministic, not
+ *   equal. */
+int dh_ns_continue(dh_ctx* ctx, double dlogz, int64_t max_fills, double* records, double* dead_logl_out,
+                   double* live_logl_out, double* dead_u_out, double* live_u_out, int64_t* n_fills_out,
+                   int32_t* dead_id_out, int32_t* dead_it_out, int32_t* dead_nc_out, int32_t* live_it_out,
+                   int32_t* rest_out /* optional, runs: unspent queue entries each run took over */);
+
+/* The kept ensemble as one host buffer and back.  The image holds a header (magic, DH_VERSION, sizeof of the per-run
+ * state, the shapes, the fill counter, whether the unit-cube phase is still on), every argument and resolved plan value
+ * of the first call, and the state arrays; the five dead-point arrays (ln L, u, id, it, nc) by each run's first niter
+ * rows only, so the size depends on what the runs produced, not on max_iter.  Workspaces that every fill rewrites are
+ * left out.  An image is read by the library version that wrote it.
+ * dh_ns_state_size: the bytes dh_ns_state_export will write now.  dh_ns_state_export: DH_ERR_ARG if `bytes` is less.
+ * dh_ns_state_import rebuilds the plan from the image (not from the environment), allocates, copies, and installs the
+ * result as the context's kept ensemble (an earlier one is freed), ready for dh_ns_continue / dh_merge_kept.
+ * max_iter = 0: the saved capacity; larger values give the runs more room (rows are `capacity` apart: only strides
+ * change).  DH_ERR_ARG, with the context left as it was: bad magic or version, another sizeof of the per-run state, a
+ * truncated buffer, a row count above the capacity, max_iter below a run's niter, a problem whose ndim differs.  That
+ * the problem is otherwise the one the ensemble was run on is the caller's responsibility, as is the integrity of the
+ * image's body. */
+int dh_ns_state_size(dh_ctx* ctx, uint64_t* bytes);
+int dh_ns_state_export(dh_ctx* ctx, void* buf, uint64_t bytes);
+int dh_ns_state_import(dh_ctx* ctx, int problem, const void* buf, uint64_t bytes,
+                       int64_t max_iter /* 0: as saved; else >= every run's niter */);
+
 /* Per-point fields of the merged run (dh_merged_fetch).  LOGL .. WEIGHT: one double per point; SAMPLES_U / SAMPLES:
  * ndim doubles per point; RUN .. NCALL: one int32 per point (ID / IT / NCALL only where the merge was given them). */
 enum {
