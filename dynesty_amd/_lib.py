@@ -126,6 +126,9 @@ SIGNATURES = {
     "dh_ns_keep": (_i, [_vp, _i]),
     "dh_ns_release": (_i, [_vp]),
     "dh_ns_continue": (_i, [_vp, _dbl, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dh_ns_batch": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _dbl, _dbl, C.c_int64, C.c_int64, _vp, _i, _u32,
+                         _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
+                         _vp, _vp, _vp, _vp, _vp]),
     "dh_ns_state_size": (_i, [_vp, _vp]),
     "dh_ns_state_export": (_i, [_vp, _vp, _u64]),
     "dh_ns_state_import": (_i, [_vp, _i, _vp, _u64, C.c_int64]),
@@ -1244,12 +1247,37 @@ class Context:
             if nd > 32:
                 raise ValueError(f"ns_ensemble: bound={bound!r} at ndim={nd} is not supported by the "
                                  "device-resident loop (balls / cubes need ndim <= 32)")
+        kind, walks, enlarge, bootstrap = self._ns_sampler("ns_ensemble", nd, sample, rng, walks, slices, enlarge, bootstrap)
+        words = entropy_words(entropy)
+        want_dead_logl = want_dead_logl or want_samples
+        buf = self._ns_buffers(runs, nlive, nd, max_iter, want_dead_logl, want_samples)
+        nf = C.c_int64(0)
+        self._ns_arm(nd, nlive, update_interval, first_update, maxiter, maxcall, logl_max, add_live, forced_exact,
+                     periodic, reflective)
+        if keep:
+            self._check(self.lib.dh_ns_keep(self.handle, 1))
+        self._check(self.lib.dh_ns_ensemble(
+            self.handle, self.problem(prob), int(runs), int(nlive), nd,
+            int(queue_size), kind, int(walks),
+            BOUND_CODES[bound],
+            1 if rebuild_sync else 0, float(dlogz), float(enlarge), int(max_fills), int(max_iter),
+            _ptr(words), words.size, int(first_run), _ptr(buf["rec"]), _ptr(buf["dead"]),
+            _ptr(buf["livel"]), _ptr(buf["dead_u"]), _ptr(buf["live_u"]), C.byref(nf), _ptr(buf["pid"]), _ptr(buf["pit"]),
+            _ptr(buf["pnc"]), _ptr(buf["lit"]), int(bootstrap), int(rebuild_every)))
+        if keep:
+            self._kept_shape = (int(runs), int(nlive), nd, int(max_iter))
+        return self._ns_result(buf, nf, want_dead_logl, want_samples)
+
+    # ---- what dh_ns_ensemble and dh_ns_batch take alike: one place for the argument handling of both ----
+    @staticmethod
+    def _ns_sampler(what, nd, sample, rng, walks, slices, enlarge, bootstrap):
+        """(sampler code, walks or slices, enlarge, bootstrap) of sample / rng with the reference's defaults."""
         if sample not in ('rwalk', 'rslice', 'slice', 'unif'):
-            raise ValueError(f"ns_ensemble: sample={sample!r} is not supported by the "
+            raise ValueError(f"{what}: sample={sample!r} is not supported by the "
                              "device-resident loop ('rwalk', 'rslice', 'slice' or 'unif')")
         kind = dict(rwalk=0, rslice=1, slice=2, unif=6)[sample]
         if rng not in ('pcg64', 'philox'):
-            raise ValueError("ns_ensemble: rng must be 'pcg64' or 'philox'")
+            raise ValueError(f"{what}: rng must be 'pcg64' or 'philox'")
         enlarge, bootstrap = enlarge_bootstrap_defaults(sample, enlarge, bootstrap)
         if kind == 6:
             walks = 1  # unused
@@ -1259,20 +1287,13 @@ class Context:
         else:
             walks = slices if slices is not None else \
                 (3 + nd if kind == 1 else 3)
-        words = entropy_words(entropy)
-        rec = np.empty((runs, 8))
-        want_dead_logl = want_dead_logl or want_samples
-        dead = np.empty((runs, max_iter)) if want_dead_logl else None
-        livel = np.empty((runs, nlive)) if want_dead_logl else None
-        # runs x max_iter x ndim: only the niter rows a run produced are touched
-        dead_u = np.empty((runs, max_iter, nd)) if want_samples else None
-        live_u = np.empty((runs, nlive, nd)) if want_samples else None
-        # the reference's per-point id / it / nc (sampler.py:1165-1182) travel with the samples
-        pid = np.empty((runs, max_iter), dtype=np.int32) if want_samples else None
-        pit = np.empty((runs, max_iter), dtype=np.int32) if want_samples else None
-        pnc = np.empty((runs, max_iter), dtype=np.int32) if want_samples else None
-        lit = np.empty((runs, nlive), dtype=np.int32) if want_samples else None
-        nf = C.c_int64(0)
+        if rng == 'philox':
+            kind += 1 if kind == 6 else 3
+        return kind, walks, enlarge, bootstrap
+
+    def _ns_arm(self, nd, nlive, update_interval, first_update, maxiter, maxcall, logl_max, add_live, forced_exact,
+                periodic, reflective):
+        """The one-shot options and boundary flags of the next dh_ns_ensemble / dh_ns_batch call."""
         nan = float('nan')
         if update_interval is not None:
             # dynesty.py:213-234: a float is a multiple of nlive, an int a number of calls
@@ -1299,31 +1320,87 @@ class Context:
             if reflective is not None:
                 bc[np.asarray(reflective, dtype=int)] = BC_REFLECT
         self._check(self.lib.dh_ns_set_boundary(self.handle, nd if bc is not None else 0, _ptr(bc)))
-        if keep:
-            self._check(self.lib.dh_ns_keep(self.handle, 1))
-        self._check(self.lib.dh_ns_ensemble(
-            self.handle, self.problem(prob), int(runs), int(nlive), nd,
-            int(queue_size), kind + ((1 if kind == 6 else 3) if rng == 'philox' else 0), int(walks),
-            BOUND_CODES[bound],
-            1 if rebuild_sync else 0, float(dlogz), float(enlarge), int(max_fills), int(max_iter),
-            _ptr(words), words.size, int(first_run), _ptr(rec), _ptr(dead),
-            _ptr(livel), _ptr(dead_u), _ptr(live_u), C.byref(nf), _ptr(pid), _ptr(pit), _ptr(pnc),
-            _ptr(lit), int(bootstrap), int(rebuild_every)))
+
+    @staticmethod
+    def _ns_buffers(runs, nlive, nd, max_iter, want_dead_logl, want_samples):
+        """The host arrays a call writes: records always, the rest where asked for (None otherwise)."""
+        def maybe(want, shape, dtype=np.float64):
+            return np.empty(shape, dtype=dtype) if want else None
+        return dict(rec=np.empty((runs, 8)),
+                    dead=maybe(want_dead_logl, (runs, max_iter)), livel=maybe(want_dead_logl, (runs, nlive)),
+                    # runs x max_iter x ndim: only the niter rows a run produced are touched
+                    dead_u=maybe(want_samples, (runs, max_iter, nd)), live_u=maybe(want_samples, (runs, nlive, nd)),
+                    # the reference's per-point id / it / nc (sampler.py:1165-1182) travel with the samples
+                    pid=maybe(want_samples, (runs, max_iter), np.int32), pit=maybe(want_samples, (runs, max_iter), np.int32),
+                    pnc=maybe(want_samples, (runs, max_iter), np.int32), lit=maybe(want_samples, (runs, nlive), np.int32))
+
+    @staticmethod
+    def _ns_result(buf, nf, want_dead_logl, want_samples):
+        rec = buf["rec"]
         out = dict(logz=rec[:, 0], logzerr=rec[:, 1],
                    niter=rec[:, 2].astype(np.int64),
                    ncall=rec[:, 3].astype(np.int64), h=rec[:, 4],
                    nbound=rec[:, 5].astype(np.int64),
                    status=rec[:, 6].astype(np.int64), eff=rec[:, 7],
                    nfills=nf.value)
-        if keep:
-            self._kept_shape = (int(runs), int(nlive), nd, int(max_iter))
         if want_dead_logl:
-            out["dead_logl"] = dead
-            out["live_logl"] = livel
+            out["dead_logl"] = buf["dead"]
+            out["live_logl"] = buf["livel"]
         if want_samples:
-            out["dead_u"] = dead_u
-            out["live_u"] = live_u
-            out["dead_id"], out["dead_it"], out["dead_nc"], out["live_it"] = pid, pit, pnc, lit
+            out["dead_u"] = buf["dead_u"]
+            out["live_u"] = buf["live_u"]
+            out["dead_id"], out["dead_it"], out["dead_nc"], out["live_it"] = buf["pid"], buf["pit"], buf["pnc"], buf["lit"]
+        return out
+
+    def ns_batch(self, prob, seed_u, seed_logl, logl_min, start, queue_size, logl_max=None, walks=None,
+                 bound='multi', dlogz=0.01, enlarge=None, entropy=(21,), first_run=0, max_fills=0, max_iter=400000,
+                 sample='rwalk', slices=None, bootstrap=None, rebuild_every=0, update_interval=None, maxiter=None,
+                 maxcall=None, add_live=True, forced_exact=True, periodic=None, reflective=None, want_samples=True,
+                 rng='pcg64', keep=False):
+        """One dynamic batch on the device (dh_ns_batch): `runs` strands of nlive_new live points inside the ln L range
+        (logl_min, logl_max] of a finished run.  seed_u (runs, nlive_new, ndim) / seed_logl (runs, nlive_new): every
+        strand's seeds, points of the finished run above logl_min (dynamic.batch_seed chooses them); start (runs, 6) or
+        (6,): logvol, logz, h, logzvar and ln L of the finished run's row at logl_min, and the scale the strand starts
+        with.  Everything else as ns_ensemble takes it, with sample in 'rwalk' | 'rslice' | 'slice' | 'unif' on PCG64
+        streams and bound in 'multi' | 'single'; a request the device refuses raises DynHipError (DH_ERR_ARG) and leaves
+        the context usable.  A batch from the prior (logl_min = -inf) is ns_ensemble(nlive=nlive_new, logl_max=...).
+
+        Returns ns_ensemble's dict (niter: the strand's own deaths; logz / logzerr / h: running values continued from
+        the start row, which steer the dlogz stop and are not results) plus start_u, start_logl, start_nc (the live set
+        the sampling phase began with), seed_ncall and seed_rng (the strand's generator at the hand-over)."""
+        nd = prob.ndim
+        seed_u = np.ascontiguousarray(seed_u, dtype=np.float64)
+        seed_logl = np.ascontiguousarray(seed_logl, dtype=np.float64)
+        if seed_u.ndim != 3 or seed_u.shape[2] != nd or seed_logl.shape != seed_u.shape[:2]:
+            raise ValueError(f"ns_batch: seed_u {seed_u.shape} / seed_logl {seed_logl.shape} are not "
+                             f"(runs, nlive_new, {nd}) / (runs, nlive_new)")
+        runs, nlive = seed_logl.shape
+        start = np.ascontiguousarray(np.broadcast_to(np.asarray(start, dtype=np.float64), (runs, 6)))
+        if bound not in BOUND_CODES:
+            raise ValueError(f"ns_batch: bound={bound!r}")
+        # (rng='philox', the friends bounds and keep=True are passed on: the device refuses them and says why)
+        kind, walks, enlarge, bootstrap = self._ns_sampler("ns_batch", nd, sample, rng, walks, slices, enlarge, bootstrap)
+        words = entropy_words(entropy)
+        buf = self._ns_buffers(runs, nlive, nd, max_iter, True, want_samples)
+        start_u = np.empty((runs, nlive, nd))
+        start_logl = np.empty((runs, nlive))
+        start_nc = np.empty((runs, nlive), dtype=np.int32)
+        seed_ncall = np.zeros(runs, dtype=np.int64)
+        seed_rng = np.zeros((runs, 4), dtype=np.uint64)
+        nf = C.c_int64(0)
+        self._ns_arm(nd, nlive, update_interval, None, maxiter, maxcall, logl_max, add_live, forced_exact, periodic,
+                     reflective)
+        if keep:
+            self._check(self.lib.dh_ns_keep(self.handle, 1))
+        self._check(self.lib.dh_ns_batch(
+            self.handle, self.problem(prob), int(runs), int(nlive), nd, int(queue_size), kind, int(walks),
+            BOUND_CODES[bound], float(dlogz), float(enlarge), int(max_fills), int(max_iter), _ptr(words), words.size,
+            int(first_run), _ptr(seed_u), _ptr(seed_logl), float(logl_min), _ptr(start), _ptr(buf["rec"]),
+            _ptr(buf["dead"]), _ptr(buf["livel"]), _ptr(buf["dead_u"]), _ptr(buf["live_u"]), C.byref(nf), _ptr(buf["pid"]),
+            _ptr(buf["pit"]), _ptr(buf["pnc"]), _ptr(buf["lit"]), int(bootstrap), int(rebuild_every), _ptr(start_u),
+            _ptr(start_logl), _ptr(start_nc), _ptr(seed_ncall), _ptr(seed_rng)))
+        out = self._ns_result(buf, nf, True, want_samples)
+        out.update(start_u=start_u, start_logl=start_logl, start_nc=start_nc, seed_ncall=seed_ncall, seed_rng=seed_rng)
         return out
 
     def ns_continue(self, dlogz=0.01, max_fills=0, maxiter=None, maxcall=None, logl_max=None, add_live=True,

@@ -15,6 +15,9 @@
 //   at the end: ns_finish  (append the final live points, write the record; reads the state, changes nothing)
 //   dh_ns_continue (a kept ensemble taken further): ns_resume (which runs go on; a fill that a stop rule cut
 //              short is put back) and one ns_consume replay of those fills, then the fills as above
+//   dh_ns_batch (strands of a dynamic batch, started inside a finished run): ns_batch_init, the bound on the seeds,
+//              seed fills of ns_seed_prepare / ns_select / ns_gather / walk / ns_seed_consume, ns_batch_start (the
+//              hand-over), then the fills as above
 //
 // All state (live points, dead points, integrals, RNG) stays in HBM; with
 // 288 GB there is room for the full dead-point history of thousands of runs.
@@ -28,6 +31,7 @@
 #include <cmath>
 
 #include "ctx.h"
+#include "ns_batch_plan.h"
 #include "ns_sort.h"
 #include "ns_state.h"
 #include "rng_pcg64.h"
@@ -164,6 +168,21 @@ struct NsArgs {
   int* sv_n;         // runs: slots saved
   int* rest;         // runs: queue entries the continuation took over (ns_resume)
   int replay;        // 1: ns_consume serves the runs with qstop == -1 only; no tuning, no fill count
+};
+
+// dh_ns_batch: the seeding phase's own arrays (the kernels ns_batch_init, ns_seed_prepare, ns_seed_consume and
+// ns_batch_start take them beside NsArgs, whose layout -- part of a saved image's plan -- stays as it is)
+struct NsSeed {
+  double* u;         // runs x N x D  the staging live set, in the order its points were accepted
+  double* v;         // runs x N x D
+  double* logl;      // runs x N
+  int* nc;           // runs x N      calls of a staged point: its entry's and the rejected entries' before it
+  int* n;            // runs          rows staged
+  long long* rej;    // runs          calls of the rejected entries since the last staged row
+  long long* ncall;  // runs          the calls the phase spent (written at the hand-over)
+  uint64_t* rng;     // runs x 4      the run's generator at the hand-over
+  double* start;     // runs x 6      logvol, logz, h, logzvar, last dead ln L, scale: where the strand joins the base run
+  double logl_min;
 };
 
 __device__ __forceinline__ double logaddexp_dev(double x, double y) {
@@ -2220,6 +2239,280 @@ __global__ void __launch_bounds__(kT) ns_resume(NsArgs a) {
   }
 }
 
+// ---- dh_ns_batch: the seeding phase of a dynamic batch and the hand-over into the loop ------------------------------
+// _configure_batch_sampler (dynamicsampler.py:300-622) for R strands at once.  A strand's live set is first the
+// nlive_new points chosen from the base run (the seeds, all above logl_min); its bound is built on them, once; then
+// nlive_new new points are proposed at the FIXED threshold logl_min from start points among the seeds -- the ordinary
+// ns_select / ns_gather / walk stages -- and collected in a staging set (ns_seed_consume), which replaces the seeds
+// when it is full (ns_batch_start).  From there on the strand is an ordinary run of the loop whose volume and evidence
+// go on from the base run's row at logl_min.  Where this departs from the reference:
+//  (a) the bound is not rebuilt during seeding (the reference's update policy would fire on the calls spent): the seed
+//      points do not change, so a second bound on them would be the first again but for its bootstrap draw;
+//  (b) the last seed fill's unused queue entries are dropped, their calls counted (the reference keeps them in the
+//      queue for the first deaths);
+//  (c) a strand always starts in bound mode (the reference stays on the unit cube while logl_min is below the base
+//      run's first bound update, sampler.py:650-653);
+//  (d) the scale the strand starts with is the caller's (start row, column 5): the merged run keeps no per-point scale
+//      (the reference takes saved_scale[subset0[0]]).
+
+// the strands' states from the start rows, their generators (child 0x80000000 + first_run + run, as ns_init), and the
+// bookkeeping of the one bound update: nbound = 1 at call count 0, its bootstrap words drawn as ns_prepare draws them
+__global__ void __launch_bounds__(kT)
+    ns_batch_init(NsArgs a, NsSeed sd, const uint32_t* __restrict__ entropy, int nwords, uint32_t first_run) {
+  for (int run = threadIdx.x; run < a.runs; run += kT) {
+    const double* s = sd.start + (size_t)run * 6;
+    NsRun r;
+    r.logvol = s[0];
+    r.logz = s[1];
+    r.h = s[2];
+    r.logzvar = s[3];
+    r.dead_prev = s[4];
+    r.scale = s[5];
+    r.lmax = -1e300;
+    r.loglstar = sd.logl_min;
+    r.it = 0;
+    r.ncall = 0;
+    r.ncall_last_update = 0;
+    r.mode = MODE_BOUND;
+    r.need_rebuild = 1;
+    r.nbound = 1;
+    r.nfill = 0;
+    r.acc = r.rej = r.doubling = r.due = 0;
+    r.fpend = r.qstop = 0;
+    r.nc_carry = 0;
+    r.pcount = r.sampler_failed = 0;
+    r.plogdvol = r.var_a = r.var_b = 0.0;
+    Pcg64 g;
+    seed_from_child(g, entropy, nwords, 0x80000000u + first_run + (uint32_t)run);
+    if (a.bootstrap > 0)
+      for (int i = 0; i < 4; ++i) a.boot_ent[(size_t)run * 4 + i] = g.next64();
+    g.store(r.rng);
+    a.st[run] = r;
+    a.rebuild_mask[run] = 1;
+    a.run_mode[run] = MODE_BOUND;
+    sd.n[run] = 0;
+    sd.rej[run] = 0;
+    sd.ncall[run] = 0;
+  }
+}
+
+// before every seed fill: which strands still collect points (the others sit the fill out), the walkers' per-run
+// parameters at the fixed threshold; a strand whose bound could not be built fails, as in ns_prepare.
+__global__ void __launch_bounds__(kT) ns_seed_prepare(NsArgs a, NsSeed sd) {
+  for (int run = threadIdx.x; run < a.runs; run += kT) {
+    NsRun& r = a.st[run];
+    if (r.mode == MODE_BOUND && a.bstatus[run] != DH_OK) {
+      r.mode = MODE_FAILED;
+      atomicAdd(a.ndone, 1);
+    }
+    const int seeding = (r.mode == MODE_BOUND && sd.n[run] < a.nlive) ? 1 : 0;
+    r.need_rebuild = 0;
+    a.rebuild_mask[run] = 0;
+    a.run_mode[run] = seeding ? MODE_BOUND : MODE_WAIT;
+    a.run_loglstar[run] = sd.logl_min;
+    a.run_scale[run] = r.scale;
+    a.run_doubling[run] = r.doubling;
+  }
+}
+
+// One seed fill's queue, one workgroup per strand: in queue order every entry above logl_min joins the staging set
+// (u, v, ln L, nc = its calls and those of the rejected entries before it) until the set holds nlive_new points; all
+// of the fill's calls are charged to the strand, and the sampler's scale is tuned as ns_consume tunes it for a fill.
+// No live point is replaced.  Which entry gets which row is a serial pass of one thread over the queue's values in LDS
+// (K <= 2048 reads, once per seed fill, nlive_new / K fills per batch: an entry is rejected only when its slice
+// failed); the rows' coordinates are then copied by all threads, sixteen elements of a thread in flight.
+__global__ void __launch_bounds__(kT) ns_seed_consume(NsArgs a, NsSeed sd) {
+  constexpr int kQ = kEPTMax * kT;
+  __shared__ double ql[kQ];
+  __shared__ int qc[kQ];
+  __shared__ int tj[kQ];   // queue index of the c-th entry this fill stages
+  __shared__ int tnc[kQ];  // ... and its nc
+  __shared__ int racc[kT], rrej[kT];
+  __shared__ int ntake_s, n0_s;
+  const int run = blockIdx.x, t = threadIdx.x;
+  const int N = a.nlive, D = a.ndim, K = a.K;
+  NsRun& r = a.st[run];
+  if (r.mode != MODE_BOUND || a.run_mode[run] != MODE_BOUND) return;
+  int acc = 0, rej = 0, bad = 0, dbl = 0;
+  for (int j = t; j < K; j += kT) {
+    const size_t q = (size_t)run * K + j;
+    // (every load unconditional, from a clamped offset where the index is data: selects below)
+    const double rl = a.r_logl[q];
+    const int ra = a.r_a[q], rb = a.r_b[q], rc = a.r_c[q], rd = a.r_d[q];
+    const double own = a.live_logl[(size_t)run * N + ((unsigned)rd < (unsigned)N ? rd : 0)];
+    double l = rl;
+    int c = ra;
+    if (a.sampler == 3) {
+      if (rb & 3) l = -INFINITY;  // no ellipsoid held the draw / the try limit: the strand fails below
+      bad |= rb & 3;
+    } else if (a.sampler == 0) {
+      c = a.walks;
+      acc += ra;
+      rej += rb;
+      if (ra == 0) l = own;  // no step accepted: the start point (a seed) with its own stored ln L, as in ns_consume
+    } else {
+      acc += rb;  // n_expand
+      rej += rc;  // n_contract
+      dbl |= rd & 1;
+      if (rd & 2) l = -INFINITY;  // failed slice: never accepted
+    }
+    ql[j] = l;
+    qc[j] = c;
+  }
+  racc[t] = acc;
+  rrej[t] = rej;
+  bad = __syncthreads_or(bad);
+  dbl = __syncthreads_or(dbl);
+  for (int sft = kT / 2; sft > 0; sft >>= 1) {
+    if (t < sft) {
+      racc[t] += racc[t + sft];
+      rrej[t] += rrej[t + sft];
+    }
+    __syncthreads();
+  }
+  // (the rows staged so far are read by the ONE thread that also stores the new count, and reach the others through
+  // LDS behind the barrier below: a wave that read the global count itself could read it after that store)
+  if (t == 0) {
+    long long pend = sd.rej[run], calls = 0;
+    const int first = sd.n[run];
+    int n = first;
+    for (int j = 0; j < K; ++j) {
+      const int c = qc[j];
+      calls += c;
+      if (n < N && ql[j] > sd.logl_min) {
+        tj[n - first] = j;
+        tnc[n - first] = (int)(pend + c);
+        pend = 0;
+        ++n;
+      } else {
+        pend += c;  // (behind the last row: dropped with the fill, departure (b))
+      }
+    }
+    ntake_s = n - first;
+    n0_s = first;
+    sd.n[run] = n;
+    sd.rej[run] = pend;
+    r.ncall += calls;
+    if (dbl) r.doubling = 1;
+    if (a.sampler != 3) {
+      const int ta = racc[0], tr = rrej[0];
+      if (a.sampler == 0) {
+        // RWalkSampler.tune (internal_samplers.py:460-493), once per queue fill
+        if (ta + tr > 0) r.scale *= exp(((double)ta / (double)(ta + tr) - a.facc) / (double)D / a.facc);
+      } else {
+        // tune_slice (internal_samplers.py:1209-1239)
+        const double ne = ta > 1 ? (double)ta : 1.0, nt = (double)tr;
+        double mult = ne * 2.0 / (ne + nt);
+        mult = fmin(fmax(mult, 0.5), 2.0);
+        r.scale *= mult;
+      }
+    }
+    if (bad) {  // a uniform-sampler walker gave up: the reference's RuntimeError
+      r.sampler_failed = 1;
+      r.mode = MODE_FAILED;
+      atomicAdd(a.ndone, 1);
+    }
+  }
+  __syncthreads();
+  const int ntake = ntake_s, n0 = n0_s;
+  for (int c = t; c < ntake; c += kT) {
+    sd.logl[(size_t)run * N + n0 + c] = ql[tj[c]];
+    sd.nc[(size_t)run * N + n0 + c] = tnc[c];
+  }
+  double* su = sd.u + ((size_t)run * N + n0) * D;
+  double* sv = sd.v + ((size_t)run * N + n0) * D;
+  const double* ru = a.r_u + (size_t)run * K * D;
+  const double* rv = a.r_v + (size_t)run * K * D;
+  const int tot = ntake * D;
+  constexpr int LS = 16;
+  for (int e0 = t; e0 < tot; e0 += LS * kT) {
+    double xu[LS], xv[LS];
+#pragma unroll
+    for (int q = 0; q < LS; ++q) {
+      const int e = e0 + q * kT;
+      const int ec = e < tot ? e : 0;
+      const int c = ec / D, j = ec - c * D;
+      const size_t from = (size_t)tj[c] * D + j;
+      xu[q] = ru[from];
+      xv[q] = rv[from];
+    }
+#pragma unroll
+    for (int q = 0; q < LS; ++q)
+      if (e0 + q * kT < tot) {
+        su[e0 + q * kT] = xu[q];
+        sv[e0 + q * kT] = xv[q];
+      }
+  }
+}
+
+// The hand-over, one workgroup per strand: the staging set becomes the live set (every point proposed at iteration 0),
+// lmax / loglstar are its largest / smallest ln L as ns_start takes them, the loop's counters start at 0 and the
+// volume, the evidence sums and the last dead ln L are the start row's (ns_batch_init put them there; seeding does not
+// touch them).  A strand whose staging set is not full after the seed fills has failed.
+__global__ void __launch_bounds__(kT) ns_batch_start(NsArgs a, NsSeed sd) {
+  const int run = blockIdx.x, t = threadIdx.x, N = a.nlive, D = a.ndim;
+  NsRun& r = a.st[run];
+  __shared__ double rmax[kT], rmin[kT];
+  if (r.mode != MODE_BOUND) return;
+  if (sd.n[run] < N) {
+    if (t == 0) {
+      r.mode = MODE_FAILED;
+      atomicAdd(a.ndone, 1);
+      sd.ncall[run] = r.ncall;
+    }
+    return;
+  }
+  double mx = -1e300, mn = INFINITY;
+  for (int i = t; i < N; i += kT) {
+    const double k = sd.logl[(size_t)run * N + i];
+    a.live_logl[(size_t)run * N + i] = k;
+    if (a.live_it) a.live_it[(size_t)run * N + i] = 0;
+    mx = fmax(mx, k);
+    mn = fmin(mn, k);
+  }
+  rmax[t] = mx;
+  rmin[t] = mn;
+  __syncthreads();
+  for (int s = kT / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      rmax[t] = fmax(rmax[t], rmax[t + s]);
+      rmin[t] = fmin(rmin[t], rmin[t + s]);
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    r.lmax = rmax[0];
+    r.loglstar = rmin[0];
+    r.it = 0;
+    r.nc_carry = 0;
+    sd.ncall[run] = r.ncall;
+    for (int i = 0; i < 4; ++i) sd.rng[(size_t)run * 4 + i] = r.rng[i];
+  }
+  // (the rows of a strand are contiguous: sixteen elements of a thread in flight, as in ns_consume's live store)
+  const double* su = sd.u + (size_t)run * N * D;
+  const double* sv = sd.v + (size_t)run * N * D;
+  double* lu = a.live_u + (size_t)run * N * D;
+  double* lv = a.live_v + (size_t)run * N * D;
+  const size_t tot = (size_t)N * D;
+  constexpr int LS = 16;
+  for (size_t e0 = t; e0 < tot; e0 += (size_t)LS * kT) {
+    double xu[LS], xv[LS];
+#pragma unroll
+    for (int q = 0; q < LS; ++q) {
+      const size_t e = e0 + (size_t)q * kT;
+      const size_t ec = e < tot ? e : 0;
+      xu[q] = su[ec];
+      xv[q] = sv[ec];
+    }
+#pragma unroll
+    for (int q = 0; q < LS; ++q)
+      if (e0 + (size_t)q * kT < tot) {
+        lu[e0 + (size_t)q * kT] = xu[q];
+        lv[e0 + (size_t)q * kT] = xv[q];
+      }
+  }
+}
+
 }  // namespace
 
 namespace {
@@ -2278,6 +2571,9 @@ struct NsAux {
   int* fr_scratch;
   double* frr;
   int* fnc;
+  // dh_ns_batch: the seeding phase's arrays (set `batch` before ns_arrays to have them carved)
+  bool batch = false;
+  NsSeed seed{};
 };
 
 int ns_plan(dh_ctx* ctx, const double* opt, size_t n_bc, int problem, int runs, int nlive, int ndim, int queue_size,
@@ -2531,6 +2827,16 @@ void ns_arrays(NsCarver& c, const NsPlan& p, NsArgs& a, NsAux& x, int n_words, b
   c(a.sv_it, R * K, p.keep);
   c(a.sv_n, R, p.keep, 0);
   c(a.rest, R, p.keep, 0);
+  // the seeding phase of a dynamic batch (dh_ns_batch): never part of a saved image (ns_entry_kind)
+  c(x.seed.u, R * N * D, x.batch);
+  c(x.seed.v, R * N * D, x.batch);
+  c(x.seed.logl, R * N, x.batch);
+  c(x.seed.nc, R * N, x.batch);
+  c(x.seed.n, R, x.batch, 0);
+  c(x.seed.rej, R, x.batch, 0);
+  c(x.seed.ncall, R, x.batch, 0);
+  c(x.seed.rng, R * 4, x.batch, 0);
+  c(x.seed.start, R * 6, x.batch);
   a.presort = x.presort;
 }
 
@@ -3025,6 +3331,131 @@ int dh_ns_ensemble(dh_ctx* ctx, int problem, int runs, int nlive, int ndim, int 
   return cleanup(DH_OK);
 }
 
+// see include/dynhip.h and the kernels' header comment (ns_batch_init ... ns_batch_start)
+int dh_ns_batch(dh_ctx* ctx, int problem, int runs, int nlive_new, int ndim, int queue_size, int sampler, int walks,
+                int bound, double dlogz, double enlarge, int64_t max_fills, int64_t max_iter,
+                const uint32_t* entropy_words, int n_words, uint32_t first_run, const double* seed_u,
+                const double* seed_logl, double logl_min, const double* start, double* records,
+                double* dead_logl_out, double* live_logl_out, double* dead_u_out, double* live_u_out,
+                int64_t* n_fills_out, int32_t* dead_id_out, int32_t* dead_it_out, int32_t* dead_nc_out,
+                int32_t* live_it_out, int bootstrap, int rebuild_every, double* start_u_out, double* start_logl_out,
+                int32_t* start_nc_out, int64_t* seed_ncall_out, uint64_t* seed_rng_out) {
+  DH_CHECK_CTX(ctx);
+  // one-shot options, boundary flags and the keep switch, as for dh_ns_ensemble: taken and forgotten however this ends
+  double opt[DH_NS_OPT_COUNT];
+  for (int i = 0; i < DH_NS_OPT_COUNT; ++i) {
+    opt[i] = ctx->ns_opt[i];
+    ctx->ns_opt[i] = __builtin_nan("");
+  }
+  std::vector<int8_t> bc;
+  bc.swap(ctx->ns_bc);
+  const int keep = ctx->ns_keep;
+  ctx->ns_keep = 0;
+  // ---- plan: everything that can be refused is refused before the device is touched ----
+  namespace nb = dh_nsb;
+  const nb::Request req = {runs,     nlive_new, ndim,   queue_size, sampler,
+                           bound,    keep,      logl_min, std::isnan(opt[DH_NS_OPT_LOGL_MAX]) ? INFINITY : opt[DH_NS_OPT_LOGL_MAX],
+                           seed_u,   seed_logl, start};
+  long long where = -1;
+  const int verdict = nb::check(req, &where);
+  if (verdict != nb::V_OK) return fail(ctx, DH_ERR_ARG, "ns_batch: %s (index %lld)", nb::verdict_text(verdict), where);
+  if (!seed_ncall_out) return fail(ctx, DH_ERR_ARG, "ns_batch: seed_ncall_out is required");
+  NsPlan p;
+  int rc = ns_plan(ctx, opt, bc.size(), problem, runs, nlive_new, ndim, queue_size, sampler, walks, bound, 0, dlogz,
+                   enlarge, max_fills, max_iter, entropy_words, n_words, first_run, records, dead_u_out != nullptr,
+                   !!dead_id_out + !!dead_it_out + !!dead_nc_out + !!live_it_out, bootstrap, rebuild_every, &p);
+  if (rc) return rc;
+  p.keep = false;
+  p.n_words = n_words;
+  p.have_bc = !bc.empty();
+  const nb::Sizes sz = nb::sizes(runs, nlive_new, ndim, queue_size);
+  NsArgs a = p.a;
+  NsAux x;
+  x.batch = true;
+  const int R = a.runs, N = a.nlive, D = a.ndim, K = a.K;
+  NsCarver sizes{ctx, nullptr};
+  ns_arrays(sizes, p, a, x, n_words, p.have_bc);
+  {
+    // the plan's size of the seeding arrays is what the layout carves for them
+    NsAux plain;
+    NsArgs a0 = p.a;
+    NsCarver without{ctx, nullptr};
+    ns_arrays(without, p, a0, plain, n_words, p.have_bc);
+    if (sizes.off - without.off != sz.stage_bytes)
+      return fail(ctx, DH_ERR_ARG, "ns_batch: the plan sizes the seeding arrays at %zu bytes, the layout at %zu",
+                  sz.stage_bytes, sizes.off - without.off);
+  }
+  char* base = nullptr;
+  (void)hipSetDevice(ctx->device);
+  if (!hip_ok(ctx, hipMalloc((void**)&base, sizes.off), "hipMalloc(ns batch state)")) return DH_ERR_NOMEM;
+  hipStream_t s = ctx->stream;
+  auto cleanup = [&](int code) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(base);
+    return code;
+  };
+  NsCarver carve{ctx, base};
+  ns_arrays(carve, p, a, x, n_words, p.have_bc);
+  NsSeed sd = x.seed;
+  sd.logl_min = logl_min;
+  const size_t RN = (size_t)R * N;
+  // the seeds are the strands' live sets: stored values, not evaluated again (their v is never read: the seeds leave
+  // before any of them can die)
+  if (!carve.ok ||
+      (x.bc && !hip_ok(ctx, hipMemcpyAsync(x.bc, bc.data(), (size_t)D, hipMemcpyHostToDevice, s), "H2D bc")) ||
+      !hip_ok(ctx, hipMemcpyAsync(x.ent, entropy_words, (size_t)n_words * 4, hipMemcpyHostToDevice, s), "H2D") ||
+      !hip_ok(ctx, hipMemcpyAsync(a.live_u, seed_u, RN * D * 8, hipMemcpyHostToDevice, s), "H2D seed u") ||
+      !hip_ok(ctx, hipMemcpyAsync(a.live_logl, seed_logl, RN * 8, hipMemcpyHostToDevice, s), "H2D seed logl") ||
+      !hip_ok(ctx, hipMemcpyAsync(sd.start, start, (size_t)R * 6 * 8, hipMemcpyHostToDevice, s), "H2D start") ||
+      !hip_ok(ctx, hipMemsetAsync(a.live_v, 0, RN * D * 8, s), "memset"))
+    return cleanup(DH_ERR_HIP);
+  if (!ns_set_lds(ctx, K, p.lds_cons > p.lds_fin ? p.lds_cons : p.lds_fin, true)) return cleanup(DH_ERR_HIP);
+  // ---- phase S: the bound on the seeds, once; then the seed fills at the fixed threshold ----
+  hipLaunchKernelGGL(ns_batch_init, dim3(1), dim3(kT), 0, s, a, sd, x.ent, n_words, first_run);
+  rc = build_bounds(ctx, p, a, x);
+  if (rc) return cleanup(rc);
+  // Exactly ceil(nlive_new / K) fills, enqueued without a look at the device.  No membership test of the start points:
+  // they are seeds, and the bound was built on the seeds (and only ever enlarged), so every one lies inside it and
+  // the forced update the test exists for cannot be due.  An entry is lost only to a failed slice; a strand whose
+  // staging set is short after these fills fails (ns_batch_start).
+  for (int f = 0; f < sz.seed_fills; ++f) {
+    hipLaunchKernelGGL(ns_seed_prepare, dim3(1), dim3(kT), 0, s, a, sd);
+    a.fx_pass = 0;
+    hipLaunchKernelGGL(ns_select, dim3(R), dim3(kT), 0, s, a);
+    if (a.sampler != 3)
+      hipLaunchKernelGGL(ns_gather, dim3((unsigned)(((size_t)R * K * D + 255) / 256)), dim3(256), 0, s, a);
+    rc = walk_stage(ctx, p, a, x, f, false);
+    if (rc) return cleanup(rc);
+    // (rwalk: walk_stage lets the generator pass presort the live ln L beside the walk, as in every fill of the loop;
+    // here the order is the seeds' and nothing consumes it -- a few workgroups of wasted work per seed fill, kept
+    // rather than giving walk_stage a second form)
+    a.presorted = 0;
+    hipLaunchKernelGGL(ns_seed_consume, dim3(R), dim3(kT), 0, s, a, sd);
+  }
+  hipLaunchKernelGGL(ns_batch_start, dim3(R), dim3(kT), 0, s, a, sd);
+  if (!hip_ok(ctx, hipGetLastError(), "ns_batch_start launch")) return cleanup(DH_ERR_HIP);
+  // ---- from here the loop dh_ns_ensemble runs: its fills count from 0 ----
+  int64_t fill = 0;
+  int l_state[2] = {0, 0};
+  bool cube_phase = false;
+  rc = ns_fill_loop(ctx, p, a, x, &fill, p.fills_cap, l_state, &cube_phase);
+  if (rc) return cleanup(rc);
+  hipLaunchKernelGGL(ns_finish, dim3(R), dim3(kT), p.lds_fin, s, a);
+  if (!hip_ok(ctx, hipGetLastError(), "ns launch") ||
+      !download(ctx, a, records, dead_logl_out, live_logl_out, dead_u_out, live_u_out, dead_id_out, dead_it_out,
+                dead_nc_out, live_it_out))
+    return cleanup(DH_ERR_HIP);
+  static_assert(sizeof(long long) == sizeof(int64_t), "seed_ncall");
+  if (!down(ctx, (long long*)seed_ncall_out, sd.ncall, (size_t)R) ||
+      (start_u_out && !down(ctx, start_u_out, sd.u, RN * D)) ||
+      (start_logl_out && !down(ctx, start_logl_out, sd.logl, RN)) ||
+      (start_nc_out && !down(ctx, (int*)start_nc_out, sd.nc, RN)) ||
+      (seed_rng_out && !down(ctx, seed_rng_out, sd.rng, (size_t)R * 4)))
+    return cleanup(DH_ERR_HIP);
+  if (n_fills_out) *n_fills_out = fill;
+  return cleanup(DH_OK);
+}
+
 }  // extern "C"
 
 // ---- a kept ensemble between two calls: dh_ns_continue, dh_ns_state_size / _export / _import (ns_state.h) ----------
@@ -3040,7 +3471,9 @@ int ns_entry_kind(const NsArgs& a, const NsAux& x, const void* ptr, size_t* elem
   if (ptr == a.dead_u) return *elem = 8 * (size_t)a.ndim, ENT_DEAD;
   if (ptr == a.dead_id || ptr == a.dead_it || ptr == a.dead_nc) return *elem = 4, ENT_DEAD;
   if (ptr == a.fin_ws || ptr == x.boot_ws || ptr == x.fr_ws || ptr == x.presort || ptr == a.prof || ptr == x.fr_mask ||
-      ptr == x.fr_scratch || ptr == a.records)
+      ptr == x.fr_scratch || ptr == a.records || ptr == x.seed.u || ptr == x.seed.v || ptr == x.seed.logl ||
+      ptr == x.seed.nc || ptr == x.seed.n || ptr == x.seed.rej || ptr == x.seed.ncall || ptr == x.seed.rng ||
+      ptr == x.seed.start)
     return ENT_SKIP;
   return ENT_FIXED;
 }

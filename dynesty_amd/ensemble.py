@@ -234,6 +234,11 @@ class MergedRun(dict, Marginals, Errors):
         if self.get("samples_run") is None or self.get("samples_id") is None:
             raise ValueError("the strand bootstrap needs the points' bookkeeping: merge with dead_id / dead_it / "
                              "dead_nc / live_it (samples_run and samples_id)")
+        if self.get("samples_batch") is not None:
+            # (strands are read off a live count that only falls: S = n[0], a final point wherever it drops; on a run
+            # with batches n rises where a batch joins, and both would be wrong)
+            raise ValueError("the strand bootstrap is not defined here for a run that carries dynamic batches "
+                             "(dynamic.merge_batch): use the volume realizations (error='jitter')")
         n = np.asarray(self["samples_n"], dtype=np.int64)
         run = np.asarray(self["samples_run"], dtype=np.int64)
         S, R = int(n[0]), int(run.max()) + 1

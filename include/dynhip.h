@@ -680,6 +680,51 @@ int dh_ns_continue(dh_ctx* ctx, double dlogz, int64_t max_fills, double* records
                    int32_t* dead_id_out, int32_t* dead_it_out, int32_t* dead_nc_out, int32_t* live_it_out,
                    int32_t* rest_out /* optional, runs: unspent queue entries each run took over */);
 
+/* ---- a dynamic batch: strands started inside a finished run (csrc/ns.hip, csrc/ns_batch_plan.h) ----
+ * dh_ns_batch runs `runs` strands of nlive_new live points each inside the ln L range (logl_min, logl_max] of a
+ * finished run: the reference's _configure_batch_sampler + sample_batch (dynamicsampler.py:300-622, 1228-1465).  The
+ * arguments, the one-shot options (logl_max comes through DH_NS_OPT_LOGL_MAX), the boundary flags, the records and the
+ * outputs are those of dh_ns_ensemble with nlive = nlive_new (rebuild_sync is 0), plus:
+ *   seed_u (runs x nlive_new x ndim), seed_logl (runs x nlive_new): every strand's seeds, points of the finished run
+ *     with ln L > logl_min, as stored: they are not evaluated again (the reference copies them);
+ *   logl_min: finite; start (runs x 6): logvol, logz, h, logzvar and ln L of the finished run's row at logl_min -- where
+ *     the strand's volume and running evidence go on from -- and the sampler's scale the strand starts with;
+ *   start_u_out / start_logl_out / start_nc_out (optional, runs x nlive_new (x ndim)): the live set the sampling phase
+ *     begins with, in the order the points were accepted, and the calls spent on each; seed_ncall_out (runs, required):
+ *     the likelihood calls of the seeding phase; seed_rng_out (optional, runs x 4): the strand's generator at the
+ *     hand-over.
+ * Phase S (seeding).  The seeds are the strand's live set; its bound is built on them once (nbound = 1, masked rebuild,
+ *   bootstrap expansion, enlarge); ceil(nlive_new / queue_size) fills of the ordinary selection / walk stages at the
+ *   fixed threshold logl_min, start points drawn among the seeds, fill a staging set in queue order (nc of a point: its
+ *   entry's calls and the rejected entries' before it); every call is charged; the scale is tuned once per fill.  The
+ *   staging set then replaces the seeds (it = 0 for every point) and the loop of dh_ns_ensemble goes on from there, its
+ *   counters at 0: niter counts the strand's own deaths, ncall = seed calls + the calls of the sampling phase.  The
+ *   record's logz / logzerr / h are the RUNNING values continued from the start row: they steer the dlogz stop as in the
+ *   reference's batch sampler and are not results -- the combined run's integrals are recomputed by whoever merges.
+ * Streams.  Strand r has the streams dh_ns_ensemble gives run first_run + r (generator: child 0x80000000 + first_run +
+ *   r of the entropy): an ensemble of strands equals its shards, bit for bit.
+ * Departures from the reference: (a) the bound is not rebuilt during seeding (the seeds do not change); (b) the last seed
+ *   fill's unused queue entries are dropped, their calls counted (the reference pops them for the first deaths); (c) a
+ *   strand always starts in bound mode (the reference stays on the unit cube while logl_min is below the base run's
+ *   first bound update); (d) the starting scale is the caller's (the reference takes the saved scale of the lowest
+ *   point above logl_min).
+ * DH_ERR_ARG, decided before the device is touched, the context left usable: the Philox samplers (3, 4, 5, 7), the
+ *   friends bounds (2, 3), an armed dh_ns_keep, a non-finite logl_min (a batch from the prior is dh_ns_ensemble with
+ *   logl_max), a seed with seed_logl <= logl_min, nlive_new below 4 or above 65535 (the loop's own limits), logl_max <=
+ *   logl_min, a non-finite start row or a scale <= 0, and whatever dh_ns_ensemble refuses for the same shape.
+ * The seed fills are exactly ceil(nlive_new / queue_size), enqueued without a look at the device, and run without the
+ *   start points' membership test (the start points are the seeds the bound was built on).  An entry is lost only to a
+ *   failed slice; a strand whose staging set is not full after the seed fills ends with status -1. */
+int dh_ns_batch(dh_ctx* ctx, int problem, int runs, int nlive_new, int ndim, int queue_size,
+                int sampler /* 0 rwalk, 1 rslice, 2 slice, 6 unif */, int walks /* or slices */,
+                int bound /* 0 single, 1 multi */, double dlogz, double enlarge, int64_t max_fills, int64_t max_iter,
+                const uint32_t* entropy_words, int n_words, uint32_t first_run, const double* seed_u,
+                const double* seed_logl, double logl_min, const double* start, double* records,
+                double* dead_logl_out, double* live_logl_out, double* dead_u_out, double* live_u_out,
+                int64_t* n_fills_out, int32_t* dead_id_out, int32_t* dead_it_out, int32_t* dead_nc_out,
+                int32_t* live_it_out, int bootstrap, int rebuild_every, double* start_u_out, double* start_logl_out,
+                int32_t* start_nc_out, int64_t* seed_ncall_out, uint64_t* seed_rng_out);
+
 /* The kept ensemble as one host buffer and back.  The image holds a header (magic, DH_VERSION, sizeof of the per-run
  * state, the shapes, the fill counter, whether the unit-cube phase is still on), every argument and resolved plan value
  * of the first call, and the state arrays; the five dead-point arrays (ln L, u, id, it, nc) by each run's first niter

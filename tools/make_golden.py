@@ -845,6 +845,110 @@ def gen_merge_dynamic(out, merge_npz):
     print("wrote", out, len(g), "arrays,", os.path.getsize(out), "bytes")
 
 
+class _ChoiceRecorder(np.random.Generator):
+    """A numpy Generator (a real one: the reference tests isinstance) whose choice() results, and the bit generator's
+    state before each, are kept in `calls`."""
+
+    def choice(self, *a, **kw):
+        if not hasattr(self, "calls"):
+            self.calls = []
+        before = _pcg_state(self)
+        d = super().choice(*a, **kw)
+        self.calls.append((before, np.array(d)))
+        return d
+
+
+def _pcg_state(rng):
+    """[state hi, state lo, inc hi, inc lo, has_uint32, uinteger] of a PCG64 generator."""
+    st = rng.bit_generator.state
+    s, i = int(st["state"]["state"]), int(st["state"]["inc"])
+    m = (1 << 64) - 1
+    return np.array([s >> 64, s & m, i >> 64, i & m, int(st["has_uint32"]), int(st["uinteger"])], dtype=np.uint64)
+
+
+def gen_batch(out):
+    """Dynamic batches (tests/test_dynamic_cpu.py): a 3-D unit Gaussian exp(-|x|^2 / 2) under a uniform prior on
+    [-10, 10]^3, DynamicNestedSampler.run_nested(nlive_init=50, nlive_batch=50, maxbatch=3), seed 20.  For every batch b:
+    the saved run before it (b/base/*), the generator's state before _configure_batch_sampler's weighted choice and the
+    chosen subset, the bounds it was given and the adjusted ones it returned, vol_idx (the rows it left in the batch
+    sampler's saved run), the new run (b/new/*) and the saved run after combine_runs (b/after/*).  Then three calls of
+    _configure_batch_sampler on the first saved run (sel/0..2): a bound with fewer than nlive_new points above it, a
+    bound below every point, and logl_bounds=None."""
+    import dynesty
+    from dynesty import dynamicsampler as dys
+
+    def loglike(x):
+        return -0.5 * float(np.dot(x, x))
+
+    def ptform(u):
+        return 20.0 * u - 10.0
+    NL = 50
+    rec = _ChoiceRecorder(np.random.PCG64(20))
+    rec.calls = []
+    ds = dynesty.DynamicNestedSampler(loglike, ptform, 3, nlive=NL, rstate=rec, sample="rwalk", bound="multi")
+    g = dict(nlive=np.array(NL))
+    keys = ("logl", "logvol", "n", "id", "it", "nc", "u", "logz", "logzvar", "h", "batch")
+
+    def saved(prefix, run, which=keys):
+        for k in which:
+            g[f"{prefix}/{k}"] = np.array(run[k])
+    state = dict(b=0, first=None)
+    conf0, comb0 = dys._configure_batch_sampler, dys.DynamicSampler.combine_runs
+
+    def conf(main_sampler, nlive_new, update_interval, logl_bounds=None, save_bounds=None):
+        b = state["b"]
+        saved(f"{b}/base", main_sampler.saved_run)
+        if state["first"] is None:
+            state["first"] = main_sampler
+        ncalls = len(rec.calls)
+        res = conf0(main_sampler, nlive_new, update_interval, logl_bounds=logl_bounds, save_bounds=save_bounds)
+        g[f"{b}/bounds_in"] = np.array(logl_bounds, dtype=np.float64)
+        g[f"{b}/bounds_out"] = np.array([res[3], res[4]], dtype=np.float64)
+        g[f"{b}/vol_idx"] = np.array(len(res[0].saved_run["logl"]))
+        if len(rec.calls) > ncalls:
+            g[f"{b}/rstate"], g[f"{b}/subset"] = rec.calls[ncalls]
+        return res
+
+    def comb(self):
+        b = state["b"]
+        saved(f"{b}/new", self.new_run, ("logl", "n", "id", "it", "nc", "u"))
+        g[f"{b}/new_bounds"] = np.array([self.new_logl_min, self.new_logl_max], dtype=np.float64)
+        comb0(self)
+        saved(f"{b}/after", self.saved_run, keys + ("logwt",))
+        g[f"{b}/after/batch_nlive"] = np.array(self.saved_run["batch_nlive"])
+        g[f"{b}/after/batch_bounds"] = np.array(self.saved_run["batch_logl_bounds"], dtype=np.float64)
+        state["b"] = b + 1
+    dys._configure_batch_sampler, dys.DynamicSampler.combine_runs = conf, comb
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            ds.run_nested(nlive_init=NL, nlive_batch=NL, maxbatch=3, print_progress=False)
+        g["nbatch"] = np.array(state["b"])
+        # three constructed selections on the FIRST saved run: the sampler is wound back to it
+        first = {k: g[f"0/base/{k}"] for k in keys}
+        for k in keys:
+            ds.saved_run[k] = list(first[k])
+        ll = first["logl"]
+        cases = [(float(ll[-NL // 2]), float(ll[-1])),  # fewer than nlive_new points above the bound
+                 (float(ll[0]) - 1.0, float(ll[-1])),   # below every point: the batch starts from the prior
+                 None]
+        for i, lb in enumerate(cases):
+            ncalls = len(rec.calls)
+            before = _pcg_state(rec)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                res = conf0(ds, NL, NL, logl_bounds=lb, save_bounds=False)
+            g[f"sel/{i}/bounds_in"] = np.array([np.nan, np.nan] if lb is None else lb, dtype=np.float64)
+            g[f"sel/{i}/bounds_out"] = np.array([res[3], res[4]], dtype=np.float64)
+            g[f"sel/{i}/vol_idx"] = np.array(len(res[0].saved_run["logl"]))
+            g[f"sel/{i}/rstate"] = rec.calls[ncalls][0] if len(rec.calls) > ncalls else before
+            g[f"sel/{i}/subset"] = rec.calls[ncalls][1] if len(rec.calls) > ncalls else np.zeros(0, dtype=np.int64)
+    finally:
+        dys._configure_batch_sampler, dys.DynamicSampler.combine_runs = conf0, comb0
+    np.savez_compressed(out, **g)
+    print("wrote", out, len(g), "arrays,", os.path.getsize(out), "bytes; batches", state["b"])
+
+
 def _ell_hp_one(key):
     import ell_hp_ref
     return key, ell_hp_ref.case_record(key)
@@ -1042,5 +1146,7 @@ if __name__ == "__main__":
         gen_merge_bootstrap(os.path.join(gdir, "merge_bootstrap.npz"), os.path.join(gdir, "merge.npz"))
     if "merge_dynamic" in which:  # not in the default list; reads merge.npz, which stays as it is
         gen_merge_dynamic(os.path.join(gdir, "merge_dynamic.npz"), os.path.join(gdir, "merge.npz"))
+    if "batch" in which:  # not in the default list: tests/test_dynamic_cpu.py
+        gen_batch(os.path.join(gdir, "batch_combine.npz"))
     if "livesets" in which:  # not in the default list: two partial reference runs (minutes)
         gen_livesets(os.path.join(gdir, "livesets.npz"))
