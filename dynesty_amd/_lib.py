@@ -7,6 +7,7 @@ with ``python -c "import __graft_entry__ as g; g.build()"`` or
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -138,7 +139,9 @@ SIGNATURES = {
     "dh_merged_moments": (_i, [_vp, _vp, _vp]),
     "dh_merged_resample": (_i, [_vp, _dbl, C.c_int64, _vp]),
     "dh_merged_gather": (_i, [_vp, C.c_int64, _vp, _vp]),
+    "dh_merged_gather_rows": (_i, [_vp, _i, C.c_int64, _vp, _vp]),
     "dh_merged_release": (_i, [_vp]),
+    "dh_merged_fold": (_i, [_vp, _i, _i, _i, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp]),
     "dh_merged_quantile": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     "dh_merged_hist1d": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp]),
     "dh_merged_hist2d": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
@@ -276,6 +279,9 @@ MERGED_FIELDS = dict(logl=(0, np.float64, False), logvol=(1, np.float64, False),
 BOOT_RUN_FIELDS = dict(idx=(16, np.int64), samples_n=(11, np.int32), logvol=(1, np.float64), logwt=(2, np.float64),
                        logz=(3, np.float64))
 MERGED_KLD = 17  # DH_MERGED_KLD: the cumulative divergence (dh_merged_realization, dh_merged_bootstrap_run)
+MERGED_BATCH = 18  # DH_MERGED_BATCH: the dynamic batch of every point (dh_merged_fetch); 0 on a run that holds none
+# what DeviceMergedRun.field fetches: the fields of the enum and the batch column
+FETCH_FIELDS = dict(MERGED_FIELDS, samples_batch=(MERGED_BATCH, np.int32, False))
 SUMMARY_FIELDS = ("niter", "logz", "logzerr", "h", "ess", "ncall")
 
 
@@ -288,11 +294,20 @@ class DeviceMergedRun(dict, Marginals, Errors):
     dh_merged_realization; and the strand bootstrap's bootstrap_realizations / resample_run / simulate_run /
     logz_error_sampling / logz_error_total: dh_merged_bootstrap, dh_merged_bootstrap_run (a merge with id / it / nc);
     and kld_realizations / kld_error / weight_function / stopping_function: dh_merged_kld, the KLD field of the two
-    per-point calls, dh_merged_weight_function, dh_merged_weights."""
+    per-point calls, dh_merged_weight_function, dh_merged_weights.
 
-    def __init__(self, ctx, summary, ndim, have_pt):
+    A run that Context.merged_fold folded dynamic batches into carries batch_nlive and batch_bounds (host lists with
+    dynamic.merge_batch's conventions: entry 0 is the base run, then one entry per strand) and the per-point field
+    samples_batch; both lists are empty on a run that holds no batch.  On such a run the strand bootstrap raises
+    ValueError, as ensemble.MergedRun's does; the volume realizations, the weight function, the marginals, the moments
+    and the resampling work unchanged."""
+
+    def __init__(self, ctx, summary, ndim, have_pt, batch_nlive=(), batch_bounds=(), prob=None):
         super().__init__()
         self.ctx, self.ndim, self.have_pt = ctx, int(ndim), bool(have_pt)
+        self.prob = prob  # the problem the run was merged with (dynamic.fold_batch folds with it)
+        self.batch_nlive = [int(x) for x in batch_nlive]
+        self.batch_bounds = [(float(lo), float(hi)) for lo, hi in batch_bounds]
         self.summary = dict(zip(SUMMARY_FIELDS, [float(x) for x in summary]))
         self.summary["niter"] = int(self.summary["niter"])
         self.summary["ncall"] = int(self.summary["ncall"])
@@ -305,12 +320,12 @@ class DeviceMergedRun(dict, Marginals, Errors):
         return self.ctx
 
     def field(self, name, first=0, count=None):
-        """`count` points of one per-point field from point `first` on (MERGED_FIELDS names)."""
+        """`count` points of one per-point field from point `first` on (FETCH_FIELDS names)."""
         ctx = self._live()
-        if name not in MERGED_FIELDS:
-            raise ValueError(f"merged field {name!r}: one of {sorted(MERGED_FIELDS)}")
-        code, dtype, row = MERGED_FIELDS[name]
-        if code >= 13 and not self.have_pt:
+        if name not in FETCH_FIELDS:
+            raise ValueError(f"merged field {name!r}: one of {sorted(FETCH_FIELDS)}")
+        code, dtype, row = FETCH_FIELDS[name]
+        if 13 <= code <= 15 and not self.have_pt:
             raise ValueError(f"merged field {name!r}: the merge was not given id / it / nc")
         first = int(first)
         count = self.niter - first if count is None else int(count)
@@ -351,13 +366,18 @@ class DeviceMergedRun(dict, Marginals, Errors):
         ctx._check_merge(ctx.lib.dh_merged_resample(ctx.handle, float(u0), int(n), _ptr(idx)))
         return idx
 
-    def gather(self, idx):
-        """Parameter rows of the points `idx`."""
+    def gather(self, idx, field="samples"):
+        """Rows of the points `idx`: their parameters (field='samples') or their unit-cube rows ('samples_u')."""
         ctx = self._live()
+        if field not in ("samples", "samples_u"):
+            raise ValueError(f"gather: field {field!r} (one of 'samples', 'samples_u')")
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         out = np.empty((len(idx), self.ndim))
-        if len(idx):
+        if len(idx) and field == "samples":
             ctx._check_merge(ctx.lib.dh_merged_gather(ctx.handle, len(idx), _ptr(idx), _ptr(out)))
+        elif len(idx):
+            ctx._check_merge(ctx.lib.dh_merged_gather_rows(ctx.handle, MERGED_FIELDS[field][0], len(idx), _ptr(idx),
+                                                           _ptr(out)))
         return out
 
     def _cols_ptr(self, cols):
@@ -552,6 +572,9 @@ class DeviceMergedRun(dict, Marginals, Errors):
             out[k] = a.astype(np.int64) if a.dtype == np.int32 else a
         if self.have_pt:
             out["eff"] = 100. * self.niter / float(out["ncall"].sum())
+        if self.batch_nlive:
+            out["samples_batch"] = self.field("samples_batch").astype(np.int64)
+            out["batch_nlive"], out["batch_bounds"] = list(self.batch_nlive), list(self.batch_bounds)
         return out
 
     def release(self):
@@ -651,14 +674,72 @@ class Context:
         self._merged(self.lib.dh_merge_runs(
             self.handle, self.problem(prob), R, N, nd, max(stride, 1) if stride else 0, _ptr(niter), _ptr(dl),
             _ptr(live_logl), _ptr(du), _ptr(live_u), _ptr(pid), _ptr(pit), _ptr(pnc), _ptr(lit), _ptr(summ)))
-        return DeviceMergedRun(self, summ, nd, have_pt)
+        return DeviceMergedRun(self, summ, nd, have_pt, prob=prob)
+
+    def merged_fold(self, base, prob, niter, dead_logl, live_logl, dead_u, live_u, dead_id=None, dead_it=None,
+                    dead_nc=None, live_it=None, logl_min=-np.inf, logl_max=np.inf):
+        """dh_merged_fold: the strands of one dynamic batch folded into the merged run `base` on the device -- the
+        host's dynamic.merge_strands.  The strand arrays are merge_runs' run arrays (R strands of N final live points);
+        id / it / nc together, and only where `base` has them.  logl_min = -inf (a batch from the prior) is passed as the
+        lowest finite double: every ln L lies above either.  Returns a new DeviceMergedRun; `base` goes stale.  On
+        ValueError (shapes, a strand point at or below logl_min, an over-long plateau) `base` stays valid."""
+        if not isinstance(base, DeviceMergedRun) or base.ctx is not self:
+            raise ValueError("merged_fold: base must be this context's DeviceMergedRun")
+        base._live()
+        nd = prob.ndim
+        niter = np.ascontiguousarray(niter, dtype=np.int64).reshape(-1)
+        R = len(niter)
+        live_logl = _f64(live_logl)
+        if R < 1 or live_logl.ndim != 2 or live_logl.shape[0] != R or live_logl.shape[1] < 1:
+            raise ValueError(f"merged_fold: live_logl of shape {live_logl.shape} for {R} strands")
+        N = live_logl.shape[1]
+        live_u = _f64(live_u)
+        if live_u.shape != (R, N, nd):
+            raise ValueError(f"merged_fold: live_u of shape {live_u.shape}, expected {(R, N, nd)}")
+        if int(niter.min()) < 0:
+            raise ValueError("merged_fold: negative niter")
+        stride = int(niter.max())
+
+        def rows(a, dtype, tail=()):
+            out = np.zeros((R, max(stride, 1)) + tail, dtype=dtype)
+            for r in range(R):
+                row = np.asarray(a[r])
+                if len(row) < niter[r] or row.shape[1:] != tail:
+                    raise ValueError(f"merged_fold: strand {r} has dead rows of shape {row.shape} for niter {niter[r]}")
+                out[r, :niter[r]] = row[:niter[r]]
+            return out
+        info = [dead_id, dead_it, dead_nc, live_it]
+        if any(x is None for x in info) and not all(x is None for x in info):
+            raise ValueError("merged_fold: dead_id, dead_it, dead_nc and live_it come together")
+        have_pt = dead_id is not None
+        if have_pt != base.have_pt:
+            raise ValueError("merged_fold: id / it / nc on one side only")
+        lmin, lmax = float(logl_min), float(logl_max)
+        if np.isnan(lmin) or lmin == np.inf or not lmax > lmin:
+            raise ValueError(f"merged_fold: bounds ({lmin}, {lmax})")
+        dl, du = rows(dead_logl, np.float64), rows(dead_u, np.float64, (nd,))
+        pid = rows(dead_id, np.int32) if have_pt else None
+        pit = rows(dead_it, np.int32) if have_pt else None
+        pnc = rows(dead_nc, np.int32) if have_pt else None
+        lit = np.ascontiguousarray(live_it, dtype=np.int32).reshape(R, N) if have_pt else None
+        b_nlive = list(base.batch_nlive) or [int(base.field("samples_n", 0, 1)[0])]
+        b_bounds = list(base.batch_bounds) or [(-np.inf, np.inf)]
+        summ = np.empty(6)
+        rc = self.lib.dh_merged_fold(
+            self.handle, self.problem(prob), R, N, max(stride, 1) if stride else 0, _ptr(niter), _ptr(dl),
+            _ptr(live_logl), _ptr(du), _ptr(live_u), _ptr(pid), _ptr(pit), _ptr(pnc), _ptr(lit),
+            max(lmin, -sys.float_info.max), lmax, _ptr(summ))
+        if rc == 0:
+            self._merge_serial += 1  # (every failure leaves the base run in place: the handle stays valid)
+        self._check_merge(rc)
+        return DeviceMergedRun(self, summ, nd, have_pt, b_nlive + [N] * R, b_bounds + [(lmin, lmax)] * R, prob=prob)
 
     def merge_kept(self, prob, niter=None):
         """dh_merge_kept: the merged run of the ensemble the last ns_ensemble(keep=True) left on the device."""
         nit = None if niter is None else np.ascontiguousarray(niter, dtype=np.int64)
         summ = np.empty(6)
         self._merged(self.lib.dh_merge_kept(self.handle, self.problem(prob), _ptr(nit), _ptr(summ)))
-        return DeviceMergedRun(self, summ, prob.ndim, True)
+        return DeviceMergedRun(self, summ, prob.ndim, True, prob=prob)
 
     def release_kept(self):
         self._check(self.lib.dh_ns_release(self.handle))

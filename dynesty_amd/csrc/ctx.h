@@ -55,8 +55,8 @@ struct dh_kept {
   std::shared_ptr<void> loop;
 };
 
-// The merged run of the last dh_merge_runs / dh_merge_kept (merge.hip): one allocation, M points in merged order; its
-// arrays are merge_plan.h's MergedArrays, laid out by carve_merged.
+// The merged run of the last dh_merge_runs / dh_merge_kept (merge.hip) or dh_merged_fold (merge_fold.hip): one
+// allocation, M points in merged order; its arrays are merge_plan.h's MergedArrays, laid out by carve_merged.
 struct dh_merged : dh_merge::MergedArrays {
   char* base = nullptr;
   long long M = 0;
@@ -69,6 +69,10 @@ struct dh_merged : dh_merge::MergedArrays {
   int* tie_ep = nullptr;   // [tie_n] merged indices
   int* tie_idx = nullptr;  // [M + 1]
   int tie_n = -1;          // -1: not built
+  // dynamic batches folded in (merge_fold.hip): how many, and the batch index of every point (an allocation of its
+  // own, merge_plan.h's BatchArrays; null on a run that holds no batch: every point is of batch 0)
+  int nbatch = 0;
+  int* batch = nullptr;
 };
 
 struct dh_ctx {

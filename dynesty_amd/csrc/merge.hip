@@ -11,160 +11,15 @@
 //               log-sum-exp pairs), information, var[ln Z], cumulative weights
 //   summaries : sums of w, w^2, w v per chunk and their fixed-order reduction; the covariance on request
 //
-// This unit is the combiner proper with fetch, moments, resample, gather and release; the marginals of the merged run
-// are merge_marginals.hip, its statistical errors merge_errors.hip.  The scans are merge_dev.h's, the sizes and the
-// scratch layouts merge_plan.h's.
+// This unit is the combiner proper with fetch, moments, resample, gather and release; the fold of dynamic batches into
+// the merged run is merge_fold.hip, the marginals of the merged run are merge_marginals.hip, its statistical errors
+// merge_errors.hip.  The scans and the kernels shared with the fold are merge_dev.h's, the sizes and the scratch
+// layouts merge_plan.h's.
+#include <string.h>
+
 #include "merge_dev.h"
 
 namespace {
-
-// ---- sequences ------------------------------------------------------------------------------------------------------
-
-// final live points of run blockIdx.y: rank of slot s = #{t : l_t < l_s or (l_t == l_s and t < s)} (a stable ascending
-// sort by counting: N^2 comparisons per run against LDS tiles, no data-dependent addressing)
-__global__ void __launch_bounds__(kT) mg_live_rank(int N, const double* __restrict__ live_logl,
-                                                   const long long* __restrict__ off, const long long* __restrict__ nit,
-                                                   double* __restrict__ seq_l, int* __restrict__ seq_run,
-                                                   int* __restrict__ live_slot) {
-  __shared__ double tile[kLiveTile];
-  const int r = blockIdx.y, s = blockIdx.x * kT + threadIdx.x;
-  const double* keys = live_logl + (size_t)r * N;
-  const bool mine = s < N;
-  const double x = keys[mine ? s : 0];
-  int rank = 0;
-  for (int t0 = 0; t0 < N; t0 += kLiveTile) {
-    const int nt = N - t0 < kLiveTile ? N - t0 : kLiveTile;
-    __syncthreads();
-    for (int t = threadIdx.x; t < nt; t += kT) tile[t] = keys[t0 + t];
-    __syncthreads();
-    for (int t = 0; t < nt; ++t) {
-      const double y = tile[t];
-      rank += (y < x || (y == x && t0 + t < s)) ? 1 : 0;
-    }
-  }
-  if (!mine) return;
-  const long long g = off[r] + nit[r] + rank;  // rank < N always (NaN keys compare false: ranks may collide, never leave)
-  seq_l[g] = x;
-  seq_run[g] = r;
-  live_slot[(size_t)r * N + rank] = s;
-}
-
-__global__ void __launch_bounds__(kT) mg_dead_copy(long long stride, const double* __restrict__ dead_logl,
-                                                   const long long* __restrict__ off, const long long* __restrict__ nit,
-                                                   double* __restrict__ seq_l, int* __restrict__ seq_run) {
-  const int r = blockIdx.y;
-  const long long i = (long long)blockIdx.x * kT + threadIdx.x;
-  if (i >= nit[r]) return;
-  seq_l[off[r] + i] = dead_logl[(size_t)r * stride + i];
-  seq_run[off[r] + i] = r;
-}
-
-// flags[0]: a NaN value; flags[1]: a run's sequence decreases somewhere; org = identity
-__global__ void __launch_bounds__(kT) mg_check(long long M, const double* __restrict__ seq_l, const int* __restrict__ seq_run,
-                                               const long long* __restrict__ off, int* __restrict__ org, int* flags) {
-  const long long g = (long long)blockIdx.x * kT + threadIdx.x;
-  if (g >= M) return;
-  const double x = seq_l[g];
-  org[g] = (int)g;
-  if (x != x) flags[0] = 1;
-  if (g > off[seq_run[g]] && x < seq_l[g - 1]) flags[1] = 1;
-}
-
-// ---- order ----------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ long long lower_bound_dev(const double* a, long long n, double x) {  // #{a_j < x}
-  long long lo = 0, hi = n;
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-__device__ __forceinline__ long long upper_bound_dev(const double* a, long long n, double x) {  // #{a_j <= x}
-  long long lo = 0, hi = n;
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    if (a[mid] <= x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// One round: the lists of runs [a, a + wd) and [a + wd, a + 2 wd) (element ranges off[...]) merge into one, the left
-// list first among equal values.  Neighbouring threads hold neighbouring values, so their searches share their probes.
-__global__ void __launch_bounds__(kT) mg_merge_round(long long M, int R, int wd, const long long* __restrict__ off,
-                                                     const double* __restrict__ key_in, const int* __restrict__ org_in,
-                                                     double* __restrict__ key_out, int* __restrict__ org_out) {
-  const long long p = (long long)blockIdx.x * kT + threadIdx.x;
-  if (p >= M) return;
-  int lo_r = 0, hi_r = R;  // the run whose element range holds p: off[lo_r] <= p < off[lo_r + 1]
-  while (hi_r - lo_r > 1) {
-    const int mid = (lo_r + hi_r) >> 1;
-    if (off[mid] <= p) lo_r = mid; else hi_r = mid;
-  }
-  const int a = lo_r / (2 * wd) * (2 * wd);
-  const int m_r = a + wd < R ? a + wd : R, e_r = a + 2 * wd < R ? a + 2 * wd : R;
-  const long long lo = off[a], mid = off[m_r], hi = off[e_r];
-  const double x = key_in[p];
-  long long pos;
-  if (p < mid)
-    pos = p + lower_bound_dev(key_in + mid, hi - mid, x);
-  else
-    pos = lo + (p - mid) + upper_bound_dev(key_in + lo, mid - lo, x);
-  key_out[pos] = x;  // lo <= pos < hi for any input
-  org_out[pos] = org_in[p];
-}
-
-// ---- scatter --------------------------------------------------------------------------------------------------------
-
-struct MgSrc {
-  const double *dead_u, *live_u;
-  const int *dead_id, *dead_it, *dead_nc, *live_it;  // null together
-  long long stride;
-  int N;
-};
-
-__global__ void __launch_bounds__(kT) mg_scatter(long long M, MgSrc s, const double* __restrict__ key, const int* __restrict__ org,
-                                                 const int* __restrict__ seq_run, const long long* __restrict__ off,
-                                                 const long long* __restrict__ nit, const int* __restrict__ live_slot,
-                                                 double* __restrict__ logl, int* __restrict__ run, int* __restrict__ seq,
-                                                 int* __restrict__ id, int* __restrict__ it, int* __restrict__ nc,
-                                                 int* __restrict__ fin, long long* __restrict__ src_row) {
-  const long long k = (long long)blockIdx.x * kT + threadIdx.x;
-  if (k >= M) return;
-  long long g = org[k];
-  if (g < 0 || g >= M) g = 0;
-  const int r = seq_run[g];
-  const long long i = g - off[r], nd = nit[r];
-  const bool live = i >= nd;
-  long long li = i - nd;
-  if (li < 0 || li >= s.N) li = 0;  // (only where NaN keys left a position unwritten: the call fails, the reads stay inside)
-  int slot = live ? live_slot[(size_t)r * s.N + li] : 0;
-  if (slot < 0 || slot >= s.N) slot = 0;
-  const long long drow = (long long)r * s.stride + (live ? 0 : i), lrow = (long long)r * s.N + slot;
-  logl[k] = key[k];
-  run[k] = r;
-  seq[k] = (int)i;
-  fin[k] = live ? 1 : 0;
-  src_row[k] = live ? -1 - lrow : drow;
-  if (s.dead_id) {
-    // (both loads are issued, the select follows: no load under a condition)
-    const int d_id = s.dead_id[drow], d_it = s.dead_it[drow], d_nc = s.dead_nc[drow], l_it = s.live_it[lrow];
-    id[k] = live ? slot : d_id;
-    it[k] = live ? l_it : d_it;
-    nc[k] = live ? 1 : d_nc;
-  }
-}
-
-__global__ void __launch_bounds__(kT) mg_scatter_rows(size_t total, int D, MgSrc s, const long long* __restrict__ src_row,
-                                                      double* __restrict__ u) {
-  const size_t e = (size_t)blockIdx.x * kT + threadIdx.x;
-  if (e >= total) return;
-  const size_t k = e / (size_t)D;
-  const int d = (int)(e - k * (size_t)D);
-  const long long row = src_row[k];
-  const double* from = row >= 0 ? s.dead_u + (size_t)row * D : s.live_u + (size_t)(-1 - row) * D;
-  u[e] = from[d];
-}
 
 // ---- scans (the operators and the three launches: merge_dev.h) ------------------------------------------------------
 
@@ -190,104 +45,9 @@ struct FVol {
   __device__ double term(long long k) const { return step[k]; }
   __device__ void put(long long k, double incl, double) const { logvol[k] = -incl; }
 };
-// ln w by the trapezoid rule and the cumulative ln Z (nested._integrate_full); d ln X of point k is its own step, not
-// the difference of two cumulative values
-struct FLogz {
-  typedef Lse Op;
-  const double *logl, *logvol, *step;
-  double *logwt, *logdvol, *logz;
-  __device__ LsePair term(long long k) const {
-    const double v0 = k > 0 ? logvol[k - 1] : 0.0, l0 = k > 0 ? logl[k - 1] : -1.e300;
-    // 1 - exp(-step) through expm1: exp(-step) is next to 1, and its rounding would be n ulps of the difference
-    const double ldv = v0 + log(-expm1(-step[k])) + (-0.6931471805599453);
-    const double lw = logaddexp_np(logl[k], l0) + ldv;
-    logdvol[k] = ldv;
-    logwt[k] = lw;
-    return LsePair{lw, 1.0};
-  }
-  __device__ void put(long long k, LsePair incl, LsePair) const { logz[k] = incl.m + log(incl.s); }
-};
-// information: cumsum(w0 l0 + w1 l1) - ln Z exp(ln Z_k - ln Z), everything normalised by the FINAL Z
-struct FInfo {
-  typedef SumD Op;
-  const double *logl, *logdvol, *logz;
-  double* h;
-  long long M;
-  __device__ double term(long long k) const {
-    const double lz = logz[M - 1], l1 = logl[k], l0 = k > 0 ? logl[k - 1] : -1.e300, ldv = logdvol[k];
-    const double w0 = exp(l0 - lz + ldv), w1 = exp(l1 - lz + ldv);
-    return (w0 > 0 ? w0 * l0 : 0.0) + (w1 > 0 ? w1 * l1 : 0.0);
-  }
-  __device__ void put(long long k, double incl, double) const {
-    const double lz = logz[M - 1];
-    h[k] = incl - lz * exp(logz[k] - lz);
-  }
-};
-// var[ln Z] = |cumsum dH d ln X|; stored as its square root
-struct FVar {
-  typedef SumD Op;
-  const double *h, *step;
-  double* logzerr;
-  __device__ double term(long long k) const { return (h[k] - (k > 0 ? h[k - 1] : 0.0)) * step[k]; }
-  __device__ void put(long long k, double incl, double) const { logzerr[k] = sqrt(fabs(incl)); }
-};
-// cumulative sum of f(k); mode 0: exp(logwt - ln Z) (its inclusive scan lands in cw), mode 1: the normalised weights
-struct FCum {
-  typedef SumD Op;
-  const double *logwt, *logz;
-  double *w, *cw;
-  long long M;
-  int mode;
-  __device__ double term(long long k) const { return mode == 0 ? exp(logwt[k] - logz[M - 1]) : w[k]; }
-  __device__ void put(long long k, double incl, double) const { cw[k] = incl; }
-};
 
-// w = exp(logwt - ln Z) / sum (the sum is the last cumulative value of the first pass)
-__global__ void __launch_bounds__(kT) mg_weights(long long M, const double* __restrict__ logwt, const double* __restrict__ logz,
-                                                 const double* __restrict__ cw, double* __restrict__ w) {
-  const long long k = (long long)blockIdx.x * kT + threadIdx.x;
-  if (k >= M) return;
-  w[k] = exp(logwt[k] - logz[M - 1]) / cw[M - 1];
-}
-// C /= C_M, so that C_M is 1 exactly (utils.resample_equal); `last` is a copy taken before this launch
-__global__ void __launch_bounds__(kT) mg_cum_norm(long long M, double* __restrict__ cw, const double* __restrict__ last) {
-  const long long k = (long long)blockIdx.x * kT + threadIdx.x;
-  if (k >= M) return;
-  cw[k] = cw[k] / last[0];
-}
+// ---- summaries (the first moments and the summary: merge_dev.h) ------------------------------------------------------
 
-// ---- summaries ------------------------------------------------------------------------------------------------------
-
-// column c < D: sum w v_c; c = D: sum w; c = D + 1: sum w^2 -- over the points of chunk blockIdx.x, in order
-__global__ void __launch_bounds__(kT) mg_mom1(long long M, int D, long long chunk, const double* __restrict__ w,
-                                              const double* __restrict__ v, double* __restrict__ part) {
-  const int c = blockIdx.y * kT + threadIdx.x;
-  if (c >= D + 2) return;
-  const long long k0 = (long long)blockIdx.x * chunk, k1 = k0 + chunk < M ? k0 + chunk : M;
-  double acc = 0.0;
-  for (long long k = k0; k < k1; ++k) {
-    const double wk = w[k];
-    const double x = c < D ? v[(size_t)k * D + c] : c == D ? 1.0 : wk;
-    acc = fma(wk, x, acc);
-  }
-  part[(size_t)blockIdx.x * (D + 2) + c] = acc;
-}
-// mom = [sum w, sum w^2, ESS, mean_0 ..]: the chunks' sums in chunk order; mean = sum w v / sum w (np.average)
-__global__ void __launch_bounds__(kT) mg_mom1_fin(int D, int nchunk, const double* __restrict__ part, double* __restrict__ mom) {
-  const int c = blockIdx.x * kT + threadIdx.x;
-  if (c >= D + 2) return;
-  double acc = 0.0, ws = 0.0;
-  for (int b = 0; b < nchunk; ++b) {
-    acc += part[(size_t)b * (D + 2) + c];
-    ws += part[(size_t)b * (D + 2) + D];
-  }
-  if (c < D) mom[3 + c] = acc / ws;
-  if (c == D) mom[0] = acc;
-  if (c == D + 1) {
-    mom[1] = acc;
-    mom[2] = 1.0 / acc;
-  }
-}
 // pair p = i D + j: sum w (v_i - mean_i) (v_j - mean_j) over the chunk's points
 __global__ void __launch_bounds__(kT) mg_mom2(long long M, int D, long long chunk, const double* __restrict__ w,
                                               const double* __restrict__ v, const double* __restrict__ mom,
@@ -313,31 +73,6 @@ __global__ void __launch_bounds__(kT) mg_mom2_fin(int D, int nchunk, const doubl
   for (int b = 0; b < nchunk; ++b) acc += part[(size_t)b * D * D + p];
   const double ws = mom[0], w2 = mom[1];
   cov[p] = ws / (ws * ws - w2) * acc;
-}
-
-// integers: order does not matter
-__global__ void __launch_bounds__(kT) mg_sum_nc(long long M, const int* __restrict__ nc, unsigned long long* out) {
-  __shared__ unsigned long long red[kT];
-  unsigned long long acc = 0;
-  for (long long k = (long long)blockIdx.x * kT + threadIdx.x; k < M; k += (long long)gridDim.x * kT) acc += (unsigned long long)nc[k];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int d = kT / 2; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicAdd(out, red[0]);
-}
-
-__global__ void mg_summary(long long M, const double* logz, const double* logzerr, const double* h, const double* mom,
-                           const unsigned long long* ncall, double* out) {
-  if (threadIdx.x || blockIdx.x) return;
-  out[0] = (double)M;
-  out[1] = logz[M - 1];
-  out[2] = logzerr[M - 1];
-  out[3] = h[M - 1];
-  out[4] = mom[2];
-  out[5] = (double)ncall[0];
 }
 
 // ---- resampling -----------------------------------------------------------------------------------------------------
@@ -388,8 +123,6 @@ int merge_core(dh_ctx* ctx, int problem, int R, int N, int D, long long stride, 
   merged_free(ctx);  // the next merge replaces the merged run
   dh_merged m;
   MergeScratch s;
-  long long chunk1;
-  const int nchunk1 = moment_chunks(M, (size_t)D + 2, &chunk1);
   auto lay_m = [&](Carver& c) { carve_merged(c, m, (size_t)M, (size_t)D, pt); };
   auto lay_s = [&](Carver& c) { carve_scratch(c, s, (size_t)M, (size_t)R, (size_t)N, (size_t)D); };
   char* mbase = device_carve(lay_m);
@@ -455,21 +188,8 @@ int merge_core(dh_ctx* ctx, int problem, int R, int N, int D, long long stride, 
   if (rc) return done(rc);
   // scans
   if (!run_scan(ctx, FCount{m.fin, m.n, s.step, R * N}, M, s.part) || !run_scan(ctx, FVol{s.step, m.logvol}, M, s.part) ||
-      !run_scan(ctx, FLogz{m.logl, m.logvol, s.step, m.logwt, s.logdvol, m.logz}, M, s.part) ||
-      !run_scan(ctx, FInfo{m.logl, s.logdvol, m.logz, m.h, M}, M, s.part) ||
-      !run_scan(ctx, FVar{m.h, s.step, m.logzerr}, M, s.part) ||
-      !run_scan(ctx, FCum{m.logwt, m.logz, m.w, m.cw, M, 0}, M, s.part))
+      !run_integrals(ctx, m, M, D, pt, s.step, IntegralScratch{s.logdvol, s.mom_part, s.last, s.summ, s.ncall, s.part}))
     return done(DH_ERR_HIP);
-  hipLaunchKernelGGL(mg_weights, dim3(gM), dim3(kT), 0, st, M, m.logwt, m.logz, m.cw, m.w);
-  if (!run_scan(ctx, FCum{m.logwt, m.logz, m.w, m.cw, M, 1}, M, s.part) ||
-      !hip_ok(ctx, hipMemcpyAsync(s.last, m.cw + (M - 1), 8, hipMemcpyDeviceToDevice, st), "D2D"))
-    return done(DH_ERR_HIP);
-  hipLaunchKernelGGL(mg_cum_norm, dim3(gM), dim3(kT), 0, st, M, m.cw, s.last);
-  // summaries
-  hipLaunchKernelGGL(mg_mom1, dim3(nchunk1, blocks_for((size_t)D + 2, kT)), dim3(kT), 0, st, M, D, chunk1, m.w, m.v, s.mom_part);
-  hipLaunchKernelGGL(mg_mom1_fin, dim3(blocks_for((size_t)D + 2, kT)), dim3(kT), 0, st, D, nchunk1, s.mom_part, m.mom);
-  if (pt) hipLaunchKernelGGL(mg_sum_nc, dim3(gM < 1024 ? gM : 1024), dim3(kT), 0, st, M, m.nc, s.ncall);
-  hipLaunchKernelGGL(mg_summary, dim3(1), dim3(64), 0, st, M, m.logz, m.logzerr, m.h, m.mom, s.ncall, s.summ);
   double summ[6];
   int flags[4];
   if (!hip_ok(ctx, hipGetLastError(), "merge launch") ||
@@ -497,6 +217,7 @@ void dh::merged_free(dh_ctx* ctx) {
   if (ctx->merged.base) (void)hipFree(ctx->merged.base);
   if (ctx->merged.idx) (void)hipFree(ctx->merged.idx);
   if (ctx->merged.tie_idx) (void)hipFree(ctx->merged.tie_idx);  // (tie_ep lies in the same allocation)
+  if (ctx->merged.batch) (void)hipFree(ctx->merged.batch);
   ctx->merged = dh_merged();
 }
 
@@ -574,6 +295,14 @@ int dh_merged_fetch(dh_ctx* ctx, int field, int64_t first, int64_t count, void* 
     case DH_MERGED_ID: src = m.id; width = 4; break;
     case DH_MERGED_IT: src = m.it; width = 4; break;
     case DH_MERGED_NCALL: src = m.nc; width = 4; break;
+    case DH_MERGED_BATCH:
+      if (!m.batch) {  // a run that holds no batch: every point is of batch 0
+        if (count) memset(out, 0, (size_t)count * 4);
+        return DH_OK;
+      }
+      src = m.batch;
+      width = 4;
+      break;
     default: return fail(ctx, DH_ERR_ARG, "merged_fetch: field %d", field);
   }
   if (!src) return fail(ctx, DH_ERR_ARG, "merged_fetch: field %d was not given to the merge", field);
@@ -656,6 +385,28 @@ int dh_merged_gather(dh_ctx* ctx, int64_t n, const int64_t* idx_or_null, double*
   }
   hipLaunchKernelGGL(mg_gather, dim3(blocks_for((size_t)n * D, kT)), dim3(kT), 0, ctx->stream, (size_t)n * D, m.ndim, m.M, m.v, d_idx, b.out);
   if (!hip_ok(ctx, hipGetLastError(), "gather launch") || !down(ctx, out_v, (const double*)b.out, (size_t)n * D)) return DH_ERR_HIP;
+  return dh_sync(ctx);
+}
+
+int dh_merged_gather_rows(dh_ctx* ctx, int field, int64_t n, const int64_t* idx, double* out) {
+  DH_CHECK_CTX(ctx);
+  if (need_merged(ctx)) return DH_ERR_ARG;
+  const dh_merged& m = ctx->merged;
+  if (field != DH_MERGED_SAMPLES_U && field != DH_MERGED_SAMPLES)
+    return fail(ctx, DH_ERR_ARG, "merged_gather_rows: field %d (SAMPLES_U or SAMPLES)", field);
+  if (n < 1 || !idx || !out || (unsigned long long)n * (unsigned long long)m.ndim >= (1ull << 32))
+    return fail(ctx, DH_ERR_ARG, "merged_gather_rows: n %lld with idx and out (at most 2^32 elements per call)", (long long)n);
+  for (int64_t i = 0; i < n; ++i)
+    if (idx[i] < 0 || idx[i] >= m.M)
+      return fail(ctx, DH_ERR_ARG, "merged_gather_rows: index %lld at %lld outside [0, %lld)", (long long)idx[i], (long long)i, m.M);
+  const size_t D = (size_t)m.ndim;
+  GatherBuf b;
+  const int rc = arena_carve(ctx, [&](Carver& c) { carve_gather_rows(c, b, (size_t)n, D); });
+  if (rc) return rc;
+  if (!arena_fill(ctx, b.idx, (const long long*)idx, (size_t)n)) return DH_ERR_NOMEM;
+  hipLaunchKernelGGL(mg_gather, dim3(blocks_for((size_t)n * D, kT)), dim3(kT), 0, ctx->stream, (size_t)n * D, m.ndim, m.M,
+                     field == DH_MERGED_SAMPLES_U ? m.u : m.v, b.idx, b.out);
+  if (!hip_ok(ctx, hipGetLastError(), "gather launch") || !down(ctx, out, (const double*)b.out, (size_t)n * D)) return DH_ERR_HIP;
   return dh_sync(ctx);
 }
 

@@ -733,6 +733,8 @@ int boot_need(dh_ctx* ctx, const char* what, int jitter, const int32_t* mult, in
   if (need_merged(ctx)) return DH_ERR_ARG;
   const dh_merged& m = ctx->merged;
   if (!m.have_pt) return fail(ctx, DH_ERR_ARG, "%s: the merge was not given id / it / nc (the strands' slots)", what);
+  if (m.nbatch > 0)  // (ensemble.MergedRun's refusal: strands are read off a live count that only falls)
+    return fail(ctx, DH_ERR_ARG, "%s: the strand bootstrap is not defined for a run that carries dynamic batches", what);
   if (jitter != 0 && jitter != 1) return fail(ctx, DH_ERR_ARG, "%s: jitter %d (0 or 1)", what, jitter);
   if (mult) {
     if (nboot != 1) return fail(ctx, DH_ERR_ARG, "%s: given multiplicities are one bootstrap (nboot %d)", what, nboot);

@@ -351,6 +351,73 @@ struct TieScratch {
 };
 inline void carve_tie_scratch(Carver& c, TieScratch& t, size_t M) { c(t.part, "part", (blocks_for(M, kChunk) + 1) * kScanElem); }
 
+// ---- the fold of dynamic batches (merge_fold.hip): a base run of M points, W new points in R strands of N live points --
+
+// static LDS of the fold's kernels: the rank sort's tile of keys, a scan's two rows of aggregates
+inline size_t fold_rank_lds() { return (size_t)kLiveTile * 8; }
+inline size_t fold_scan_lds() { return (size_t)2 * kT * kScanElem; }
+
+// the batch index of every point of a run that holds batches: an allocation of its own beside the merged block
+struct BatchArrays {
+  int* batch = nullptr;
+};
+inline void carve_batch(Carver& c, BatchArrays& b, size_t T) { c(b.batch, "batch", T); }
+
+// the fold's scratch, freed when the fold returns (T = M + W points)
+struct FoldScratch {
+  long long *off, *nit, *n_row;
+  double *seq_l, *key_b, *ustage, *vstage, *eval_l, *step, *vterm, *logdvol, *mom_part, *last, *summ;
+  int *seq_run, *org_a, *org_b, *live_slot, *n_run, *n_seq, *n_fin, *n_id, *n_it, *n_nc;  // the W new points, in their order
+  int *src, *finnew, *gstart, *shift, *idmax, *flags;
+  u64* ncall;
+  char* part;
+};
+inline void carve_fold_scratch(Carver& c, FoldScratch& s, size_t M, size_t W, size_t R, size_t N, size_t D, bool pt) {
+  const size_t T = M + W;
+  long long chunk;
+  const size_t nchunk = (size_t)moment_chunks((long long)T, D + 2, &chunk);
+  c(s.off, "off", R + 1);
+  c(s.nit, "nit", R);
+  c(s.n_row, "n_row", W);
+  c(s.seq_l, "seq_l", W);
+  c(s.key_b, "key_b", W);
+  c(s.ustage, "ustage", W * D);
+  c(s.vstage, "vstage", W * D);
+  c(s.eval_l, "eval_l", W);
+  c(s.step, "step", T);
+  c(s.vterm, "vterm", T);
+  c(s.logdvol, "logdvol", T);
+  c(s.mom_part, "mom_part", nchunk * (D + 2));
+  c(s.last, "last", 1);
+  c(s.summ, "summ", 8);
+  c(s.seq_run, "seq_run", W);
+  c(s.org_a, "org_a", W);
+  c(s.org_b, "org_b", W);
+  c(s.live_slot, "live_slot", R * N);
+  c(s.n_run, "n_run", W);
+  c(s.n_seq, "n_seq", W);
+  c(s.n_fin, "n_fin", W);
+  c(s.n_id, "n_id", W, pt);
+  c(s.n_it, "n_it", W, pt);
+  c(s.n_nc, "n_nc", W, pt);
+  c(s.src, "src", T);
+  c(s.finnew, "finnew", T);
+  c(s.gstart, "gstart", T);
+  c(s.shift, "shift", R);
+  c(s.idmax, "idmax", 1);
+  c(s.flags, "flags", 4);
+  c(s.ncall, "ncall", 1);
+  c(s.part, "part", (blocks_for(T, kChunk) + 1) * kScanElem);
+}
+
+// the strands of dh_merged_fold, staged from the host: dh_merge_runs' shapes with strands for runs
+inline void carve_fold_stage(Carver& c, MergeStage& s, size_t R, size_t N, size_t D, size_t S, bool pt) {
+  carve_stage(c, s, R, N, D, S, pt);
+}
+
+// dh_merged_gather_rows: n rows of one row field out, their indices in
+inline void carve_gather_rows(Carver& c, GatherBuf& b, size_t n, size_t D) { carve_gather(c, b, n, D, true); }
+
 // the weight function: zweight and weight of every point, the maximum's bits, the bounds
 struct WeightBuf {
   char* part;

@@ -8,9 +8,14 @@ into the saved run.  Here
   batch_seed   restates the choice of the start points (NumPy, host; the same calls on the same bits give the
                reference's indices),
   Context.ns_batch (dh_ns_batch, csrc/ns.hip) samples the live set and runs the strands on the device,
-  merge_batch  restates combine_runs (NumPy, host),
-  run_dynamic  is the loop around them: weight_function -> batch_seed x strands -> ns_batch -> merge_batch ->
-               stopping_function.
+  merge_batch  restates combine_runs (NumPy, host), one strand at a time,
+  merge_strands  folds all strands of a batch in one pass (NumPy, host): the same result as merge_batch strand after
+               strand, with one integration of the whole run; the host mirror of the device's fold (dh_merged_fold,
+               csrc/merge_fold.hip),
+  fold_batch   folds an ns_batch / ns_ensemble result into a MergedRun (merge_strands) or a DeviceMergedRun (the
+               device's fold),
+  run_dynamic  is the loop around them: weight_function -> batch_seed x strands -> ns_batch -> merge_batch (merge='host')
+               or fold_batch on the device (merge='device') -> stopping_function.
 
 Where this departs from the reference: a batch needs nlive_new seeds of positive weight (the reference goes on with
 fewer live points; batch_seed raises ValueError); the device's departures (a)-(d) are listed in include/dynhip.h.
@@ -22,7 +27,7 @@ import numpy as np
 
 from .ensemble import MergedRun, run_ensemble_merged
 
-__all__ = ["batch_seed", "merge_batch", "strand_of", "run_dynamic"]
+__all__ = ["batch_seed", "merge_batch", "merge_strands", "fold_batch", "single_run", "strand_of", "run_dynamic"]
 
 
 def _base_columns(base):
@@ -41,8 +46,11 @@ def _base_row(base, i):
     return one["logvol"], one["logz"], one["information"], one["logzerr"] ** 2, one["logl"]
 
 
-def batch_seed(base, logl_bounds, nlive_new, rstate):
+def batch_seed(base, logl_bounds, nlive_new, rstate, columns=None):
     """The start points of one strand of a batch (dynamicsampler.py:394-416, 457-533, 606-610).
+
+    columns: (logl, logvol) of the saved run where the caller holds them already -- the strands of one batch share one
+    download of a DeviceMergedRun's two columns; default: read from `base`.
 
     base: a MergedRun or a DeviceMergedRun (the saved run); logl_bounds: (logl_min, logl_max) or None for the
     reference's default, (-inf, ln L at the last index with logvol < logvol[-1] + ln nlive_new); rstate: a
@@ -58,7 +66,7 @@ def batch_seed(base, logl_bounds, nlive_new, rstate):
     Raises RuntimeError when no saved point lies above logl_min (the reference's type), ValueError when fewer than
     nlive_new points of positive weight are available (the reference goes on with fewer live points; this does not)."""
     nlive_new = int(nlive_new)
-    saved_logl, saved_logvol = _base_columns(base)
+    saved_logl, saved_logvol = _base_columns(base) if columns is None else columns
     if logl_bounds is None:
         pos = np.nonzero(saved_logvol < (saved_logvol[-1] + np.log(nlive_new)))[0]
         pos = pos[-1] if len(pos) > 0 else len(saved_logl) - 1
@@ -217,9 +225,120 @@ def merge_batch(base, strand, logl_min, logl_max):
     return out
 
 
+def single_run(m):
+    """A merge of static runs as ONE run, in place: a point's id names its strand in the whole run (run * nlive + slot),
+    its run is 0.  nlive is read off the run itself: the first point's live count is runs * nlive.  A run that is one
+    already (a single static run, a run that holds batches) comes back as it is."""
+    if m.get("samples_batch") is not None or m.get("samples_run") is None:
+        return m
+    run = np.asarray(m["samples_run"], dtype=np.int64)
+    nruns = int(run.max()) + 1 if len(run) else 1
+    if m.get("samples_id") is not None:
+        nlive = int(np.asarray(m["samples_n"])[0]) // nruns
+        m["samples_id"] = run * nlive + np.asarray(m["samples_id"], dtype=np.int64)
+    m["samples_run"] = np.zeros(len(run), dtype=np.int64)
+    return m
+
+
+def merge_strands(base, strands, logl_min, logl_max):
+    """All strands of one batch folded into the saved run in one pass: the result of merge_batch applied strand after
+    strand, in strand order, with the same bounds -- one sort and one integration of the whole run instead of one per
+    strand.  base: a MergedRun as merge_batch takes it; strands: a list of strand_of dicts (n = nlive_new for the dead
+    points and nlive_new, ..., 1 for the final ones).
+
+      order  the stable order of (base, strand 0, .., strand R-1): on equal ln L the base point first, then the strands
+             by index, then a strand's own order
+      n      n_base at the base's next point (0 past its end) + where ln L > logl_min (strictly) the strands' heads:
+             the sum of the strands' first n less one for each of their FINAL points before the position
+      id     strand s shifted by the largest id so far + 1; batch = batches before + 1 + s
+      ln X   _batch_logvol's plateau rule over the whole run; the integrals by _integrate_full
+
+    Raises ValueError where merge_batch does (an empty strand; a plateau longer than the live count where it starts),
+    and for a strand point at or below logl_min, which merge_batch would count without its own strand."""
+    from .nested import _integrate_full
+    if len(strands) < 1:
+        raise ValueError("No new samples are currently saved.")
+    sl = np.asarray(base["logl"], dtype=np.float64)
+    sn = np.asarray(base["samples_n"], dtype=np.int64)
+    ns_ = len(sl)
+    nls = [np.asarray(s["logl"], dtype=np.float64) for s in strands]
+    nns = [np.asarray(s["n"], dtype=np.int64) for s in strands]
+    if any(len(x) == 0 for x in nls):
+        raise ValueError("No new samples are currently saved.")
+    nl = np.concatenate(nls)
+    if not (nl > logl_min).all():
+        raise ValueError(f"merge_strands: a strand point lies at or below logl_min = {logl_min}")
+    nw = len(nl)
+    # a strand's final points: where its live count falls (the last nn[0] points, as strand_of writes them)
+    fin_new = np.concatenate([np.concatenate([x[:-1] > x[1:], [True]]) for x in nns])
+    heads = int(sum(int(x[0]) for x in nns))
+    order = np.argsort(np.concatenate([sl, nl]), kind="stable")
+    from_new = order >= ns_
+    idx_saved = np.arange(ns_ + nw) - (np.cumsum(from_new) - from_new)   # base points before each position
+    fin_sorted = np.concatenate([np.zeros(ns_, dtype=bool), fin_new])[order]
+    cfin = np.cumsum(fin_sorted) - fin_sorted                            # new final points before it
+    logl = np.concatenate([sl, nl])[order]
+    n = np.concatenate([sn, [0]])[idx_saved] + np.where(logl > logl_min, heads - cfin, 0)
+    logvol = _batch_logvol(logl, n)
+    logwt, logz, h, logzvar = _integrate_full(logl, logvol)
+    b_nlive, b_bounds = base.get("batch_nlive"), base.get("batch_bounds")
+    b_nlive = [int(sn.max())] if b_nlive is None or len(b_nlive) == 0 else [int(x) for x in b_nlive]
+    b_bounds = ([(-np.inf, np.inf)] if b_bounds is None or len(b_bounds) == 0
+                else [(float(lo), float(hi)) for lo, hi in b_bounds])
+    nbatch = len(b_nlive) - 1
+    sbatch = base.get("samples_batch")
+    sbatch = np.zeros(ns_, dtype=np.int64) if sbatch is None else np.asarray(sbatch, dtype=np.int64)
+    sid = np.asarray(base["samples_id"], dtype=np.int64)
+    ids, top = [sid], int(sid.max())
+    for s in strands:  # (the running maximum: the largest id so far, as one merge_batch after the other sees it)
+        ids.append(np.asarray(s["id"], dtype=np.int64) + top + 1)
+        top = int(ids[-1].max())
+    out = MergedRun(niter=len(logl), logl=logl, logvol=logvol, logwt=logwt, logz=logz, logzerr=np.sqrt(logzvar),
+                    information=h, samples_n=n.astype(np.int64), samples_id=np.concatenate(ids)[order],
+                    samples_batch=np.concatenate([sbatch] + [np.full(len(x), nbatch + 1 + i, dtype=np.int64)
+                                                             for i, x in enumerate(nls)])[order],
+                    batch_nlive=b_nlive + [int(x.max()) for x in nns],
+                    batch_bounds=b_bounds + [(float(logl_min), float(logl_max))] * len(strands))
+
+    def both(key, skey, dtype=np.int64):
+        b = base.get(key)
+        if b is None or any(skey not in s for s in strands):
+            return
+        out[key] = np.concatenate([np.asarray(b, dtype=dtype)] + [np.asarray(s[skey], dtype=dtype) for s in strands])[order]
+    both("samples_it", "it")
+    both("ncall", "nc")
+    both("samples_u", "u", np.float64)
+    both("samples", "v", np.float64)
+    if base.get("samples_run") is not None:
+        out["samples_run"] = np.concatenate([np.asarray(base["samples_run"], dtype=np.int64),
+                                             np.zeros(nw, dtype=np.int64)])[order]
+    out["samples_seq"] = np.concatenate([np.asarray(base["samples_seq"], dtype=np.int64) if base.get("samples_seq")
+                                         is not None else np.arange(ns_)] + [np.arange(len(x)) for x in nls])[order]
+    if isinstance(out.get("ncall"), np.ndarray):
+        out["eff"] = 100. * len(logl) / float(out["ncall"].sum())
+    return out
+
+
+def fold_batch(base, out, nlive_new, logl_min, logl_max, prior_transform=None):
+    """One batch folded into the saved run: `out` is a Context.ns_batch / ns_ensemble result (want_samples=True), all of
+    whose strands join.  A DeviceMergedRun is folded where it lives (Context.merged_fold, dh_merged_fold; the strands'
+    arrays are uploaded, the run stays on the device; the old handle goes stale; the new points' parameters are the
+    problem's the run was merged with); a MergedRun by merge_strands, with prior_transform for the new points'
+    parameters.  Returns the new run, of the base's type."""
+    if hasattr(base, "field") and not isinstance(base, MergedRun):
+        if int(np.shape(out["live_logl"])[1]) != int(nlive_new):
+            raise ValueError(f"fold_batch: strands of {np.shape(out['live_logl'])[1]} live points, nlive_new {nlive_new}")
+        pt = dict(dead_id=out["dead_id"], dead_it=out["dead_it"], dead_nc=out["dead_nc"],
+                  live_it=out["live_it"]) if base.have_pt else {}
+        return base._live().merged_fold(base, base.prob, out["niter"], out["dead_logl"], out["live_logl"], out["dead_u"],
+                                         out["live_u"], logl_min=logl_min, logl_max=logl_max, **pt)
+    strands = [strand_of(out, r, nlive_new, prior_transform=prior_transform) for r in range(len(out["niter"]))]
+    return merge_strands(base, strands, logl_min, logl_max)
+
+
 def run_dynamic(prob, runs, nlive_init, strands, nlive_batch, maxbatch, pfrac=0.8, entropy=(21,), queue_size=None,
                 maxfrac=0.8, pad=1, dlogz_init=0.01, dlogz_batch=0.01, max_iter=None, rstate=None, stop_kwargs=None,
-                **kw):
+                merge='host', **kw):
     """Dynamic nested sampling on one device: a base ensemble of `runs` static runs of nlive_init live points, merged;
     then up to maxbatch batches of `strands` strands of nlive_batch live points each, placed by the merged run's
     weight_function(pfrac, maxfrac, pad) and folded in by merge_batch.  After every batch
@@ -229,10 +348,18 @@ def run_dynamic(prob, runs, nlive_init, strands, nlive_batch, maxbatch, pfrac=0.
     weighted choice (default: np.random.default_rng(entropy words)).  **kw goes to Context.ns_ensemble and
     Context.ns_batch alike (sample, walks, slices, bound, enlarge, bootstrap, ...; PCG64 streams, 'multi' / 'single').
 
-    Returns (MergedRun, log): log[0] describes the base run (and holds it, merged, under "run"), log[b] batch b --
+    merge='host' (default): the base ensemble is merged on the host and every strand folded in by merge_batch; the run
+    is a MergedRun.  merge='device': the base is merged on the device (run_ensemble_merged(merge='device')) and stays
+    there; per batch the saved run's logl and logvol columns cross once, the seeds' unit-cube rows by a gather, and all
+    strands fold in one dh_merged_fold (fold_batch); the run is a DeviceMergedRun.  Both routes run the same strands:
+    the seeds' choice and the PCG64 streams are the same functions of the same bits.
+
+    Returns (the run, log): log[0] describes the base run (and holds it, merged, under "run"), log[b] batch b --
     bounds, whether it started from the prior, ncall, seed_ncall, niter (points added), seconds, and the stopping
     function's verdict after it."""
     from .backend import get_backend
+    if merge not in ('host', 'device'):
+        raise ValueError(f"run_dynamic: merge={merge!r} (one of 'host', 'device')")
     be = get_backend()
     entropy = tuple(int(x) for x in np.atleast_1d(entropy))
     if queue_size is None:
@@ -240,17 +367,18 @@ def run_dynamic(prob, runs, nlive_init, strands, nlive_batch, maxbatch, pfrac=0.
     if rstate is None:
         rstate = np.random.default_rng(list(entropy))
     stop_kwargs = dict(stop_kwargs or {})
+    on_device = merge == 'device'
 
     def ptform(u):
         return be.problem_eval(prob, u)[0]
     t0 = time.perf_counter()
-    m = run_ensemble_merged(prob, runs, nlive_init, queue_size, entropy=entropy, max_iter=max_iter, merge='host',
+    m = run_ensemble_merged(prob, runs, nlive_init, queue_size, entropy=entropy, max_iter=max_iter, merge=merge,
                             dlogz=dlogz_init, **kw)
     base_runs = m.pop("runs")
-    # one run from here on: a point's id names its strand in the WHOLE run (run * nlive + slot for the base's)
-    m["samples_id"] = np.asarray(m["samples_run"], dtype=np.int64) * int(nlive_init) + np.asarray(m["samples_id"])
-    m["samples_run"] = np.zeros(len(m["logl"]), dtype=np.int64)
-    log = [dict(bounds=(-np.inf, np.inf), prior=True, ncall=int(base_runs["ncall"].sum()), niter=int(m["niter"]),
+    if not on_device:
+        # one run from here on: a point's id names its strand in the WHOLE run (run * nlive + slot for the base's)
+        m = single_run(m)  # (the device's first fold renumbers its base the same way)
+    log = [dict(bounds=(-np.inf, np.inf), prior=True, ncall=int(base_runs["ncall"].sum()), niter=int(m.niter),
                 seconds=time.perf_counter() - t0, stop=bool(m.stopping_function(**stop_kwargs)), run=m)]
     cap = max_iter if max_iter is not None else 80 * nlive_batch
     for b in range(1, int(maxbatch) + 1):
@@ -258,7 +386,9 @@ def run_dynamic(prob, runs, nlive_init, strands, nlive_batch, maxbatch, pfrac=0.
             break
         t0 = time.perf_counter()
         bounds = m.weight_function(pfrac=pfrac, maxfrac=maxfrac, pad=pad)
-        seeds = [batch_seed(m, bounds, nlive_batch, rstate) for _ in range(int(strands))]
+        # (the device's run: its two columns cross once per batch, the seeds' rows by a gather)
+        cols = _base_columns(m) if on_device else None
+        seeds = [batch_seed(m, bounds, nlive_batch, rstate, columns=cols) for _ in range(int(strands))]
         s0 = seeds[0]
         ent = entropy + (b,)
         if s0["prior"]:
@@ -268,17 +398,27 @@ def run_dynamic(prob, runs, nlive_init, strands, nlive_batch, maxbatch, pfrac=0.
             seed_calls = 0
         else:
             start = np.array(list(s0["start"]) + [1.0])  # (the merged run keeps no per-point scale: departure (d))
-            out = be.ns_batch(prob, np.stack([m["samples_u"][s["idx"]] for s in seeds]),
-                              np.stack([m["logl"][s["idx"]] for s in seeds]), s0["logl_min"], start, queue_size,
+            if on_device:
+                pick = np.concatenate([s["idx"] for s in seeds])
+                seed_u = m.gather(pick, "samples_u").reshape(len(seeds), -1, m.ndim)
+                seed_l = cols[0][pick].reshape(len(seeds), -1)
+            else:
+                seed_u = np.stack([m["samples_u"][s["idx"]] for s in seeds])
+                seed_l = np.stack([m["logl"][s["idx"]] for s in seeds])
+            out = be.ns_batch(prob, seed_u, seed_l, s0["logl_min"], start, queue_size,
                               logl_max=s0["logl_max"], entropy=ent, max_iter=cap, dlogz=dlogz_batch, **kw)
             seed_calls = int(out["seed_ncall"].sum())
         if (out["status"] != 0).any():
             raise RuntimeError(f"run_dynamic: strands of batch {b} failed, status {out['status']}")
-        added = 0
-        for r in range(int(strands)):
-            s = strand_of(out, r, nlive_batch, prior_transform=ptform)
-            m = merge_batch(m, s, s0["logl_min"], s0["logl_max"])
-            added += len(s["logl"])
+        if on_device:
+            m = fold_batch(m, out, nlive_batch, s0["logl_min"], s0["logl_max"])
+            added = int(np.sum(out["niter"])) + int(strands) * int(nlive_batch)
+        else:
+            added = 0
+            for r in range(int(strands)):
+                s = strand_of(out, r, nlive_batch, prior_transform=ptform)
+                m = merge_batch(m, s, s0["logl_min"], s0["logl_max"])
+                added += len(s["logl"])
         log.append(dict(bounds=(s0["logl_min"], s0["logl_max"]), prior=bool(s0["prior"]),
                         ncall=int(out["ncall"].sum()), seed_ncall=seed_calls, niter=added,
                         seconds=time.perf_counter() - t0, stop=bool(m.stopping_function(**stop_kwargs))))

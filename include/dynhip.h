@@ -744,7 +744,8 @@ int dh_ns_state_import(dh_ctx* ctx, int problem, const void* buf, uint64_t bytes
                        int64_t max_iter /* 0: as saved; else >= every run's niter */);
 
 /* Per-point fields of the merged run (dh_merged_fetch).  LOGL .. WEIGHT: one double per point; SAMPLES_U / SAMPLES:
- * ndim doubles per point; RUN .. NCALL: one int32 per point (ID / IT / NCALL only where the merge was given them). */
+ * ndim doubles per point; RUN .. NCALL and BATCH: one int32 per point (ID / IT / NCALL only where the merge was given
+ * them). */
 enum {
   DH_MERGED_LOGL = 0,
   DH_MERGED_LOGVOL = 1,
@@ -769,6 +770,10 @@ enum {
 /* Nor is this one: for dh_merged_realization and dh_merged_bootstrap_run, the cumulative Kullback-Leibler divergence of
  * one realization or bootstrap from the merged run (utils.kld_error, utils.py:1932-1997), a double per point. */
 #define DH_MERGED_KLD 17
+/* A field of the merged run again (dh_merged_fetch): the dynamic batch the point came in with, int32 -- 0 for the base
+ * run, b for the b-th strand folded in by dh_merged_fold (samples_batch of dynamicsampler.py:1467-1609); 0 everywhere
+ * on a run that holds no batch. */
+#define DH_MERGED_BATCH 18
 
 /* `runs` static runs of equal nlive merged into one run that stays on the device -- ensemble.merge_static_runs, i.e.
  * the reference's utils.merge_runs for such runs.  Host pointers: niter (runs), dead_logl / dead_id / dead_it / dead_nc
@@ -797,7 +802,43 @@ int dh_merged_resample(dh_ctx* ctx, double u0, int64_t n_out, int64_t* idx_out);
 /* Parameter rows of n points: out_v n x ndim (n x ndim < 2^32 per call).  idx NULL = the first n indices of the last
  * dh_merged_resample. */
 int dh_merged_gather(dh_ctx* ctx, int64_t n, const int64_t* idx_or_null, double* out_v);
+/* Rows of the n points idx of one row field, DH_MERGED_SAMPLES_U or DH_MERGED_SAMPLES: out n x ndim (n x ndim < 2^32 per
+ * call).  The seeds of a dynamic batch -- the unit-cube rows of the points _configure_batch_sampler chose
+ * (dynamicsampler.py:457-533) -- come to the host this way, without the column.  DH_ERR_ARG: no merged run, another
+ * field, n < 1, idx or out NULL, an index outside [0, M). */
+int dh_merged_gather_rows(dh_ctx* ctx, int field, int64_t n, const int64_t* idx, double* out);
 int dh_merged_release(dh_ctx* ctx);
+
+/* ---- dynamic batches folded into the merged run ------------------------------------------
+ * The strands of one batch folded into the context's merged run -- the reference's combine_runs
+ * (dynamicsampler.py:1467-1609) applied strand after strand, in strand order, with the same bounds; here in one pass.
+ * The strand arguments have the shapes and meaning of dh_merge_runs' run arguments: per strand niter[r] dead points in
+ * death order and nlive_new final live points in slot order (host pointers; id / it / nc / live it together, and only
+ * where the merged run has them).  The result replaces the merged run and stays on the device:
+ *   order    the stable order of (base, strand 0, .., strand R-1): on equal ln L the base point first, then the strands
+ *            by index, then a strand's own order (:1517-1552)
+ *   n        the base's live count at its next point (0 past its end) plus, where ln L > logl_min (strictly), the
+ *            strands': strands x nlive_new less their final live points before the position (:1528-1545)
+ *   id       strand s shifted by (the largest id so far) + 1; a base that is a merge of several static runs is first
+ *            renumbered id <- run x nlive + id, run <- 0; new points get run 0, seq their index in the strand's own
+ *            sequence, final 1 for a final live point, batch = (batches before) + 1 + s
+ *   ln X     combine_runs' plateau rule (:1554-1583): an ordinary point steps by log1p(1 / n); p >= 2 equal ln L
+ *            entered at volume X with live count n take ln X + log1p(-(j + 1) / (n + 1)), j = 0 .. p - 1
+ *   ln w, ln Z, H, var ln Z, the weights, the moments, the summary: recomputed over the whole run as by dh_merge_runs,
+ *            every point with its own step ln X_{k-1} - ln X_k
+ *   rows     the base's u and v rows move bit for bit; a new point's v is dh_problem_eval of its u, bit for bit
+ * summary_out: 6 doubles as dh_merge_runs'.  The fold is built beside the base run and swapped in on success, so EVERY
+ * error leaves the merged run as it was:
+ * DH_ERR_ARG: no merged run, a problem of another ndim, strands < 1, nlive_new < 1, logl_min not finite (a batch from
+ * the prior passes -DBL_MAX), logl_max <= logl_min, id / it / nc on one side only, M + W >= 2^31 points or
+ * (M + W) x ndim >= 2^32 elements.  DH_ERR_VALUE: a NaN, a strand's sequence that decreases, a strand point with
+ * ln L <= logl_min, a plateau of p >= n + 1 points (no positive volume is left; the reference's log fails there).
+ * DH_ERR_NOMEM.  After a fold dh_merged_bootstrap, dh_merged_bootstrap_run and the DH_KLD_RESAMPLE / DH_KLD_SIMULATE
+ * modes of dh_merged_kld answer DH_ERR_ARG: the strand bootstrap is not defined for a run that carries dynamic batches. */
+int dh_merged_fold(dh_ctx* ctx, int problem, int strands, int nlive_new, int64_t stride, const int64_t* niter,
+                   const double* dead_logl, const double* live_logl, const double* dead_u, const double* live_u,
+                   const int32_t* dead_id, const int32_t* dead_it, const int32_t* dead_nc, const int32_t* live_it,
+                   double logl_min, double logl_max, double* summary_out);
 
 /* ---- marginals of the merged run --------------------------------------------------------
  * All three work on the merged run's parameter rows (the SAMPLES field) and normalised weights (the WEIGHT field)
@@ -868,7 +909,8 @@ int dh_merged_realization(dh_ctx* ctx, uint64_t seed, int64_t real, int jitter, 
  * (M') of nboot each (h, ess, npoints may be NULL), mean [nboot][ndim] with want_mean.  A bootstrap's numbers depend on
  * (seed, b) alone.  mult_or_null: S host values >= 0 in strand-key order that replace the drawn multiplicities
  * (nboot = 1; their sum need not be S).
- * DH_ERR_ARG (the merged run stays): no merged run, a merge without id / it / nc, nboot outside [1, 65536], first < 0,
+ * DH_ERR_ARG (the merged run stays): no merged run, a merge without id / it / nc, a run that holds dynamic batches
+ * (dh_merged_fold: strands are read off a live count that only falls), nboot outside [1, 65536], first < 0,
  * jitter not 0 or 1, mult with nboot != 1 or a negative entry, M' = 0 or M' >= 2^31, want_mean without mean or the
  * reverse, no logz. */
 int dh_merged_bootstrap(dh_ctx* ctx, uint64_t seed, int64_t first, int nboot, int jitter, const int32_t* mult_or_null,
