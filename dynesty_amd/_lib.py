@@ -130,6 +130,7 @@ SIGNATURES = {
     "dh_ns_batch": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _dbl, _dbl, C.c_int64, C.c_int64, _vp, _i, _u32,
                          _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
                          _vp, _vp, _vp, _vp, _vp]),
+    "dh_merged_batch_seed": (_i, [_vp, _u64, C.c_int64, _i, _i, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "dh_ns_state_size": (_i, [_vp, _vp]),
     "dh_ns_state_export": (_i, [_vp, _vp, _u64]),
     "dh_ns_state_import": (_i, [_vp, _i, _vp, _u64, C.c_int64]),
@@ -379,6 +380,17 @@ class DeviceMergedRun(dict, Marginals, Errors):
             ctx._check_merge(ctx.lib.dh_merged_gather_rows(ctx.handle, MERGED_FIELDS[field][0], len(idx), _ptr(idx),
                                                            _ptr(out)))
         return out
+
+    def batch_seeds(self, logl_min, nlive_new, strands, seed, first=0, want_rows=True, want_keys=False):
+        """The start points of `strands` strands of one dynamic batch, chosen on the device (dh_merged_batch_seed;
+        seeds.batch_seeds_host is the NumPy mirror, dynamic.batch_seed the Generator's form of the same law): dict(prior,
+        idx (strands, nlive_new) or None, keys (with want_keys) or None, logl_min (effective), vol_idx, start, lo, count,
+        n_pos, passes) and, with want_rows, seed_u (strands, nlive_new, ndim) and seed_logl (strands, nlive_new): the
+        chosen points' unit-cube rows and ln L as Context.ns_batch takes them, gathered on the device (no column and
+        no second call crosses for them).  Raises RuntimeError where no point lies above logl_min and ValueError where
+        fewer than nlive_new points of positive weight do, as dynamic.batch_seed."""
+        return self._live().merged_batch_seed(self, logl_min, nlive_new, strands, seed, first=first, want_rows=want_rows,
+                                              want_keys=want_keys)
 
     def _cols_ptr(self, cols):
         """NULL for all columns in order (the C calls' own default), else the list."""
@@ -733,6 +745,41 @@ class Context:
             self._merge_serial += 1  # (every failure leaves the base run in place: the handle stays valid)
         self._check_merge(rc)
         return DeviceMergedRun(self, summ, nd, have_pt, b_nlive + [N] * R, b_bounds + [(lmin, lmax)] * R, prob=prob)
+
+    def merged_batch_seed(self, base, logl_min, nlive_new, strands, seed, first=0, want_rows=True, want_keys=False):
+        """dh_merged_batch_seed on the merged run `base` (DeviceMergedRun.batch_seeds documents the result)."""
+        if not isinstance(base, DeviceMergedRun) or base.ctx is not self:
+            raise ValueError("merged_batch_seed: base must be this context's DeviceMergedRun")
+        base._live()
+        strands, k = int(strands), int(nlive_new)
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed: an unsigned 64-bit integer")
+        ok = 1 <= strands <= 65536 and 1 <= k <= 65535  # (the call refuses the rest: no buffers of a bad shape)
+        idx = np.empty((strands, k), dtype=np.int64) if ok else None
+        keys = np.empty((strands, k)) if ok and want_keys else None
+        seed_u = np.empty((strands, k, base.ndim)) if ok and want_rows else None
+        seed_l = np.empty((strands, k)) if ok and want_rows else None
+        info = np.zeros(12)
+        rc = self.lib.dh_merged_batch_seed(self.handle, int(seed), int(first), strands, k, float(logl_min), _ptr(idx),
+                                           _ptr(keys), _ptr(seed_u), _ptr(seed_l), _ptr(info))
+        if rc == ERR_VALUE:
+            raise RuntimeError(self.lib.dh_last_error(self.handle).decode())
+        self._check_merge(rc)
+        prior, lo, count, n_pos = bool(info[0]), int(info[1]), int(info[2]), int(info[3])
+        out = dict(prior=prior, idx=None, keys=None, logl_min=float(info[4]), vol_idx=int(info[5]),
+                   start=None if prior else tuple(float(x) for x in info[6:11]), lo=lo, count=count, n_pos=n_pos,
+                   passes=int(info[11]))
+        if want_rows:
+            out.update(seed_u=None, seed_logl=None)
+        if prior and lo == 0 and count == base.niter and n_pos == 0:
+            return out  # from the prior: no choice was made
+        if n_pos < k:
+            raise ValueError(f"batch_seeds: {n_pos} saved points of positive weight above ln L = {out['logl_min']}, "
+                             f"nlive_new = {k} are needed (a batch on fewer live points is not supported)")
+        out["idx"], out["keys"] = idx, keys
+        if want_rows:
+            out.update(seed_u=seed_u, seed_logl=seed_l)
+        return out
 
     def merge_kept(self, prob, niter=None):
         """dh_merge_kept: the merged run of the ensemble the last ns_ensemble(keep=True) left on the device."""

@@ -128,6 +128,36 @@ __device__ __forceinline__ double logaddexp_np(double x, double y) {  // np.loga
   return x + y;
 }
 
+// ---- the counter-based stream of the statistical errors and of the seeds' choice -------------------------------------
+
+// Philox4x32-10 under key `seed`, rocrand's stream model: block `blk` of subsequence `seq`, four words in stream order
+__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t seq, uint64_t blk, uint32_t* w) {
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  uint32_t c0 = (uint32_t)blk, c1 = (uint32_t)(blk >> 32), c2 = (uint32_t)seq, c3 = (uint32_t)(seq >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+  }
+  w[0] = c0;
+  w[1] = c1;
+  w[2] = c2;
+  w[3] = c3;
+}
+// rocrand's uniform_distribution_double(v1, v2): (0, 1], exact
+__device__ __forceinline__ double uniform_double(uint32_t w0, uint32_t w1) {
+  const unsigned long long m = (unsigned long long)w0 | ((unsigned long long)(w1 >> 11) << 32);
+  return 1.1102230246251565e-16 + (double)m * 1.1102230246251565e-16;
+}
+
 template <class F>
 bool run_scan(dh_ctx* ctx, const F& f, long long M, void* part) {
   typedef typename F::Op Op;

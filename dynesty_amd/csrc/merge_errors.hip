@@ -21,32 +21,7 @@ constexpr int kMeanLoads = 16;  // rows of v a thread of the mean sums has in fl
 constexpr int kFinLoads = 8;    // chunks a thread of me_finish has in flight
 constexpr double kLnHalf = -0.6931471805599453;
 
-__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint64_t seq, uint64_t blk, uint32_t* w) {
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  uint32_t c0 = (uint32_t)blk, c1 = (uint32_t)(blk >> 32), c2 = (uint32_t)seq, c3 = (uint32_t)(seq >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0;
-    c1 = l1;
-    c2 = h0 ^ c3 ^ k1;
-    c3 = l0;
-  }
-  w[0] = c0;
-  w[1] = c1;
-  w[2] = c2;
-  w[3] = c3;
-}
-// rocrand's uniform_distribution_double(v1, v2): (0, 1], exact
-__device__ __forceinline__ double uniform_double(uint32_t w0, uint32_t w1) {
-  const unsigned long long m = (unsigned long long)w0 | ((unsigned long long)(w1 >> 11) << 32);
-  return 1.1102230246251565e-16 + (double)m * 1.1102230246251565e-16;
-}
+// (philox4x32_10 and uniform_double: merge_dev.h, shared with the seeds' choice)
 __device__ __forceinline__ double expected_step(int n) { return -log1p(1.0 / (double)n); }
 
 // the steps of the points k0 .. k0 + kItems - 1 (k0 a multiple of kItems: whole Philox blocks)

@@ -434,4 +434,126 @@ inline void carve_weights(Carver& c, WeightBuf& w, size_t M) {
   c(w.wt, "wt", M);
 }
 
+// ---- the seeds of a dynamic batch chosen on the device (merge_seed.hip) --------------------
+// Per strand the k = nlive_new largest keys logvol_i + Gumbel(seed, strand, i) over the points above logl_min: a radix
+// select on the keys' order-preserving 64-bit image, 8 bits per pass from the top, the keys made again in every pass.
+
+constexpr int kSeedStrandsMax = 65536;  // strands per call
+constexpr int kSeedNliveMax = 65535;    // the resident loop's limit on nlive_new
+constexpr int kSeedPairs = 4;           // Philox blocks (two neighbouring points each) per thread of a pass
+constexpr int kSeedChunk = kT * kSeedPairs * 2;  // points per workgroup of a pass
+constexpr int kSeedTile = 8;            // strands a workgroup carries through its chunk
+constexpr int kSeedBins = 256;          // bins of a pass: 8 bits of the image
+constexpr int kSeedPasses = 8;          // at most: the image has 64 bits
+constexpr int kSeedCap = 2048;          // a threshold bin of at most this many keys is not narrowed further
+constexpr int kSeedRankTile = 1024;     // (image, index) pairs staged in LDS per step of the final rank sort
+constexpr int kSeedInfo = 12;           // info_out: prior, lo, count, n_pos, logl_min, vol_idx, start[5], passes
+constexpr double kSeedLogMin = -708.0;  // a point has positive weight iff logvol - max(logvol) >= this
+
+enum SeedVerdict : int {
+  SV_OK = 0,
+  SV_NO_RUN = 1,   // no merged run in the context
+  SV_STRANDS = 2,  // strands < 1 or > kSeedStrandsMax
+  SV_NLIVE = 3,    // nlive_new < 1 or > kSeedNliveMax
+  SV_LOGL_MIN = 4, // logl_min is NaN
+  SV_INFO = 5,     // info_out is NULL
+  SV_FIRST = 6,    // first < 0 or first + strands beyond 2^62 (the subsequences 2^63 + 2^62 + s stay below 2^64)
+};
+inline const char* seed_verdict_text(int v) {
+  switch (v) {
+    case SV_OK: return "ok";
+    case SV_NO_RUN: return "no merged run in this context";
+    case SV_STRANDS: return "strands must be 1 ... 65536";
+    case SV_NLIVE: return "nlive_new must be 1 ... 65535";
+    case SV_LOGL_MIN: return "logl_min is NaN";
+    case SV_INFO: return "info_out is required";
+    case SV_FIRST: return "first must be 0 ... 2^62 - strands";
+  }
+  return "?";
+}
+// The first reason to refuse the request, in the order above (decided before the device is touched).
+inline int seed_check(bool have_run, long long first, int strands, int nlive_new, double logl_min, bool have_info) {
+  if (!have_run) return SV_NO_RUN;
+  if (strands < 1 || strands > kSeedStrandsMax) return SV_STRANDS;
+  if (nlive_new < 1 || nlive_new > kSeedNliveMax) return SV_NLIVE;
+  if (logl_min != logl_min) return SV_LOGL_MIN;
+  if (!have_info) return SV_INFO;
+  if (first < 0 || first > (1ll << 62) - strands) return SV_FIRST;
+  return SV_OK;
+}
+
+// The launch of a pass over the subset [lo, M): whole Philox blocks (block b serves points 2 b and 2 b + 1) from the
+// one that holds lo, kSeedPairs per thread; a workgroup carries kSeedTile strands through its chunk.
+struct SeedGrid {
+  long long pair0, npairs;
+  unsigned chunks, tiles;
+};
+inline SeedGrid seed_grid(long long lo, long long M, int strands) {
+  SeedGrid g;
+  g.pair0 = lo >> 1;
+  g.npairs = ((M + 1) >> 1) - g.pair0;
+  g.chunks = blocks_for((size_t)g.npairs, (size_t)kT * kSeedPairs);
+  g.tiles = blocks_for((size_t)strands, kSeedTile);
+  return g;
+}
+// (image, index) pairs a strand's collect pass can emit: everything above the threshold bin (fewer than k) and that
+// bin (at most kSeedCap, or exactly what is still needed), never more than the points of positive weight
+inline size_t seed_ecap(int k, long long n_pos) {
+  const long long e = (long long)k + kSeedCap;
+  return (size_t)(e < n_pos ? e : n_pos);
+}
+inline size_t seed_pass_lds() { return (size_t)2 * kSeedBins * 4; }
+inline size_t seed_rank_lds() { return (size_t)kSeedRankTile * (8 + 4); }
+
+// a strand's state between the passes
+struct SeedState {
+  u64 prefix;  // the image's bits decided so far
+  int need;    // keys still to take from the threshold bin
+  int shift;   // where the next pass's digit starts (56 in the first pass, -8 when all 64 bits are decided)
+  int active;  // 0: the threshold bin is small enough (or exact)
+  unsigned pop;  // the threshold bin's population
+};
+
+// the head of a call: what the bounds, the maximum and the count leave for the host
+struct SeedHead {
+  double* info;  // kSeedInfo
+  long long* li; // lo, count
+  u64 *maxbits, *npos;
+  int *flags, *nactive;
+};
+inline void carve_seed_head(Carver& c, SeedHead& h) {
+  c(h.info, "info", kSeedInfo);
+  c(h.li, "li", 2);
+  c(h.maxbits, "maxbits", 1);
+  c(h.npos, "npos", 1);
+  c(h.flags, "flags", 4);
+  c(h.nactive, "nactive", 1);
+}
+// the select's scratch: S strands, k seeds each, ecap pairs per strand
+struct SeedSelBuf {
+  unsigned *bins, *cnt;
+  SeedState* st;
+  u64* pimg;
+  int* pidx;
+  long long* idx;
+  double* key;
+};
+inline void carve_seed_select(Carver& c, SeedSelBuf& b, size_t S, size_t k, size_t ecap) {
+  c(b.bins, "bins", S * kSeedBins);
+  c(b.cnt, "cnt", S);
+  c(b.st, "st", S);
+  c(b.pimg, "pimg", S * ecap);
+  c(b.pidx, "pidx", S * ecap);
+  c(b.idx, "idx", S * k);
+  c(b.key, "key", S * k);
+}
+// the gathered rows: the chosen points' unit-cube rows and ln L, strand after strand in draw order
+struct SeedStage {
+  double *u = nullptr, *logl = nullptr;
+};
+inline void carve_seed_stage(Carver& c, SeedStage& s, size_t S, size_t k, size_t D) {
+  c(s.u, "u", S * k * D);
+  c(s.logl, "logl", S * k);
+}
+
 }  // namespace dh_merge

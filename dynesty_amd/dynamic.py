@@ -15,7 +15,9 @@ into the saved run.  Here
   fold_batch   folds an ns_batch / ns_ensemble result into a MergedRun (merge_strands) or a DeviceMergedRun (the
                device's fold),
   run_dynamic  is the loop around them: weight_function -> batch_seed x strands -> ns_batch -> merge_batch (merge='host')
-               or fold_batch on the device (merge='device') -> stopping_function.
+               or fold_batch on the device (merge='device') -> stopping_function.  With seeds='device' the seeds of all
+               strands are chosen where the merged run lives (DeviceMergedRun.batch_seeds, csrc/merge_seed.hip; the
+               NumPy mirror is seeds.py); the chosen rows come back with the indices and go into ns_batch.
 
 Where this departs from the reference: a batch needs nlive_new seeds of positive weight (the reference goes on with
 fewer live points; batch_seed raises ValueError); the device's departures (a)-(d) are listed in include/dynhip.h.
@@ -338,7 +340,7 @@ def fold_batch(base, out, nlive_new, logl_min, logl_max, prior_transform=None):
 
 def run_dynamic(prob, runs, nlive_init, strands, nlive_batch, maxbatch, pfrac=0.8, entropy=(21,), queue_size=None,
                 maxfrac=0.8, pad=1, dlogz_init=0.01, dlogz_batch=0.01, max_iter=None, rstate=None, stop_kwargs=None,
-                merge='host', **kw):
+                merge='host', seeds='host', **kw):
     """Dynamic nested sampling on one device: a base ensemble of `runs` static runs of nlive_init live points, merged;
     then up to maxbatch batches of `strands` strands of nlive_batch live points each, placed by the merged run's
     weight_function(pfrac, maxfrac, pad) and folded in by merge_batch.  After every batch
@@ -354,12 +356,23 @@ def run_dynamic(prob, runs, nlive_init, strands, nlive_batch, maxbatch, pfrac=0.
     strands fold in one dh_merged_fold (fold_batch); the run is a DeviceMergedRun.  Both routes run the same strands:
     the seeds' choice and the PCG64 streams are the same functions of the same bits.
 
+    seeds='host' (default): dynamic.batch_seed per strand, the Generator's weighted choice.  seeds='device' (with
+    merge='device' only): per batch ONE DeviceMergedRun.batch_seeds chooses the seeds of all strands where the run
+    lives (the same law as a pure function of a per-batch seed, SeedSequence(entropy + (b,)); rstate is not used) and
+    returns their rows and ln L, gathered on the device, for ns_batch; fold_batch folds.  The logl / logvol columns do
+    not cross PCIe and no gather call is made; the chosen rows come down and go back up.  A batch from the prior runs
+    through ns_ensemble(logl_max=) on either route.
+
     Returns (the run, log): log[0] describes the base run (and holds it, merged, under "run"), log[b] batch b --
     bounds, whether it started from the prior, ncall, seed_ncall, niter (points added), seconds, and the stopping
-    function's verdict after it."""
+    function's verdict after it, and which route chose the seeds."""
     from .backend import get_backend
     if merge not in ('host', 'device'):
         raise ValueError(f"run_dynamic: merge={merge!r} (one of 'host', 'device')")
+    if seeds not in ('host', 'device'):
+        raise ValueError(f"run_dynamic: seeds={seeds!r} (one of 'host', 'device')")
+    if seeds == 'device' and merge != 'device':
+        raise ValueError("run_dynamic: seeds='device' chooses the seeds where the merged run lives: it needs merge='device'")
     be = get_backend()
     entropy = tuple(int(x) for x in np.atleast_1d(entropy))
     if queue_size is None:
@@ -386,25 +399,37 @@ def run_dynamic(prob, runs, nlive_init, strands, nlive_batch, maxbatch, pfrac=0.
             break
         t0 = time.perf_counter()
         bounds = m.weight_function(pfrac=pfrac, maxfrac=maxfrac, pad=pad)
-        # (the device's run: its two columns cross once per batch, the seeds' rows by a gather)
-        cols = _base_columns(m) if on_device else None
-        seeds = [batch_seed(m, bounds, nlive_batch, rstate, columns=cols) for _ in range(int(strands))]
-        s0 = seeds[0]
         ent = entropy + (b,)
+        if seeds == 'device':
+            # one call for all strands, their rows gathered on the device; the batch's seed is a function of ent
+            bseed = int(np.random.SeedSequence(list(ent)).generate_state(1, np.uint64)[0])
+            s0 = m.batch_seeds(bounds[0], nlive_batch, int(strands), bseed, want_rows=True)
+            s0["logl_max"] = float(bounds[1])
+            picked = None
+        else:
+            # (the device's run: its two columns cross once per batch, the seeds' rows by a gather)
+            cols = _base_columns(m) if on_device else None
+            picked = [batch_seed(m, bounds, nlive_batch, rstate, columns=cols) for _ in range(int(strands))]
+            s0 = picked[0]
         if s0["prior"]:
             # logl_min = -inf: an ordinary ensemble of nlive_batch live points up to logl_max
             out = be.ns_ensemble(prob, int(strands), nlive_batch, queue_size, entropy=ent, max_iter=cap,
                                  want_samples=True, dlogz=dlogz_batch, logl_max=s0["logl_max"], **kw)
             seed_calls = 0
+        elif seeds == 'device':
+            start = np.array(list(s0["start"]) + [1.0])
+            out = be.ns_batch(prob, s0["seed_u"], s0["seed_logl"], s0["logl_min"], start, queue_size,
+                              logl_max=s0["logl_max"], entropy=ent, max_iter=cap, dlogz=dlogz_batch, **kw)
+            seed_calls = int(out["seed_ncall"].sum())
         else:
             start = np.array(list(s0["start"]) + [1.0])  # (the merged run keeps no per-point scale: departure (d))
             if on_device:
-                pick = np.concatenate([s["idx"] for s in seeds])
-                seed_u = m.gather(pick, "samples_u").reshape(len(seeds), -1, m.ndim)
-                seed_l = cols[0][pick].reshape(len(seeds), -1)
+                pick = np.concatenate([s["idx"] for s in picked])
+                seed_u = m.gather(pick, "samples_u").reshape(len(picked), -1, m.ndim)
+                seed_l = cols[0][pick].reshape(len(picked), -1)
             else:
-                seed_u = np.stack([m["samples_u"][s["idx"]] for s in seeds])
-                seed_l = np.stack([m["logl"][s["idx"]] for s in seeds])
+                seed_u = np.stack([m["samples_u"][s["idx"]] for s in picked])
+                seed_l = np.stack([m["logl"][s["idx"]] for s in picked])
             out = be.ns_batch(prob, seed_u, seed_l, s0["logl_min"], start, queue_size,
                               logl_max=s0["logl_max"], entropy=ent, max_iter=cap, dlogz=dlogz_batch, **kw)
             seed_calls = int(out["seed_ncall"].sum())
@@ -420,6 +445,6 @@ def run_dynamic(prob, runs, nlive_init, strands, nlive_batch, maxbatch, pfrac=0.
                 m = merge_batch(m, s, s0["logl_min"], s0["logl_max"])
                 added += len(s["logl"])
         log.append(dict(bounds=(s0["logl_min"], s0["logl_max"]), prior=bool(s0["prior"]),
-                        ncall=int(out["ncall"].sum()), seed_ncall=seed_calls, niter=added,
+                        ncall=int(out["ncall"].sum()), seed_ncall=seed_calls, niter=added, seeds=seeds,
                         seconds=time.perf_counter() - t0, stop=bool(m.stopping_function(**stop_kwargs))))
     return m, log

@@ -289,6 +289,22 @@ class MergedRun(dict, Marginals, Errors):
         w = np.exp(self["logwt"] - np.max(self["logwt"]))
         return float(self["logzerr"][-1]), float(w.sum() ** 2 / (w * w).sum())
 
+    def batch_seeds(self, logl_min, nlive_new, strands, seed, first=0, want_rows=True, want_keys=False):
+        """The start points of `strands` strands of one dynamic batch as a pure function of (seed, strand, point):
+        seeds.batch_seeds_host on this run's columns, the mirror of _lib.DeviceMergedRun.batch_seeds.  dict(prior, idx,
+        keys, logl_min, vol_idx, start, lo, count, n_pos) and, with want_rows, seed_u / seed_logl (samples_u and logl at
+        idx)."""
+        from .seeds import batch_seeds_host
+        out = batch_seeds_host(self["logl"], self["logvol"], self["logz"], self["information"], self["logzerr"], logl_min,
+                               nlive_new, seed, strands, first)
+        if not want_keys:
+            out["keys"] = None
+        if want_rows:
+            has = out["idx"] is not None and self.get("samples_u") is not None
+            out["seed_u"] = np.asarray(self["samples_u"])[out["idx"]] if has else None
+            out["seed_logl"] = np.asarray(self["logl"])[out["idx"]] if out["idx"] is not None else None
+        return out
+
     def importance_weights(self):
         """Normalised posterior weights exp(logwt - logz[-1])."""
         w = np.exp(self["logwt"] - self["logz"][-1])

@@ -40,6 +40,8 @@ import numpy as np
 MAX_REAL = 65536  # realizations per call (dh_merged_realize's cap)
 MAX_BOOT = 65536  # bootstraps per call (dh_merged_bootstrap's cap)
 BOOT_SEQ = 1 << 63  # bootstrap b draws its strands from subsequence BOOT_SEQ + b: realization indices stay below it
+# (the subsequences of one seed: realizations [0, 2^63), bootstraps 2^63 + b with b < 2^62, and from 2^63 + 2^62 on the
+# strands of a dynamic batch's weighted choice of seeds -- seeds.SEED_SEQ + s, csrc/merge_seed.hip)
 FIELDS = ("logvol", "logwt", "logz")
 BOOT_FIELDS = ("idx", "samples_n", "logvol", "logwt", "logz")
 KLD_MODES = ("jitter", "resample", "simulate")  # dh_merged_kld's DH_KLD_JITTER, _RESAMPLE, _SIMULATE

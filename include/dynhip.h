@@ -840,6 +840,41 @@ int dh_merged_fold(dh_ctx* ctx, int problem, int strands, int nlive_new, int64_t
                    const int32_t* dead_id, const int32_t* dead_it, const int32_t* dead_nc, const int32_t* live_it,
                    double logl_min, double logl_max, double* summary_out);
 
+/* ---- the seeds of a dynamic batch, chosen where the merged run lives (csrc/merge_seed.hip) --
+ * dh_merged_batch_seed chooses the start points of `strands` strands of one batch in one call: the reference's
+ * _configure_batch_sampler (dynamicsampler.py:394-416 the subset, :457-533 the weighted choice without replacement,
+ * :606-610 vol_idx), dynamic.batch_seed on the host.  The choice is the reference's successive sampling, order of the
+ * draws included, written as a pure function (Plackett-Luce: the nlive_new largest of logvol_i + Gumbel noise):
+ *   words   strand s of the call is the global strand first + s and uses subsequence 2^63 + 2^62 + first + s of the
+ *           Philox4x32-10 stream keyed by `seed` (volume realizations stay below 2^63, bootstraps are 2^63 + b); point
+ *           i -- its index in the merged run -- takes words 2 i and 2 i + 1; u = 2^-53 + m 2^-53 in (0, 1] as for the
+ *           realizations
+ *   key     logvol_i - log(-log u); u = 1 gives +inf, a legal key that is always chosen
+ *   order   descending key, equal keys by smaller i; the strand's seeds are the first nlive_new points, in that order
+ *   subset  lo = #{logl <= logl_min}; lo = 0: from the prior, no choice is made; fewer than nlive_new points above
+ *           logl_min: the boundary moves down to the last nlive_new points and logl_min becomes logl[lo' - 1], or -inf
+ *           at lo' = 0 (the seeds stand, the strand is a prior strand); vol_idx = argmin |logl - logl_min| + 1, first
+ *           occurrence; the start row is (logvol, logz, information, logzerr^2, logl) at vol_idx - 1
+ * idx_out / key_out (optional, strands x nlive_new): the chosen indices into the merged run in draw order, their keys.
+ * u_out (optional, strands x nlive_new x ndim) / logl_out (optional, strands x nlive_new): the chosen points' unit-cube
+ * rows and ln L, gathered on the device and brought down in one piece -- what dh_ns_batch takes as seed_u and
+ * seed_logl; the logl and logvol columns never cross.
+ * info_out (required, 12 doubles): prior (0 / 1), lo, count (points of the subset), n_pos (those of positive weight),
+ * logl_min (effective), vol_idx, start[5] (NaN for a prior batch), the select's histogram passes.  n_pos < nlive_new
+ * (dynamic.batch_seed's ValueError) and prior = 1 with lo = 0 and n_pos = 0 are answers in info_out, not errors: no
+ * choice is returned.
+ * Departures from dynamic.batch_seed: (a) the stream is Philox, not the Generator's; the law is the same, the indices
+ * are not; (b) a point has positive weight iff logvol_i - max(logvol over the subset) >= -708, a threshold on exp's
+ * argument where the host tests exp(..) / sum > 0 (the two libraries' exp may differ at the denormal edge); (c) more
+ * than 2048 exactly equal keys at a strand's threshold -- every one u = 1 -- are DH_ERR_VALUE.
+ * Not built: a staging block that would keep the chosen rows on the device for dh_ns_batch.
+ * Errors, all leaving the merged run as it was: DH_ERR_ARG: no merged run, strands < 1 or > 65536, nlive_new < 1 or
+ * > 65535, NaN logl_min, info_out NULL, first < 0, strands x nlive_new x ndim >= 2^32.  DH_ERR_VALUE: no point above
+ * logl_min (the reference's RuntimeError).  DH_ERR_NOMEM. */
+int dh_merged_batch_seed(dh_ctx* ctx, uint64_t seed, int64_t first, int strands, int nlive_new, double logl_min,
+                         int64_t* idx_out_or_null, double* key_out_or_null, double* u_out_or_null, double* logl_out_or_null,
+                         double* info_out);
+
 /* ---- marginals of the merged run --------------------------------------------------------
  * All three work on the merged run's parameter rows (the SAMPLES field) and normalised weights (the WEIGHT field)
  * where they live; only the results come to the host.  Every sum of weights is a sum of the integers
