@@ -16,6 +16,7 @@
 // ns_prepare).  oracle/nested_ref.py boot_generator restates it.
 #include "ctx.h"
 #include "rng_pcg64.h"
+#include "stage_plan.h"
 
 using namespace dh;
 
@@ -260,24 +261,22 @@ int dh_bootstrap_expand(dh_ctx* ctx, int runs, const double* pts, int n, int d, 
   if (runs < 1 || bootstrap < 1 || n < 2 || d < 1 || !pts || !ent || !expand)
     return dh::fail(ctx, DH_ERR_ARG, "bootstrap_expand: bad arguments");
   const int me = multi ? (n / (2 * d) > 0 ? n / (2 * d) : 1) : 1;
-  dh::arena_reset(ctx);
-  const size_t wsb = dh::bootstrap_ws_bytes(runs, n, d, me, bootstrap);
-  int rc = dh::arena_reserve(ctx, wsb + (size_t)runs * n * d * 8 + (size_t)runs * (32 + 16) + 4096);
+  dh_stage::BootExpandBuf b;
+  int rc = dh::arena_carve(ctx, [&](dh_stage::Carver& c) {
+    dh_stage::carve_boot_expand(c, b, (size_t)runs, (size_t)n, (size_t)d,
+                                dh::bootstrap_ws_bytes(runs, n, d, me, bootstrap));
+  });
   if (rc) return rc;
-  const double* d_pts = dh::arena_up(ctx, pts, (size_t)runs * n * d);
-  const uint64_t* d_ent = dh::arena_up(ctx, ent, (size_t)runs * 4);
-  void* ws = dh::arena_get(ctx, wsb);
-  double* d_shift = (double*)dh::arena_get(ctx, (size_t)runs * 8);
-  double* d_ex = (double*)dh::arena_get(ctx, (size_t)runs * 8);
-  int* d_bs = (int*)dh::arena_get(ctx, (size_t)runs * 4);
-  if (!d_pts || !d_ent || !ws || !d_shift || !d_ex || !d_bs) return DH_ERR_NOMEM;
-  if (!dh::hip_ok(ctx, hipMemsetAsync(d_bs, 0, (size_t)runs * 4, ctx->stream), "memset")) return DH_ERR_HIP;
-  rc = dh::bootstrap_expand_launch(ctx, runs, d_pts, n, d, multi, me, bootstrap, d_ent, nullptr, ws, d_shift, d_ex, d_bs);
+  if (!dh::arena_fill(ctx, b.pts, pts, (size_t)runs * n * d) || !dh::arena_fill(ctx, b.ent, ent, (size_t)runs * 4))
+    return DH_ERR_NOMEM;
+  if (!dh::hip_ok(ctx, hipMemsetAsync(b.bstatus, 0, (size_t)runs * 4, ctx->stream), "memset")) return DH_ERR_HIP;
+  rc = dh::bootstrap_expand_launch(ctx, runs, b.pts, n, d, multi, me, bootstrap, b.ent, nullptr, b.ws, b.shift, b.expand,
+                                   b.bstatus);
   if (rc) return rc;
   std::vector<int> bs(runs);
-  if (!dh::down(ctx, expand, d_ex, (size_t)runs) || !dh::down(ctx, bs.data(), d_bs, (size_t)runs)) return DH_ERR_HIP;
+  if (!dh::down(ctx, expand, b.expand, (size_t)runs) || !dh::down(ctx, bs.data(), b.bstatus, (size_t)runs)) return DH_ERR_HIP;
   // (the replicas' sample sizes sit right behind the points and the masks in the workspace: see bootstrap_expand_launch)
-  if (n_in && !dh::down(ctx, n_in, (const int32_t*)((char*)ws + al256((size_t)runs * bootstrap * n * d * 8) +
+  if (n_in && !dh::down(ctx, n_in, (const int32_t*)((char*)b.ws + al256((size_t)runs * bootstrap * n * d * 8) +
                                                      al256((size_t)runs * bootstrap * n)),
                         (size_t)runs * bootstrap))
     return DH_ERR_HIP;

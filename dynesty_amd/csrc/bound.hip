@@ -1,5 +1,6 @@
 // Bounding kernels: ellipsoid membership (K5).  Rebuild kernels follow below.
 #include "ctx.h"
+#include "stage_plan.h"
 
 using namespace dh;
 
@@ -287,36 +288,33 @@ int dh_contains(dh_ctx* ctx, const double* x, int k, int d, const double* ctrs, 
   if (k <= 0) return DH_OK;
   if (!x || !ctrs || !ams || !count || d < 1 || m < 1 || (mode != 0 && mode != 1))
     return fail(ctx, DH_ERR_ARG, "contains: bad arguments (d=%d m=%d mode=%d)", d, m, mode);
-  arena_reset(ctx);
   const size_t nwords = (size_t)(k + 63) / 64;
-  int rc = arena_reserve(ctx, ((size_t)k * d + (size_t)m * d + (size_t)m * d * d + (size_t)k * m) * 8 +
-                                  (size_t)k * 4 + nwords * m * 8 + 8192);
+  dh_stage::ContainsBuf b;
+  int rc = arena_carve(ctx, [&](dh_stage::Carver& c) {
+    dh_stage::carve_contains(c, b, (size_t)k, (size_t)d, (size_t)m, mask != nullptr, quad != nullptr);
+  });
   if (rc) return rc;
-  const double* d_x = arena_up(ctx, x, (size_t)k * d);
-  const double* d_c = arena_up(ctx, ctrs, (size_t)m * d);
-  const double* d_a = arena_up(ctx, ams, (size_t)m * d * d);
-  int32_t* d_cnt = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  uint64_t* d_mask = mask ? (uint64_t*)arena_get(ctx, nwords * m * 8) : nullptr;
-  double* d_q = quad ? (double*)arena_get(ctx, (size_t)k * m * 8) : nullptr;
-  if (!d_x || !d_c || !d_a || !d_cnt || (mask && !d_mask) || (quad && !d_q)) return DH_ERR_NOMEM;
+  if (!arena_fill(ctx, b.x, x, (size_t)k * d) || !arena_fill(ctx, b.ctrs, ctrs, (size_t)m * d) ||
+      !arena_fill(ctx, b.ams, ams, (size_t)m * d * d))
+    return DH_ERR_NOMEM;
   const dim3 grid((k + 63) / 64), block(64);
   bool hit = false;
   if (d > kMaxRegDim) {
     hit = true;
-    rc = wide_contains_launch(ctx, d_x, k, d, d_c, d_a, m, mode, d_cnt, d_mask, d_q);
+    rc = wide_contains_launch(ctx, b.x, k, d, b.ctrs, b.ams, m, mode, b.count, b.mask, b.quad);
     if (rc) return rc;
   }
 #define X(NN)                                                                                   \
   if (!hit && d <= NN) {                                                                        \
     hit = true;                                                                                 \
-    hipLaunchKernelGGL(contains_kernel<NN>, grid, block, 0, ctx->stream, d_x, k, d, d_c, d_a, m, \
-                       mode, d_cnt, d_mask, d_q);                                               \
+    hipLaunchKernelGGL(contains_kernel<NN>, grid, block, 0, ctx->stream, b.x, k, d, b.ctrs, b.ams, m, mode, b.count, \
+                       b.mask, b.quad);                                                                          \
   }
   DH_DIM_LIST(X)
 #undef X
   if (!hip_ok(ctx, hipGetLastError(), "contains launch")) return DH_ERR_HIP;
-  if (!down(ctx, count, d_cnt, (size_t)k) || !down(ctx, mask, d_mask, nwords * m) ||
-      !down(ctx, quad, d_q, (size_t)k * m))
+  if (!down(ctx, count, b.count, (size_t)k) || !down(ctx, mask, b.mask, nwords * m) ||
+      !down(ctx, quad, b.quad, (size_t)k * m))
     return DH_ERR_HIP;
   return dh_sync(ctx);
 }

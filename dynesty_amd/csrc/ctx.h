@@ -156,35 +156,24 @@ inline int env_int(const char* name, int def) {
   return e ? atoi(e) : def;
 }
 
-// bump allocator over the context arena (256-byte aligned); reset per call
+// bump allocator over the context arena (256-byte aligned); reset per call.  The entry points go through arena_carve.
 void arena_reset(dh_ctx* ctx);
 void* arena_get(dh_ctx* ctx, size_t bytes);  // nullptr + error set on failure
 int arena_reserve(dh_ctx* ctx, size_t bytes);
 
-template <typename T>
-inline T* arena_up(dh_ctx* ctx, const T* host, size_t count) {
-  T* d = (T*)arena_get(ctx, count * sizeof(T));
-  if (!d) return nullptr;
-  if (host && count) {
-    if (!hip_ok(ctx, hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream),
-                "H2D"))
-      return nullptr;
-  }
-  return d;
-}
-
-// The arena as one layout (merge_plan.h: a function of a Carver): reset, the size pass, that total reserved and taken
-// in one piece, the pointer pass.  No caller adds up bytes, and what the pointer pass hands out is what was reserved.
+// The arena as one layout (carve.h: a function of a Carver; the layouts are merge_plan.h's and stage_plan.h's): reset,
+// the size pass, that total reserved and taken in one piece, the pointer pass.  No caller adds up bytes, and what the
+// pointer pass hands out is what was reserved.
 template <class Layout>
 inline int arena_carve(dh_ctx* ctx, Layout&& layout) {
   arena_reset(ctx);
-  dh_merge::Carver size;
+  dh_carve::Carver size;
   layout(size);
   const int rc = arena_reserve(ctx, size.off);
   if (rc) return rc;
   char* base = (char*)arena_get(ctx, size.off);
   if (!base) return DH_ERR_NOMEM;
-  dh_merge::Carver place{base};
+  dh_carve::Carver place{base};
   layout(place);
   return DH_OK;
 }

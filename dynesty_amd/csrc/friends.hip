@@ -21,8 +21,10 @@
 #include "ctx.h"
 #include "eig_wave.h"
 #include "rng_pcg64.h"
+#include "stage_plan.h"
 
 using namespace dh;
+using namespace dh_stage;
 
 namespace {
 
@@ -675,67 +677,51 @@ int dh_friends_update(dh_ctx* ctx, const double* pts, int n, int d, int kind, co
       !axes_inv || !logvol || !rmax || nboot < 0 || (nboot > 0 && !in_mask))
     return fail(ctx, DH_ERR_ARG, "friends_update: bad arguments (2 <= n, 1 <= d <= 64)");
   (void)hipSetDevice(ctx->device);
-  arena_reset(ctx);
   const size_t nd = (size_t)n * d, dd = (size_t)d * d;
   const int nw = (n + 63) / 64;
   const int reps = nboot > 0 ? nboot : 1;
-  const size_t need = nd * 8 * 3 + (size_t)n * nw * 8 + (size_t)n * 4 + dd * 8 * 6 + (size_t)reps * n * 9 + 65536;
-  int rc = arena_reserve(ctx, need);
+  FriendsUpdateBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_friends_update(c, b, (size_t)n, (size_t)d, (size_t)(nboot > 0 ? nboot : 0), am_prev != nullptr);
+  });
   if (rc) return rc;
   hipStream_t s = ctx->stream;
-  double* d_x = arena_up(ctx, pts, nd);
-  double* d_y = (double*)arena_get(ctx, nd * 8);
-  double* d_mv = (double*)arena_get(ctx, nd * 8);  // cluster means (n x d, rows of roots), then recentred points
-  double* d_prev = am_prev ? arena_up(ctx, am_prev, dd) : nullptr;
-  unsigned long long* d_bits = (unsigned long long*)arena_get(ctx, (size_t)n * nw * 8);
-  int* d_label = (int*)arena_get(ctx, (size_t)n * 4);
-  int* d_nc = (int*)arena_get(ctx, 8);
-  double* d_m = (double*)arena_get(ctx, (size_t)d * 8);
-  double* d_cov = (double*)arena_get(ctx, dd * 8);
-  double* d_am = (double*)arena_get(ctx, dd * 8);
-  double* d_ax = (double*)arena_get(ctx, dd * 8);
-  double* d_ai = (double*)arena_get(ctx, dd * 8);
-  double* d_info = (double*)arena_get(ctx, 32);
-  int* d_st = (int*)arena_get(ctx, 8);
-  unsigned char* d_mask = nboot > 0 ? arena_up(ctx, in_mask, (size_t)nboot * n) : nullptr;
-  double* d_nn = (double*)arena_get(ctx, (size_t)reps * n * 8);
-  double* d_r = (double*)arena_get(ctx, 8);
-  if (!d_x || !d_y || !d_mv || !d_bits || !d_label || !d_nc || !d_m || !d_cov || !d_am || !d_ax || !d_ai ||
-      !d_info || !d_st || !d_nn || !d_r || (am_prev && !d_prev) || (nboot > 0 && !d_mask))
+  if (!arena_fill(ctx, b.x, pts, nd) || !arena_fill(ctx, b.prev, am_prev, dd) ||
+      (nboot > 0 && !arena_fill(ctx, b.mask, in_mask, (size_t)nboot * n)))
     return DH_ERR_NOMEM;
   const int gb = (int)((nd + kT - 1) / kT);
-  const double* d_src = d_x;  // points whose covariance is taken
+  const double* d_src = b.x;  // points whose covariance is taken
   int ncl = 1;
-  if (d_prev) {
+  if (b.prev) {
     // clusters: single linkage cut at Mahalanobis distance 1 in the previous metric
     size_t lds_adj = 0;
     if ((rc = fr_adjacency_lds(ctx, d, &lds_adj))) return rc;
-    hipLaunchKernelGGL(fr_adjacency, dim3(nw, (n + 3) / 4), dim3(kT), lds_adj, s, d_x, d_prev, n, d, d_bits, nw,
+    hipLaunchKernelGGL(fr_adjacency, dim3(nw, (n + 3) / 4), dim3(kT), lds_adj, s, b.x, b.prev, n, d, b.bits, nw,
                        nullptr, 0);
-    hipLaunchKernelGGL(fr_components, dim3(1), dim3(1024), 0, s, d_bits, n, nw, d_label, d_nc, nullptr, 0);
-    if (!down(ctx, &ncl, d_nc, 1) || !hip_ok(ctx, hipStreamSynchronize(s), "sync")) return DH_ERR_HIP;
+    hipLaunchKernelGGL(fr_components, dim3(1), dim3(1024), 0, s, b.bits, n, nw, b.label, b.nc, nullptr, 0);
+    if (!down(ctx, &ncl, b.nc, 1) || !hip_ok(ctx, hipStreamSynchronize(s), "sync")) return DH_ERR_HIP;
     if (ncl > 1) {
-      double* d_mean = d_y;  // the whitened copy is no longer needed
-      hipLaunchKernelGGL(fr_cluster_mean, dim3(n), dim3(64), 0, s, d_x, d_label, n, d, d_mean, nullptr, nullptr, 0);
-      hipLaunchKernelGGL(fr_recentre, dim3(gb), dim3(kT), 0, s, d_x, d_label, d_mean, n, d, d_mv, nullptr, nullptr, 0);
-      d_src = d_mv;
+      double* d_mean = b.y;  // the whitened copy is no longer needed
+      hipLaunchKernelGGL(fr_cluster_mean, dim3(n), dim3(64), 0, s, b.x, b.label, n, d, d_mean, nullptr, nullptr, 0);
+      hipLaunchKernelGGL(fr_recentre, dim3(gb), dim3(kT), 0, s, b.x, b.label, d_mean, n, d, b.mv, nullptr, nullptr, 0);
+      d_src = b.mv;
     }
   }
-  hipLaunchKernelGGL(fr_colmean, dim3(d), dim3(kT), 0, s, d_src, n, d, d_m, nullptr, 0);
-  hipLaunchKernelGGL(fr_cov, dim3(d * d), dim3(kT), 0, s, d_src, d_m, n, d, d_cov, nullptr, 0);
-  hipLaunchKernelGGL(fr_shape, dim3(1), dim3(64), fr_shape_lds(d), s, d_cov, d, d_am, d_ax, d_ai, d_info, d_st, nullptr,
-                     0);
+  hipLaunchKernelGGL(fr_colmean, dim3(d), dim3(kT), 0, s, d_src, n, d, b.mean, nullptr, 0);
+  hipLaunchKernelGGL(fr_cov, dim3(d * d), dim3(kT), 0, s, d_src, b.mean, n, d, b.cov, nullptr, 0);
+  hipLaunchKernelGGL(fr_shape, dim3(1), dim3(64), fr_shape_lds(d), s, b.cov, d, b.am, b.axes, b.axes_inv, b.info, b.status,
+                     nullptr, 0);
   // whitened points and the radius
-  hipLaunchKernelGGL(fr_matmul, dim3(gb), dim3(kT), dd * 8, s, d_x, d_ai, n, d, d_y, nullptr, 0);
-  hipLaunchKernelGGL(fr_nn, dim3((n + kT - 1) / kT, reps), dim3(kT), (size_t)64 * d * 8, s, d_y, n, d, kind, d_mask,
-                     d_nn, nullptr, 0);
-  hipLaunchKernelGGL(fr_max, dim3(1), dim3(kT), 0, s, d_nn, (long long)reps * n, d_r, nullptr, 0);
+  hipLaunchKernelGGL(fr_matmul, dim3(gb), dim3(kT), dd * 8, s, b.x, b.axes_inv, n, d, b.y, nullptr, 0);
+  hipLaunchKernelGGL(fr_nn, dim3((n + kT - 1) / kT, reps), dim3(kT), (size_t)64 * d * 8, s, b.y, n, d, kind, b.mask,
+                     b.nn, nullptr, 0);
+  hipLaunchKernelGGL(fr_max, dim3(1), dim3(kT), 0, s, b.nn, (long long)reps * n, b.r, nullptr, 0);
   if ((rc = launch_ok(ctx, "friends_update launch"))) return rc;
   int st = 0;
   double info[2] = {0, 0}, r = 0.0;
-  if (!down(ctx, cov, d_cov, dd) || !down(ctx, am, d_am, dd) || !down(ctx, axes, d_ax, dd) ||
-      !down(ctx, axes_inv, d_ai, dd) || !down(ctx, info, d_info, 2) || !down(ctx, &st, d_st, 1) ||
-      !down(ctx, &r, d_r, 1) || !hip_ok(ctx, hipStreamSynchronize(s), "sync"))
+  if (!down(ctx, cov, b.cov, dd) || !down(ctx, am, b.am, dd) || !down(ctx, axes, b.axes, dd) ||
+      !down(ctx, axes_inv, b.axes_inv, dd) || !down(ctx, info, b.info, 2) || !down(ctx, &st, b.status, 1) ||
+      !down(ctx, &r, b.r, 1) || !hip_ok(ctx, hipStreamSynchronize(s), "sync"))
     return DH_ERR_HIP;
   if (st != DH_OK) return fail(ctx, DH_ERR_VALUE, "friends_update: covariance is not finite");
   if (info[1] > 0.5 || !(r > 0.0) || !isfinite(r))
@@ -767,39 +753,27 @@ int dh_friends_update_batch(dh_ctx* ctx, int runs, const double* pts, int n, int
       !axes || !axes_inv || !logvol || !rmax || !status || nboot < 0 || (nboot > 0 && !in_mask))
     return fail(ctx, DH_ERR_ARG, "friends_update_batch: bad arguments (runs >= 1, 2 <= n, 1 <= d <= 64)");
   (void)hipSetDevice(ctx->device);
-  arena_reset(ctx);
   const size_t R = (size_t)runs, nd = (size_t)n * d, dd = (size_t)d * d;
-  const size_t wsb = friends_batch_ws_bytes(runs, n, d, nboot);
-  const size_t need = R * nd * 8 + (am_prev ? R * dd * 8 : 0) + (nboot > 0 ? R * nboot * n : 0) + R * 4 +
-                      R * (4 * dd * 8 + 16 + 8) + wsb + 65536;
-  int rc = arena_reserve(ctx, need);
+  FriendsBatchBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_friends_batch(c, b, R, (size_t)n, (size_t)d, (size_t)(nboot > 0 ? nboot : 0),
+                        friends_batch_ws_bytes(runs, n, d, nboot), am_prev != nullptr, active != nullptr);
+  });
   if (rc) return rc;
-  double* d_x = arena_up(ctx, pts, R * nd);
-  double* d_prev = am_prev ? arena_up(ctx, am_prev, R * dd) : nullptr;
-  unsigned char* d_mask = nboot > 0 ? arena_up(ctx, in_mask, R * nboot * n) : nullptr;
-  int* d_act = active ? (int*)arena_up(ctx, active, R) : nullptr;
-  double* d_cov = (double*)arena_get(ctx, R * dd * 8);
-  double* d_am = (double*)arena_get(ctx, R * dd * 8);
-  double* d_ax = (double*)arena_get(ctx, R * dd * 8);
-  double* d_ai = (double*)arena_get(ctx, R * dd * 8);
-  double* d_lv = (double*)arena_get(ctx, R * 8);
-  double* d_rm = (double*)arena_get(ctx, R * 8);
-  int* d_ncl = (int*)arena_get(ctx, R * 4);
-  int* d_st = (int*)arena_get(ctx, R * 4);
-  void* ws = arena_get(ctx, wsb);
-  if (!d_x || (am_prev && !d_prev) || (nboot > 0 && !d_mask) || (active && !d_act) || !d_cov || !d_am || !d_ax ||
-      !d_ai || !d_lv || !d_rm || !d_ncl || !d_st || !ws)
+  if (!arena_fill(ctx, b.x, pts, R * nd) || !arena_fill(ctx, b.prev, am_prev, R * dd) ||
+      (nboot > 0 && !arena_fill(ctx, b.mask, in_mask, R * nboot * n)) ||
+      !arena_fill(ctx, b.active, active, R))
     return DH_ERR_NOMEM;
-  rc = friends_update_launch(ctx, runs, d_x, n, d, kind, d_prev, nboot, d_mask, d_act, 0.0, ws, d_cov, d_am, d_ax, d_ai,
-                             d_lv, d_rm, d_ncl, d_st, nullptr);
+  rc = friends_update_launch(ctx, runs, b.x, n, d, kind, b.prev, nboot, b.mask, b.active, 0.0, b.ws, b.cov, b.am, b.axes,
+                             b.axes_inv, b.logvol, b.rmax, b.nclusters, b.status, nullptr);
   if (rc) return rc;
   // inactive runs' outputs stay as the caller left them: results come back through host copies
   std::vector<double> h_m(4 * R * dd), h_s(2 * R);
   std::vector<int32_t> h_i(2 * R);
-  if (!down(ctx, h_m.data(), d_cov, R * dd) || !down(ctx, h_m.data() + R * dd, d_am, R * dd) ||
-      !down(ctx, h_m.data() + 2 * R * dd, d_ax, R * dd) || !down(ctx, h_m.data() + 3 * R * dd, d_ai, R * dd) ||
-      !down(ctx, h_s.data(), d_lv, R) || !down(ctx, h_s.data() + R, d_rm, R) || !down(ctx, h_i.data(), d_ncl, R) ||
-      !down(ctx, h_i.data() + R, d_st, R))
+  if (!down(ctx, h_m.data(), b.cov, R * dd) || !down(ctx, h_m.data() + R * dd, b.am, R * dd) ||
+      !down(ctx, h_m.data() + 2 * R * dd, b.axes, R * dd) || !down(ctx, h_m.data() + 3 * R * dd, b.axes_inv, R * dd) ||
+      !down(ctx, h_s.data(), b.logvol, R) || !down(ctx, h_s.data() + R, b.rmax, R) ||
+      !down(ctx, h_i.data(), b.nclusters, R) || !down(ctx, h_i.data() + R, b.status, R))
     return DH_ERR_HIP;
   if ((rc = dh_sync(ctx))) return rc;
   for (size_t r = 0; r < R; ++r) {
@@ -825,27 +799,25 @@ int dh_friends_within(dh_ctx* ctx, const double* ctrs, int n, int d, int kind, c
   if (!ctrs || n < 1 || d < 1 || d > 64 || !axes_inv || !x || m < 1 || !counts)
     return fail(ctx, DH_ERR_ARG, "friends_within: bad arguments");
   (void)hipSetDevice(ctx->device);
-  arena_reset(ctx);
   const size_t nd = (size_t)n * d, md = (size_t)m * d, dd = (size_t)d * d;
   const int nw = (n + 63) / 64;
-  int rc = arena_reserve(ctx, (nd + md) * 16 + dd * 8 + (size_t)m * 4 + (bits ? (size_t)m * nw * 8 : 0) + 8192);
+  FriendsWithinBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_friends_within(c, b, (size_t)n, (size_t)d, (size_t)m, bits != nullptr);
+  });
   if (rc) return rc;
   hipStream_t s = ctx->stream;
-  double* d_c = arena_up(ctx, ctrs, nd);
-  double* d_x = arena_up(ctx, x, md);
-  double* d_ai = arena_up(ctx, axes_inv, dd);
-  double* d_ct = (double*)arena_get(ctx, nd * 8);
-  double* d_xt = (double*)arena_get(ctx, md * 8);
-  int* d_cnt = (int*)arena_get(ctx, (size_t)m * 4);
-  unsigned long long* d_b = bits ? (unsigned long long*)arena_get(ctx, (size_t)m * nw * 8) : nullptr;
-  if (!d_c || !d_x || !d_ai || !d_ct || !d_xt || !d_cnt || (bits && !d_b)) return DH_ERR_NOMEM;
-  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), dd * 8, s, d_c, d_ai, n, d, d_ct, nullptr, 0);
-  hipLaunchKernelGGL(fr_matmul, dim3((int)((md + kT - 1) / kT)), dim3(kT), dd * 8, s, d_x, d_ai, m, d, d_xt, nullptr, 0);
-  hipLaunchKernelGGL(fr_within, dim3((m + 63) / 64), dim3(64), (size_t)64 * d * 8, s, d_ct, d_xt, n, m, d, kind, d_cnt,
-                     d_b, nw);
+  if (!arena_fill(ctx, b.ctrs, ctrs, nd) || !arena_fill(ctx, b.x, x, md) || !arena_fill(ctx, b.axes_inv, axes_inv, dd))
+    return DH_ERR_NOMEM;
+  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), dd * 8, s, b.ctrs, b.axes_inv, n, d, b.ct,
+                     nullptr, 0);
+  hipLaunchKernelGGL(fr_matmul, dim3((int)((md + kT - 1) / kT)), dim3(kT), dd * 8, s, b.x, b.axes_inv, m, d, b.xt, nullptr,
+                     0);
+  hipLaunchKernelGGL(fr_within, dim3((m + 63) / 64), dim3(64), (size_t)64 * d * 8, s, b.ct, b.xt, n, m, d, kind, b.counts,
+                     b.bits, nw);
   if ((rc = launch_ok(ctx, "friends_within launch"))) return rc;
-  if (!down(ctx, counts, d_cnt, (size_t)m) ||
-      (bits && !down(ctx, (unsigned long long*)bits, d_b, (size_t)m * nw)))
+  if (!down(ctx, counts, b.counts, (size_t)m) ||
+      (bits && !down(ctx, (unsigned long long*)bits, b.bits, (size_t)m * nw)))
     return DH_ERR_HIP;
   return dh_sync(ctx);
 }
@@ -857,25 +829,20 @@ int dh_friends_draw(dh_ctx* ctx, const uint64_t* state6, int nsamp, const double
   if (!state6 || nsamp < 1 || !ctrs || n < 1 || d < 1 || d > 64 || !axes || !axes_inv || !xs || !qs || !state6_out)
     return fail(ctx, DH_ERR_ARG, "friends_draw: bad arguments");
   (void)hipSetDevice(ctx->device);
-  arena_reset(ctx);
   const size_t nd = (size_t)n * d, dd = (size_t)d * d;
-  int rc = arena_reserve(ctx, nd * 16 + dd * 16 + (size_t)nsamp * (d * 8 + 4) + 8192);
+  FriendsDrawBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) { carve_friends_draw(c, b, (size_t)nsamp, (size_t)n, (size_t)d); });
   if (rc) return rc;
   hipStream_t s = ctx->stream;
-  uint64_t* d_s = arena_up(ctx, state6, 6);
-  double* d_c = arena_up(ctx, ctrs, nd);
-  double* d_ax = arena_up(ctx, axes, dd);
-  double* d_ai = arena_up(ctx, axes_inv, dd);
-  double* d_ct = (double*)arena_get(ctx, nd * 8);
-  double* d_x = (double*)arena_get(ctx, (size_t)nsamp * d * 8);
-  int32_t* d_q = (int32_t*)arena_get(ctx, (size_t)nsamp * 4);
-  uint64_t* d_o = (uint64_t*)arena_get(ctx, 48);
-  if (!d_s || !d_c || !d_ax || !d_ai || !d_ct || !d_x || !d_q || !d_o) return DH_ERR_NOMEM;
-  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), dd * 8, s, d_c, d_ai, n, d, d_ct, nullptr, 0);
-  hipLaunchKernelGGL(fr_draw, dim3(1), dim3(64), (size_t)3 * d * 8, s, d_s, nsamp, n, d, kind, d_c, d_ct, d_ax, d_ai,
-                     return_q, d_x, d_q, d_o, ctx->zki(), ctx->zwi(), ctx->zfi());
+  if (!arena_fill(ctx, b.state, state6, 6) || !arena_fill(ctx, b.ctrs, ctrs, nd) || !arena_fill(ctx, b.axes, axes, dd) ||
+      !arena_fill(ctx, b.axes_inv, axes_inv, dd))
+    return DH_ERR_NOMEM;
+  hipLaunchKernelGGL(fr_matmul, dim3((int)((nd + kT - 1) / kT)), dim3(kT), dd * 8, s, b.ctrs, b.axes_inv, n, d, b.ct,
+                     nullptr, 0);
+  hipLaunchKernelGGL(fr_draw, dim3(1), dim3(64), (size_t)3 * d * 8, s, b.state, nsamp, n, d, kind, b.ctrs, b.ct, b.axes,
+                     b.axes_inv, return_q, b.x, b.q, b.state_out, ctx->zki(), ctx->zwi(), ctx->zfi());
   if ((rc = launch_ok(ctx, "friends_draw launch"))) return rc;
-  if (!down(ctx, xs, d_x, (size_t)nsamp * d) || !down(ctx, qs, d_q, (size_t)nsamp) || !down(ctx, state6_out, d_o, 6))
+  if (!down(ctx, xs, b.x, (size_t)nsamp * d) || !down(ctx, qs, b.q, (size_t)nsamp) || !down(ctx, state6_out, b.state_out, 6))
     return DH_ERR_HIP;
   return dh_sync(ctx);
 }

@@ -3,12 +3,14 @@
 //
 // The constants the sizes depend on, the launch arithmetic as functions of the shape alone, and one layout per scratch
 // user: THE list of that user's arrays -- element type, element count, wanted or not --, written once and walked twice
-// by a Carver, first without a base for the total, then with the block for the addresses (arena_carve of ctx.h,
+// by a Carver (carve.h), first without a base for the total, then with the block for the addresses (arena_carve of ctx.h,
 // device_carve of merge_dev.h).  Nothing here touches the device, so a host program holds it to its invariants
 // (tests/test_merge_plan_cpu.py).  Plain C++17: no HIP include.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+
+#include "carve.h"
 
 namespace dh_merge {
 
@@ -93,28 +95,9 @@ inline size_t boot_cap_regrown(size_t Mx) { return Mx + Mx / 4 + kChunk; }
 
 // ---- layouts --------------------------------------------------------------------------------------------------------
 
-// One array of a walk, for the host test.
-struct Slot {
-  const char* name;
-  size_t off, bytes;  // bytes == 0: not wanted -- no room, a null pointer
-  bool null;
-};
-
-// Hands out consecutive 256-byte aligned arrays of a block; without a base it only adds up.
-struct Carver {
-  char* base = nullptr;
-  size_t off = 0;
-  Slot* log = nullptr;  // where the host test has the walk written down
-  int nlog = 0;
-  template <class T>
-  void operator()(T*& p, const char* name, size_t count, bool wanted = true) {
-    p = nullptr;
-    const size_t bytes = wanted ? count * sizeof(T) : 0;
-    if (wanted && base) p = (T*)(base + off);
-    if (log) log[nlog++] = Slot{name, off, bytes, p == nullptr};
-    off += (bytes + 255) & ~(size_t)255;
-  }
-};
+// the walk over a layout (carve.h)
+using dh_carve::Carver;
+using dh_carve::Slot;
 
 typedef unsigned long long u64;
 

@@ -35,6 +35,7 @@
 #include "ns_sort.h"
 #include "ns_state.h"
 #include "rng_pcg64.h"
+#include "stage_plan.h"
 
 using namespace dh;
 
@@ -3127,8 +3128,10 @@ int dh_ns_consume(dh_ctx* ctx, int runs, int nlive, int queue_size, double dlogz
   a.cap = K;
   a.dlogz = dlogz;
   a.dead_rel = 1;
-  arena_reset(ctx);
-  int rc = arena_reserve(ctx, (size_t)R * (sizeof(NsRun) + (size_t)N * 24 + (size_t)K * 40 + 64) + 16384);
+  dh_stage::NsConsumeBuf b;
+  int rc = arena_carve(ctx, [&](dh_stage::Carver& c) {
+    dh_stage::carve_ns_consume(c, b, (size_t)R, (size_t)N, (size_t)K, sizeof(NsRun), want_pt);
+  });
   if (rc) return rc;
   std::vector<NsRun> st((size_t)R);
   for (int r = 0; r < R; ++r) {
@@ -3149,28 +3152,26 @@ int dh_ns_consume(dh_ctx* ctx, int runs, int nlive, int queue_size, double dlogz
       x.plogdvol = plateau[(size_t)r * 2 + 1];
     }
   }
-  a.st = arena_up(ctx, st.data(), (size_t)R);
-  a.live_logl = arena_up(ctx, live_logl, (size_t)R * N);
-  a.dead_logl = (double*)arena_get(ctx, (size_t)R * K * 8);
-  a.r_logl = arena_up(ctx, q_logl, (size_t)R * K);
-  a.r_a = (int*)arena_up(ctx, q_ncalls, (size_t)R * K);
-  a.trace_slot = (int*)arena_get(ctx, (size_t)R * K * 4);
-  a.trace_src = (int*)arena_get(ctx, (size_t)R * K * 4);
-  a.trace_n = (int*)arena_get(ctx, (size_t)R * 8);
-  a.ndone = (int*)arena_get(ctx, 64);
-  a.bstatus = (int*)arena_get(ctx, (size_t)R * 4);
-  if (want_pt) {
-    a.live_it = (int*)arena_up(ctx, (const int*)live_it, (size_t)R * N);
-    a.dead_id = (int*)arena_get(ctx, (size_t)R * K * 4);
-    a.dead_it = (int*)arena_get(ctx, (size_t)R * K * 4);
-    a.dead_nc = (int*)arena_get(ctx, (size_t)R * K * 4);
-    if (!a.live_it || !a.dead_id || !a.dead_it || !a.dead_nc) return DH_ERR_NOMEM;
-  }
-  if (!a.st || !a.live_logl || !a.dead_logl || !a.r_logl || !a.r_a ||
-      !a.trace_slot || !a.trace_src || !a.trace_n || !a.ndone || !a.bstatus)
+  a.st = (NsRun*)b.st;
+  a.live_logl = b.live_logl;
+  a.dead_logl = b.dead_logl;
+  a.r_logl = b.r_logl;
+  a.r_a = b.r_a;
+  a.trace_slot = b.trace_slot;
+  a.trace_src = b.trace_src;
+  a.trace_n = b.trace_n;
+  a.ndone = b.ndone;
+  a.bstatus = b.bstatus;
+  a.live_it = b.live_it;
+  a.dead_id = b.dead_id;
+  a.dead_it = b.dead_it;
+  a.dead_nc = b.dead_nc;
+  if (!arena_fill(ctx, a.st, st.data(), (size_t)R) || !arena_fill(ctx, b.live_logl, live_logl, (size_t)R * N) ||
+      !arena_fill(ctx, b.r_logl, q_logl, (size_t)R * K) || !arena_fill(ctx, b.r_a, q_ncalls, (size_t)R * K) ||
+      (want_pt && !arena_fill(ctx, b.live_it, live_it, (size_t)R * N)))
     return DH_ERR_NOMEM;
   hipStream_t s = ctx->stream;
-  if (!hip_ok(ctx, hipMemsetAsync(a.ndone, 0, 64, s), "memset") ||
+  if (!hip_ok(ctx, hipMemsetAsync(a.ndone, 0, dh_stage::kNsDoneInts * 4, s), "memset") ||
       !hip_ok(ctx, hipMemsetAsync(a.bstatus, 0, (size_t)R * 4, s), "memset") ||
       !hip_ok(ctx, hipMemsetAsync(a.trace_n, 0, (size_t)R * 8, s), "memset"))
     return DH_ERR_HIP;

@@ -23,9 +23,11 @@
 #include <vector>
 #include "eig_wave.h"
 #include "rebuild_plan.h"
+#include "stage_plan.h"
 
 using namespace dh;
 using namespace dh_plan;
+using namespace dh_stage;
 using dh_eig::jacobi_wave;
 using dh_eig::sort_eigs_wave;
 using dh_eig::wave_sync;
@@ -4099,30 +4101,18 @@ int dh_rebuild(dh_ctx* ctx, const double* pts, int n, int d, int mode, int max_e
   DH_CHECK_CTX(ctx);
   if (!pts || !nells || !ctrs || !covs || !ams || !axes || !axlens || !logvols)
     return fail(ctx, DH_ERR_ARG, "rebuild: null pointer");
-  arena_reset(ctx);
   const size_t dd = (size_t)d * d;
-  const size_t need = ((size_t)n * d + (size_t)max_ells * (3 * dd + 2 * d + 1)) * 8 + (size_t)n * 4 + 8192;
-  int rc = arena_reserve(ctx, need);
+  RebuildBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_rebuild(c, b, (size_t)n, (size_t)d, (size_t)max_ells, leaf_of_point != nullptr);
+  });
   if (rc) return rc;
-  const double* d_pts = arena_up(ctx, pts, (size_t)n * d);
-  int32_t* d_nells = (int32_t*)arena_get(ctx, 4);
-  int32_t* d_status = (int32_t*)arena_get(ctx, 4);
-  int32_t* d_nn = (int32_t*)arena_get(ctx, 4);
-  double* d_ctrs = (double*)arena_get(ctx, (size_t)max_ells * d * 8);
-  double* d_covs = (double*)arena_get(ctx, (size_t)max_ells * dd * 8);
-  double* d_ams = (double*)arena_get(ctx, (size_t)max_ells * dd * 8);
-  double* d_axes = (double*)arena_get(ctx, (size_t)max_ells * dd * 8);
-  double* d_axl = (double*)arena_get(ctx, (size_t)max_ells * d * 8);
-  double* d_lv = (double*)arena_get(ctx, (size_t)max_ells * 8);
-  int32_t* d_lop = leaf_of_point ? (int32_t*)arena_get(ctx, (size_t)n * 4) : nullptr;
-  if (!d_pts || !d_nells || !d_status || !d_nn || !d_ctrs || !d_covs || !d_ams || !d_axes || !d_axl ||
-      !d_lv || (leaf_of_point && !d_lop))
-    return DH_ERR_NOMEM;
-  rc = dh_rebuild_batch_dev(ctx, 1, d_pts, n, d, mode, max_ells, d_nells, d_status, d_ctrs, d_covs, d_ams,
-                            d_axes, d_axl, d_lv, d_lop, d_nn);
+  if (!arena_fill(ctx, b.pts, pts, (size_t)n * d)) return DH_ERR_NOMEM;
+  rc = dh_rebuild_batch_dev(ctx, 1, b.pts, n, d, mode, max_ells, b.nells, b.status, b.ctrs, b.covs, b.ams, b.axes,
+                            b.axlens, b.logvols, b.leaf_of_point, b.nnodes);
   if (rc) return rc;
   int32_t h_status = 0, h_nells = 0;
-  if (!down(ctx, &h_status, d_status, 1) || !down(ctx, &h_nells, d_nells, 1)) return DH_ERR_HIP;
+  if (!down(ctx, &h_status, b.status, 1) || !down(ctx, &h_nells, b.nells, 1)) return DH_ERR_HIP;
   if ((rc = dh_sync(ctx))) return rc;
   if (h_status != DH_OK) {
     const char* msg = h_status == DH_ERR_VALUE     ? "Cannot compute a bounding ellipsoid (single point or singular covariance)"
@@ -4134,9 +4124,9 @@ int dh_rebuild(dh_ctx* ctx, const double* pts, int n, int d, int mode, int max_e
   }
   *nells = h_nells;
   const size_t m = (size_t)h_nells;
-  if (!down(ctx, ctrs, d_ctrs, m * d) || !down(ctx, covs, d_covs, m * dd) || !down(ctx, ams, d_ams, m * dd) ||
-      !down(ctx, axes, d_axes, m * dd) || !down(ctx, axlens, d_axl, m * d) || !down(ctx, logvols, d_lv, m) ||
-      !down(ctx, leaf_of_point, d_lop, (size_t)n) || !down(ctx, nnodes, d_nn, 1))
+  if (!down(ctx, ctrs, b.ctrs, m * d) || !down(ctx, covs, b.covs, m * dd) || !down(ctx, ams, b.ams, m * dd) ||
+      !down(ctx, axes, b.axes, m * dd) || !down(ctx, axlens, b.axlens, m * d) || !down(ctx, logvols, b.logvols, m) ||
+      !down(ctx, leaf_of_point, b.leaf_of_point, (size_t)n) || !down(ctx, nnodes, b.nnodes, 1))
     return DH_ERR_HIP;
   return dh_sync(ctx);
 }
@@ -4150,17 +4140,11 @@ int dh_ell_from_cov(dh_ctx* ctx, int m, int d, const double* covs, double* axes,
   const int LD = d | 1;
   const size_t lds = ((size_t)3 * d * LD + d + 128) * 8 + (128 + (size_t)d + 8) * 4;
   if (lds > 160 * 1024) return fail(ctx, DH_ERR_ARG, "ell_from_cov: d=%d too large for LDS", d);
-  arena_reset(ctx);
   const size_t dd = (size_t)d * d;
-  int rc = arena_reserve(ctx, (size_t)m * (3 * dd + d + 2) * 8 + 8192);
+  EllFromCovBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) { carve_ell_from_cov(c, b, (size_t)m, (size_t)d); });
   if (rc) return rc;
-  const double* d_c = arena_up(ctx, covs, (size_t)m * dd);
-  double* d_ax = (double*)arena_get(ctx, (size_t)m * dd * 8);
-  double* d_am = (double*)arena_get(ctx, (size_t)m * dd * 8);
-  double* d_al = (double*)arena_get(ctx, (size_t)m * d * 8);
-  double* d_lv = (double*)arena_get(ctx, (size_t)m * 8);
-  int* d_st = (int*)arena_get(ctx, (size_t)m * 4);
-  if (!d_c || !d_ax || !d_am || !d_al || !d_lv || !d_st) return DH_ERR_NOMEM;
+  if (!arena_fill(ctx, b.covs, covs, (size_t)m * dd)) return DH_ERR_NOMEM;
   const double pre = d * log(2.0) + d * lgamma(1.5) - lgamma(d / 2.0 + 1.0);
   DH_DEV_MEMO(attr_lds);
   if (lds > attr_lds) {
@@ -4171,13 +4155,13 @@ int dh_ell_from_cov(dh_ctx* ctx, int m, int d, const double* covs, double* axes,
       return DH_ERR_HIP;
     attr_lds = lds;
   }
-  hipLaunchKernelGGL(ell_from_cov_kernel, dim3(m), dim3(64), lds, ctx->stream, m, d, d_c, pre, d_ax, d_al,
-                     d_am, d_lv, d_st);
+  hipLaunchKernelGGL(ell_from_cov_kernel, dim3(m), dim3(64), lds, ctx->stream, m, d, b.covs, pre, b.axes, b.axlens,
+                     b.ams, b.logvols, b.status);
   if (!hip_ok(ctx, hipGetLastError(), "ell_from_cov launch")) return DH_ERR_HIP;
   std::vector<int> st((size_t)m);
-  if (!down(ctx, axes, d_ax, (size_t)m * dd) || !down(ctx, ams, d_am, (size_t)m * dd) ||
-      !down(ctx, axlens, d_al, (size_t)m * d) || !down(ctx, logvols, d_lv, (size_t)m) ||
-      !down(ctx, st.data(), d_st, (size_t)m))
+  if (!down(ctx, axes, b.axes, (size_t)m * dd) || !down(ctx, ams, b.ams, (size_t)m * dd) ||
+      !down(ctx, axlens, b.axlens, (size_t)m * d) || !down(ctx, logvols, b.logvols, (size_t)m) ||
+      !down(ctx, st.data(), b.status, (size_t)m))
     return DH_ERR_HIP;
   if ((rc = dh_sync(ctx))) return rc;
   for (int i = 0; i < m; ++i)
@@ -4196,19 +4180,14 @@ int dh_improve_covar_mat(dh_ctx* ctx, int m, int d, const double* covs_in, int32
   const int LD = d | 1;
   const size_t lds = rebuild_lds_bytes(d);
   const size_t dd = (size_t)d * d;
-  arena_reset(ctx);
-  int rc = arena_reserve(ctx, (size_t)m * ((size_t)d * LD + 3 * dd + 1) * 8 + 8192);
+  ImproveCovBuf b;
+  const int rc = arena_carve(ctx, [&](Carver& c) { carve_improve_cov(c, b, (size_t)m, (size_t)d); });
   if (rc) return rc;
   std::vector<double> padded((size_t)m * d * LD, 0.0);
   for (int e = 0; e < m; ++e)
     for (int i = 0; i < d; ++i)
       for (int j = 0; j < d; ++j) padded[((size_t)e * d + i) * LD + j] = covs_in[(size_t)e * dd + i * d + j];
-  double* d_w = arena_up(ctx, padded.data(), padded.size());
-  double* d_c = (double*)arena_get(ctx, (size_t)m * dd * 8);
-  double* d_am = (double*)arena_get(ctx, (size_t)m * dd * 8);
-  double* d_ax = (double*)arena_get(ctx, (size_t)m * dd * 8);
-  int* d_g = (int*)arena_get(ctx, (size_t)m * 4);
-  if (!d_w || !d_c || !d_am || !d_ax || !d_g) return DH_ERR_NOMEM;
+  if (!arena_fill(ctx, b.padded, padded.data(), padded.size())) return DH_ERR_NOMEM;
   if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync(H2D of a temporary)")) return DH_ERR_HIP;
   DH_DEV_MEMO(attr_icm);
   if (lds > attr_icm) {
@@ -4217,10 +4196,11 @@ int dh_improve_covar_mat(dh_ctx* ctx, int m, int d, const double* covs_in, int32
       return DH_ERR_HIP;
     attr_icm = lds;
   }
-  hipLaunchKernelGGL(improve_cov_kernel, dim3(m), dim3(kThreads), lds, ctx->stream, m, d, d_w, d_g, d_c, d_am, d_ax);
+  hipLaunchKernelGGL(improve_cov_kernel, dim3(m), dim3(kThreads), lds, ctx->stream, m, d, b.padded, b.good, b.covs, b.ams,
+                     b.axes);
   if (!hip_ok(ctx, hipGetLastError(), "improve_covar_mat launch")) return DH_ERR_HIP;
-  if (!down(ctx, covs, d_c, (size_t)m * dd) || !down(ctx, ams, d_am, (size_t)m * dd) ||
-      !down(ctx, axes, d_ax, (size_t)m * dd) || !down(ctx, (int*)good, d_g, (size_t)m))
+  if (!down(ctx, covs, b.covs, (size_t)m * dd) || !down(ctx, ams, b.ams, (size_t)m * dd) ||
+      !down(ctx, axes, b.axes, (size_t)m * dd) || !down(ctx, (int*)good, b.good, (size_t)m))
     return DH_ERR_HIP;
   return dh_sync(ctx);
 }
@@ -4241,24 +4221,21 @@ int dh_scale_to_logvol(dh_ctx* ctx, int m, int d, double* covs, double* ams, dou
   if (m <= 0) return DH_OK;
   if (!covs || !ams || !axes || !axlens || !logvols || !targets || d < 1)
     return fail(ctx, DH_ERR_ARG, "scale_to_logvol: bad arguments");
-  arena_reset(ctx);
   const size_t dd = (size_t)d * d;
-  int rc = arena_reserve(ctx, (size_t)m * (3 * dd + d + 2) * 8 + 8192);
+  ScaleLogvolBuf b;
+  const int rc = arena_carve(ctx, [&](Carver& c) { carve_scale_logvol(c, b, (size_t)m, (size_t)d); });
   if (rc) return rc;
-  double* d_c = arena_up(ctx, (const double*)covs, (size_t)m * dd);
-  double* d_p = arena_up(ctx, (const double*)ams, (size_t)m * dd);
-  double* d_x = arena_up(ctx, (const double*)axes, (size_t)m * dd);
-  double* d_al = arena_up(ctx, (const double*)axlens, (size_t)m * d);
-  double* d_lv = arena_up(ctx, (const double*)logvols, (size_t)m);
-  const double* d_t = arena_up(ctx, targets, (size_t)m);
-  if (!d_c || !d_p || !d_x || !d_al || !d_lv || !d_t) return DH_ERR_NOMEM;
+  if (!arena_fill(ctx, b.covs, covs, (size_t)m * dd) || !arena_fill(ctx, b.ams, ams, (size_t)m * dd) ||
+      !arena_fill(ctx, b.axes, axes, (size_t)m * dd) || !arena_fill(ctx, b.axlens, axlens, (size_t)m * d) ||
+      !arena_fill(ctx, b.logvols, logvols, (size_t)m) || !arena_fill(ctx, b.targets, targets, (size_t)m))
+    return DH_ERR_NOMEM;
   hipLaunchKernelGGL(scale_logvol_kernel, dim3(m), dim3(d > 64 ? 1024 : 256), (size_t)2 * d * 8 + 64, ctx->stream, m, d,
-                     d_c, d_p, d_x, d_al, d_lv, d_t, 0.0, (const int*)nullptr, 1, (const int*)nullptr,
+                     b.covs, b.ams, b.axes, b.axlens, b.logvols, b.targets, 0.0, (const int*)nullptr, 1, (const int*)nullptr,
                      (const double*)nullptr, 0);
   if (!hip_ok(ctx, hipGetLastError(), "scale_to_logvol launch")) return DH_ERR_HIP;
-  if (!down(ctx, covs, d_c, (size_t)m * dd) || !down(ctx, ams, d_p, (size_t)m * dd) ||
-      !down(ctx, axes, d_x, (size_t)m * dd) || !down(ctx, axlens, d_al, (size_t)m * d) ||
-      !down(ctx, logvols, d_lv, (size_t)m))
+  if (!down(ctx, covs, b.covs, (size_t)m * dd) || !down(ctx, ams, b.ams, (size_t)m * dd) ||
+      !down(ctx, axes, b.axes, (size_t)m * dd) || !down(ctx, axlens, b.axlens, (size_t)m * d) ||
+      !down(ctx, logvols, b.logvols, (size_t)m))
     return DH_ERR_HIP;
   return dh_sync(ctx);
 }

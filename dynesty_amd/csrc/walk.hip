@@ -16,8 +16,10 @@
 
 #include "ctx.h"
 #include "rng_pcg64.h"
+#include "stage_plan.h"
 
 using namespace dh;
+using namespace dh_stage;
 #ifndef DH_RW_OCC
 #define DH_RW_OCC 2
 #endif
@@ -507,8 +509,40 @@ int dh::rwalk_launch_runs(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, 
   return hip_ok(ctx, hipGetLastError(), "rwalk launch") ? DH_OK : DH_ERR_HIP;
 }
 
-extern "C" {
+namespace {
+// host-pointer form of the batched random walk; key == nullptr: PCG64 streams from `rng`
+int rwalk_batch_host(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, const double* u0, const double* axes, int m,
+                     const int32_t* axes_idx, double scale, double loglstar, int walks, const int8_t* bc,
+                     const uint64_t* rng, double* u, double* v, double* logl, int32_t* naccept, int32_t* nreject,
+                     uint64_t* rng_out, const dh::PhiloxKey* key) {
+  DH_CHECK_CTX(ctx);
+  if (k <= 0) return DH_OK;
+  if (!u0 || !axes || (!rng && !key) || !u || !v || !logl || !naccept || !nreject)
+    return fail(ctx, DH_ERR_ARG, "rwalk%s: null pointer", key ? " (philox)" : "");
+  const size_t kd = (size_t)k * ndim;
+  RwalkBatchBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_rwalk_batch(c, b, (size_t)k, (size_t)ndim, (size_t)ncdim, (size_t)m, axes_idx != nullptr, bc != nullptr,
+                      key != nullptr);
+  });
+  if (rc) return rc;
+  if (!arena_fill(ctx, b.u0, u0, kd) || !arena_fill(ctx, b.axes, axes, (size_t)m * ncdim * ncdim) ||
+      !arena_fill(ctx, b.axes_idx, axes_idx, (size_t)k) || !arena_fill(ctx, b.bc, bc, (size_t)ndim) ||
+      (!key && !arena_fill(ctx, b.rng, rng, (size_t)k * 4)))
+    return DH_ERR_NOMEM;
+  rc = dh::rwalk_launch_runs(ctx, problem, k, ndim, ncdim, b.u0, b.axes, m, b.axes_idx, scale, loglstar, walks, b.bc,
+                             b.rng, b.u, b.v, b.logl, b.naccept, b.nreject, b.rng_out, nullptr, nullptr, nullptr, 1, 0,
+                             key);
+  if (rc) return rc;
+  if (!down(ctx, u, b.u, kd) || !down(ctx, v, b.v, kd) || !down(ctx, logl, b.logl, (size_t)k) ||
+      !down(ctx, naccept, b.naccept, (size_t)k) || !down(ctx, nreject, b.nreject, (size_t)k) ||
+      (!key && !down(ctx, rng_out, b.rng_out, (size_t)k * 4)))
+    return DH_ERR_HIP;
+  return dh_sync(ctx);
+}
+}  // namespace
 
+extern "C" {
 
 int dh_rwalk_propose(dh_ctx* ctx, int k, int ndim, int ncdim, const double* u0, const double* axes, int m,
                      const int32_t* axes_idx, double scale, const int8_t* bc, const uint64_t* rng,
@@ -519,26 +553,21 @@ int dh_rwalk_propose(dh_ctx* ctx, int k, int ndim, int ncdim, const double* u0, 
     return fail(ctx, DH_ERR_ARG, "rwalk_propose: null pointer");
   if (ndim > kMaxRegDim)
     return fail(ctx, DH_ERR_ARG, "rwalk_propose: ndim=%d > %d not built", ndim, kMaxRegDim);
-  arena_reset(ctx);
   const size_t kd = (size_t)k * ndim;
-  int rc = arena_reserve(ctx, 2 * kd * 8 + (size_t)m * ncdim * ncdim * 8 + (size_t)k * (4 + 4 + 64) +
-                                  (size_t)ndim + 8192);
+  RwalkProposeBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_rwalk_propose(c, b, (size_t)k, (size_t)ndim, (size_t)ncdim, (size_t)m, axes_idx != nullptr, bc != nullptr);
+  });
   if (rc) return rc;
-  const double* d_u0 = arena_up(ctx, u0, kd);
-  const double* d_axes = arena_up(ctx, axes, (size_t)m * ncdim * ncdim);
-  const int32_t* d_idx = axes_idx ? arena_up(ctx, axes_idx, (size_t)k) : nullptr;
-  const int8_t* d_bc = bc ? arena_up(ctx, bc, (size_t)ndim) : nullptr;
-  const uint64_t* d_rng = arena_up(ctx, rng, (size_t)k * 4);
-  double* d_u = (double*)arena_get(ctx, kd * 8);
-  int32_t* d_in = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  uint64_t* d_ro = (uint64_t*)arena_get(ctx, (size_t)k * 32);
-  if (!d_u0 || !d_axes || !d_rng || !d_u || !d_in || !d_ro || (axes_idx && !d_idx) || (bc && !d_bc))
+  if (!arena_fill(ctx, b.u0, u0, kd) || !arena_fill(ctx, b.axes, axes, (size_t)m * ncdim * ncdim) ||
+      !arena_fill(ctx, b.axes_idx, axes_idx, (size_t)k) || !arena_fill(ctx, b.bc, bc, (size_t)ndim) ||
+      !arena_fill(ctx, b.rng, rng, (size_t)k * 4))
     return DH_ERR_NOMEM;
-  rc = dh::rwalk_launch_runs(ctx, -1, k, ndim, ncdim, d_u0, d_axes, m, d_idx, scale, 0.0, 1, d_bc, d_rng, d_u,
-                             nullptr, nullptr, d_in, nullptr, d_ro, nullptr, nullptr, nullptr, 1, 0, nullptr);
+  rc = dh::rwalk_launch_runs(ctx, -1, k, ndim, ncdim, b.u0, b.axes, m, b.axes_idx, scale, 0.0, 1, b.bc, b.rng, b.u,
+                             nullptr, nullptr, b.inside, nullptr, b.rng_out, nullptr, nullptr, nullptr, 1, 0, nullptr);
   if (rc) return rc;
-  if (!down(ctx, u_prop, d_u, kd) || !down(ctx, inside, d_in, (size_t)k) ||
-      !down(ctx, rng_out, d_ro, (size_t)k * 4))
+  if (!down(ctx, u_prop, b.u, kd) || !down(ctx, inside, b.inside, (size_t)k) ||
+      !down(ctx, rng_out, b.rng_out, (size_t)k * 4))
     return DH_ERR_HIP;
   return dh_sync(ctx);
 }
@@ -547,71 +576,17 @@ int dh_rwalk_batch(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, const d
                    const double* axes, int m, const int32_t* axes_idx, double scale, double loglstar,
                    int walks, const int8_t* bc, const uint64_t* rng, double* u, double* v,
                    double* logl, int32_t* naccept, int32_t* nreject, uint64_t* rng_out) {
-  DH_CHECK_CTX(ctx);
-  if (k <= 0) return DH_OK;
-  if (!u0 || !axes || !rng || !u || !v || !logl || !naccept || !nreject)
-    return fail(ctx, DH_ERR_ARG, "rwalk: null pointer");
-  arena_reset(ctx);
-  const size_t kd = (size_t)k * ndim;
-  size_t need = 3 * kd * 8 + (size_t)m * ncdim * ncdim * 8 + (size_t)k * (4 + 8 + 4 + 4 + 64) +
-                (size_t)ndim + 16 * 256;
-  int rc = arena_reserve(ctx, need);
-  if (rc) return rc;
-  const double* d_u0 = arena_up(ctx, u0, kd);
-  const double* d_axes = arena_up(ctx, axes, (size_t)m * ncdim * ncdim);
-  const int32_t* d_idx = axes_idx ? arena_up(ctx, axes_idx, (size_t)k) : nullptr;
-  const int8_t* d_bc = bc ? arena_up(ctx, bc, (size_t)ndim) : nullptr;
-  const uint64_t* d_rng = arena_up(ctx, rng, (size_t)k * 4);
-  double* d_u = (double*)arena_get(ctx, kd * 8);
-  double* d_v = (double*)arena_get(ctx, kd * 8);
-  double* d_logl = (double*)arena_get(ctx, (size_t)k * 8);
-  int32_t* d_na = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  int32_t* d_nr = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  uint64_t* d_ro = (uint64_t*)arena_get(ctx, (size_t)k * 32);
-  if (!d_u0 || !d_axes || !d_rng || !d_u || !d_v || !d_logl || !d_na || !d_nr || !d_ro ||
-      (axes_idx && !d_idx) || (bc && !d_bc))
-    return DH_ERR_NOMEM;
-  rc = dh_rwalk_batch_dev(ctx, problem, k, ndim, ncdim, d_u0, d_axes, m, d_idx, scale, loglstar, walks,
-                          d_bc, d_rng, d_u, d_v, d_logl, d_na, d_nr, d_ro);
-  if (rc) return rc;
-  if (!down(ctx, u, d_u, kd) || !down(ctx, v, d_v, kd) || !down(ctx, logl, d_logl, (size_t)k) ||
-      !down(ctx, naccept, d_na, (size_t)k) || !down(ctx, nreject, d_nr, (size_t)k) ||
-      !down(ctx, rng_out, d_ro, (size_t)k * 4))
-    return DH_ERR_HIP;
-  return dh_sync(ctx);
+  return rwalk_batch_host(ctx, problem, k, ndim, ncdim, u0, axes, m, axes_idx, scale, loglstar, walks, bc, rng, u, v,
+                          logl, naccept, nreject, rng_out, nullptr);
 }
 
 int dh_rwalk_batch_philox(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, const double* u0,
                           const double* axes, int m, const int32_t* axes_idx, double scale, double loglstar,
                           int walks, const int8_t* bc, uint64_t seed, uint64_t sequence0, uint64_t offset,
                           double* u, double* v, double* logl, int32_t* naccept, int32_t* nreject) {
-  DH_CHECK_CTX(ctx);
-  if (k <= 0) return DH_OK;
-  if (!u0 || !axes || !u || !v || !logl || !naccept || !nreject)
-    return fail(ctx, DH_ERR_ARG, "rwalk (philox): null pointer");
-  arena_reset(ctx);
-  const size_t kd = (size_t)k * ndim;
-  size_t need = 3 * kd * 8 + (size_t)m * ncdim * ncdim * 8 + (size_t)k * (4 + 8 + 4 + 4) + (size_t)ndim + 16 * 256;
-  int rc = arena_reserve(ctx, need);
-  if (rc) return rc;
-  const double* d_u0 = arena_up(ctx, u0, kd);
-  const double* d_axes = arena_up(ctx, axes, (size_t)m * ncdim * ncdim);
-  const int32_t* d_idx = axes_idx ? arena_up(ctx, axes_idx, (size_t)k) : nullptr;
-  const int8_t* d_bc = bc ? arena_up(ctx, bc, (size_t)ndim) : nullptr;
-  double* d_u = (double*)arena_get(ctx, kd * 8);
-  double* d_v = (double*)arena_get(ctx, kd * 8);
-  double* d_logl = (double*)arena_get(ctx, (size_t)k * 8);
-  int32_t* d_na = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  int32_t* d_nr = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  if (!d_u0 || !d_axes || !d_u || !d_v || !d_logl || !d_na || !d_nr || (axes_idx && !d_idx) || (bc && !d_bc))
-    return DH_ERR_NOMEM;
-  rc = dh_rwalk_batch_philox_dev(ctx, problem, k, ndim, ncdim, d_u0, d_axes, m, d_idx, scale, loglstar, walks,
-                                 d_bc, seed, sequence0, offset, d_u, d_v, d_logl, d_na, d_nr);
-  if (rc) return rc;
-  if (!down(ctx, u, d_u, kd) || !down(ctx, v, d_v, kd) || !down(ctx, logl, d_logl, (size_t)k) ||
-      !down(ctx, naccept, d_na, (size_t)k) || !down(ctx, nreject, d_nr, (size_t)k))
-    return DH_ERR_HIP;
-  return dh_sync(ctx);
+  const dh::PhiloxKey key = {seed, sequence0, offset};
+  return rwalk_batch_host(ctx, problem, k, ndim, ncdim, u0, axes, m, axes_idx, scale, loglstar, walks, bc, nullptr, u,
+                          v, logl, naccept, nreject, nullptr, &key);
 }
 
 }  // extern "C"
@@ -646,34 +621,31 @@ int dh_problem_eval(dh_ctx* ctx, int problem, int k, const double* u, double* v,
   if (!get_problem(ctx, problem, &p)) return DH_ERR_ARG;
   if (k <= 0) return DH_OK;
   const int ndim = p.ndim;
-  arena_reset(ctx);
   const size_t kd = (size_t)k * ndim;
-  int rc = arena_reserve(ctx, 2 * kd * 8 + (size_t)k * 8 + 4096);
+  EvalBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) { carve_eval(c, b, (size_t)k, (size_t)ndim); });
   if (rc) return rc;
-  const double* d_u = arena_up(ctx, u, kd);
-  double* d_v = (double*)arena_get(ctx, kd * 8);
-  double* d_l = (double*)arena_get(ctx, (size_t)k * 8);
-  if (!d_u || !d_v || !d_l) return DH_ERR_NOMEM;
+  if (!arena_fill(ctx, b.u, u, kd)) return DH_ERR_NOMEM;
   const dim3 grid((k + 63) / 64), block(64);
   bool hit = false;
   const bool ext = problem_kind(p.like_id, p.prior_id) == KIND_EXT;
   if (ndim > kMaxRegDim) {
     hit = true;
-    rc = wide_eval_launch(ctx, p, k, d_u, d_v, d_l);
+    rc = wide_eval_launch(ctx, p, k, b.u, b.v, b.logl);
     if (rc) return rc;
   }
 #define X(NN)                                                                      \
   if (!hit && ndim <= NN) {                                                        \
     hit = true;                                                                    \
     if (ext)                                                                       \
-      hipLaunchKernelGGL((eval_kernel<NN, KIND_EXT>), grid, block, 0, ctx->stream, p, k, d_u, d_v, d_l); \
+      hipLaunchKernelGGL((eval_kernel<NN, KIND_EXT>), grid, block, 0, ctx->stream, p, k, b.u, b.v, b.logl); \
     else                                                                           \
-      hipLaunchKernelGGL((eval_kernel<NN, KIND_GENERIC>), grid, block, 0, ctx->stream, p, k, d_u, d_v, d_l); \
+      hipLaunchKernelGGL((eval_kernel<NN, KIND_GENERIC>), grid, block, 0, ctx->stream, p, k, b.u, b.v, b.logl); \
   }
   DH_DIM_LIST(X)
 #undef X
   if (!hip_ok(ctx, hipGetLastError(), "eval launch")) return DH_ERR_HIP;
-  if (!down(ctx, v, d_v, kd) || !down(ctx, logl, d_l, (size_t)k)) return DH_ERR_HIP;
+  if (!down(ctx, v, b.v, kd) || !down(ctx, logl, b.logl, (size_t)k)) return DH_ERR_HIP;
   return dh_sync(ctx);
 }
 
@@ -683,16 +655,14 @@ int dh_seed_children(dh_ctx* ctx, const uint32_t* entropy_words, int n_words, ui
   if (k <= 0) return DH_OK;
   if (!entropy_words || n_words < 1 || n_words > 64 || !states)
     return fail(ctx, DH_ERR_ARG, "seed_children: n_words=%d", n_words);
-  arena_reset(ctx);
-  int rc = arena_reserve(ctx, (size_t)k * 32 + 1024);
+  SeedChildrenBuf b;
+  const int rc = arena_carve(ctx, [&](Carver& c) { carve_seed_children(c, b, (size_t)k, (size_t)n_words); });
   if (rc) return rc;
-  const uint32_t* d_e = arena_up(ctx, entropy_words, (size_t)n_words);
-  uint64_t* d_s = (uint64_t*)arena_get(ctx, (size_t)k * 32);
-  if (!d_e || !d_s) return DH_ERR_NOMEM;
-  hipLaunchKernelGGL(seed_kernel, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, d_e, n_words,
-                     first_child, k, d_s);
+  if (!arena_fill(ctx, b.entropy, entropy_words, (size_t)n_words)) return DH_ERR_NOMEM;
+  hipLaunchKernelGGL(seed_kernel, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, b.entropy, n_words,
+                     first_child, k, b.states);
   if (!hip_ok(ctx, hipGetLastError(), "seed launch")) return DH_ERR_HIP;
-  if (!down(ctx, states, d_s, (size_t)k * 4)) return DH_ERR_HIP;
+  if (!down(ctx, states, b.states, (size_t)k * 4)) return DH_ERR_HIP;
   return dh_sync(ctx);
 }
 
@@ -700,19 +670,15 @@ int dh_rng_stream(dh_ctx* ctx, const uint64_t* state4, int n_normal, int n_unif,
                   double* unifs, uint64_t* state4_out) {
   DH_CHECK_CTX(ctx);
   if (!state4 || n_normal < 0 || n_unif < 0) return fail(ctx, DH_ERR_ARG, "rng_stream: bad args");
-  arena_reset(ctx);
-  int rc = arena_reserve(ctx, (size_t)(n_normal + n_unif) * 8 + 4096);
+  RngStreamBuf b;
+  const int rc = arena_carve(ctx, [&](Carver& c) { carve_rng_stream(c, b, (size_t)n_normal, (size_t)n_unif); });
   if (rc) return rc;
-  const uint64_t* d_s = arena_up(ctx, state4, 4);
-  double* d_n = (double*)arena_get(ctx, (size_t)(n_normal + 1) * 8);
-  double* d_u = (double*)arena_get(ctx, (size_t)(n_unif + 1) * 8);
-  uint64_t* d_o = (uint64_t*)arena_get(ctx, 32);
-  if (!d_s || !d_n || !d_u || !d_o) return DH_ERR_NOMEM;
-  hipLaunchKernelGGL(stream_kernel, dim3(1), dim3(64), 0, ctx->stream, d_s, n_normal, n_unif, d_n, d_u,
-                     d_o, ctx->zki(), ctx->zwi(), ctx->zfi());
+  if (!arena_fill(ctx, b.state, state4, 4)) return DH_ERR_NOMEM;
+  hipLaunchKernelGGL(stream_kernel, dim3(1), dim3(64), 0, ctx->stream, b.state, n_normal, n_unif, b.normals, b.unifs,
+                     b.state_out, ctx->zki(), ctx->zwi(), ctx->zfi());
   if (!hip_ok(ctx, hipGetLastError(), "stream launch")) return DH_ERR_HIP;
-  if (!down(ctx, normals, d_n, (size_t)n_normal) || !down(ctx, unifs, d_u, (size_t)n_unif) ||
-      !down(ctx, state4_out, d_o, 4))
+  if (!down(ctx, normals, b.normals, (size_t)n_normal) || !down(ctx, unifs, b.unifs, (size_t)n_unif) ||
+      !down(ctx, state4_out, b.state_out, 4))
     return DH_ERR_HIP;
   return dh_sync(ctx);
 }

@@ -6,8 +6,10 @@
 
 #include "ctx.h"
 #include "rng_gen.h"
+#include "stage_plan.h"
 
 using namespace dh;
+using namespace dh_stage;
 
 namespace {
 
@@ -1034,33 +1036,23 @@ int slice_batch_host(dh_ctx* ctx, int problem, int k, int ndim, int mode, const 
   if (k <= 0) return DH_OK;
   if (!u0 || !axes || (!rng && !key) || !u || !v || !logl || !ncalls || !nexpand || !ncontract || !flags)
     return fail(ctx, DH_ERR_ARG, "slice: null pointer");
-  arena_reset(ctx);
   const size_t kd = (size_t)k * ndim;
-  int rc = arena_reserve(ctx, 3 * kd * 8 + (size_t)m * ndim * ndim * 8 + (size_t)k * (8 + 20 + 64) + 8192);
+  SliceBatchBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_slice_batch(c, b, (size_t)k, (size_t)ndim, (size_t)m, axes_idx != nullptr, key != nullptr);
+  });
   if (rc) return rc;
-  const double* d_u0 = arena_up(ctx, u0, kd);
-  const double* d_axes = arena_up(ctx, axes, (size_t)m * ndim * ndim);
-  const int32_t* d_idx = axes_idx ? arena_up(ctx, axes_idx, (size_t)k) : nullptr;
-  const uint64_t* d_rng = key ? nullptr : arena_up(ctx, rng, (size_t)k * 4);
-  double* d_u = (double*)arena_get(ctx, kd * 8);
-  double* d_v = (double*)arena_get(ctx, kd * 8);
-  double* d_l = (double*)arena_get(ctx, (size_t)k * 8);
-  int32_t* d_nc = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  int32_t* d_ne = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  int32_t* d_nt = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  int32_t* d_fl = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  uint64_t* d_ro = (uint64_t*)arena_get(ctx, (size_t)k * 32);
-  if (!d_u0 || !d_axes || (!key && !d_rng) || !d_u || !d_v || !d_l || !d_nc || !d_ne || !d_nt || !d_fl || !d_ro ||
-      (axes_idx && !d_idx))
+  if (!arena_fill(ctx, b.u0, u0, kd) || !arena_fill(ctx, b.axes, axes, (size_t)m * ndim * ndim) ||
+      !arena_fill(ctx, b.axes_idx, axes_idx, (size_t)k) || (!key && !arena_fill(ctx, b.rng, rng, (size_t)k * 4)))
     return DH_ERR_NOMEM;
-  rc = dh::slice_launch_runs(ctx, problem, k, ndim, mode, d_u0, d_axes, m, d_idx, scale, loglstar, slices, doubling,
-                             d_rng, d_u, d_v, d_l, d_nc, d_ne, d_nt, d_fl, key ? nullptr : d_ro, nullptr, nullptr,
-                             nullptr, nullptr, 1, 0, key);
+  rc = dh::slice_launch_runs(ctx, problem, k, ndim, mode, b.u0, b.axes, m, b.axes_idx, scale, loglstar, slices, doubling,
+                             b.rng, b.u, b.v, b.logl, b.ncalls, b.nexpand, b.ncontract, b.flags,
+                             key ? nullptr : b.rng_out, nullptr, nullptr, nullptr, nullptr, 1, 0, key);
   if (rc) return rc;
-  if (!down(ctx, u, d_u, kd) || !down(ctx, v, d_v, kd) || !down(ctx, logl, d_l, (size_t)k) ||
-      !down(ctx, ncalls, d_nc, (size_t)k) || !down(ctx, nexpand, d_ne, (size_t)k) ||
-      !down(ctx, ncontract, d_nt, (size_t)k) || !down(ctx, flags, d_fl, (size_t)k) ||
-      (!key && !down(ctx, rng_out, d_ro, (size_t)k * 4)))
+  if (!down(ctx, u, b.u, kd) || !down(ctx, v, b.v, kd) || !down(ctx, logl, b.logl, (size_t)k) ||
+      !down(ctx, ncalls, b.ncalls, (size_t)k) || !down(ctx, nexpand, b.nexpand, (size_t)k) ||
+      !down(ctx, ncontract, b.ncontract, (size_t)k) || !down(ctx, flags, b.flags, (size_t)k) ||
+      (!key && !down(ctx, rng_out, b.rng_out, (size_t)k * 4)))
     return DH_ERR_HIP;
   if ((rc = dh_sync(ctx))) return rc;
   for (int i = 0; i < k; ++i)
@@ -1384,33 +1376,26 @@ int unif_batch_host(dh_ctx* ctx, int problem, int k, int ndim, int ncdim, int m,
   if ((!rng && !key) || !u || (problem != -1 && (!v || !logl || !ncalls)) || (m > 0 && (!ctrs || !axes)) ||
       (m > 1 && (!ams || !cumprob)))
     return fail(ctx, DH_ERR_ARG, "unif: null pointer");
-  arena_reset(ctx);
-  const size_t kd = (size_t)k * ndim, mm = (size_t)(m > 0 ? m : 1);
-  int rc = arena_reserve(ctx, 2 * kd * 8 + mm * ((size_t)2 * ncdim * ncdim + ncdim + 1) * 8 +
-                                  (size_t)k * (8 + 8 + 64) + (size_t)ndim + 8192);
+  const size_t kd = (size_t)k * ndim, mc = (size_t)(m > 0 ? m : 0);
+  UnifBatchBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_unif_batch(c, b, (size_t)k, (size_t)ndim, (size_t)ncdim, mc, bc != nullptr, key != nullptr);
+  });
   if (rc) return rc;
-  const double* d_c = m > 0 ? arena_up(ctx, ctrs, (size_t)m * ncdim) : nullptr;
-  const double* d_ax = m > 0 ? arena_up(ctx, axes, (size_t)m * ncdim * ncdim) : nullptr;
-  const double* d_am = m > 1 ? arena_up(ctx, ams, (size_t)m * ncdim * ncdim) : nullptr;
-  const double* d_cp = m > 1 ? arena_up(ctx, cumprob, (size_t)m) : nullptr;
-  const int8_t* d_bc = bc ? arena_up(ctx, bc, (size_t)ndim) : nullptr;
-  const uint64_t* d_rng = key ? nullptr : arena_up(ctx, rng, (size_t)k * 4);
-  double* d_u = (double*)arena_get(ctx, kd * 8);
-  double* d_v = (double*)arena_get(ctx, kd * 8);
-  double* d_l = (double*)arena_get(ctx, (size_t)k * 8);
-  int32_t* d_nc = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  int32_t* d_fl = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  uint64_t* d_ro = (uint64_t*)arena_get(ctx, (size_t)k * 32);
-  if ((!key && !d_rng) || !d_u || !d_v || !d_l || !d_nc || !d_fl || !d_ro) return DH_ERR_NOMEM;
-  rc = dh::unif_launch_runs(ctx, problem, k, ndim, ncdim, m, d_c, d_ax, d_am, d_cp, loglstar, d_bc, d_rng, max_tries,
-                            d_u, d_v, d_l, d_nc, d_fl, key ? nullptr : d_ro, nullptr, nullptr, 1, 0, key);
+  if (!arena_fill(ctx, b.ctrs, ctrs, mc * ncdim) || !arena_fill(ctx, b.axes, axes, mc * ncdim * ncdim) ||
+      (m > 1 && (!arena_fill(ctx, b.ams, ams, mc * ncdim * ncdim) || !arena_fill(ctx, b.cumprob, cumprob, mc))) ||
+      !arena_fill(ctx, b.bc, bc, (size_t)ndim) || (!key && !arena_fill(ctx, b.rng, rng, (size_t)k * 4)))
+    return DH_ERR_NOMEM;
+  rc = dh::unif_launch_runs(ctx, problem, k, ndim, ncdim, m, b.ctrs, b.axes, b.ams, b.cumprob, loglstar, b.bc, b.rng,
+                            max_tries, b.u, b.v, b.logl, b.ncalls, b.flags, key ? nullptr : b.rng_out, nullptr, nullptr,
+                            1, 0, key);
   if (rc) return rc;
   std::vector<int32_t> fl((size_t)k);
-  if (!down(ctx, u, d_u, kd) || !down(ctx, fl.data(), d_fl, (size_t)k) ||
-      (!key && !down(ctx, rng_out, d_ro, (size_t)k * 4)))
+  if (!down(ctx, u, b.u, kd) || !down(ctx, fl.data(), b.flags, (size_t)k) ||
+      (!key && !down(ctx, rng_out, b.rng_out, (size_t)k * 4)))
     return DH_ERR_HIP;
-  if (problem != -1 && (!down(ctx, v, d_v, kd) || !down(ctx, logl, d_l, (size_t)k) ||
-                        !down(ctx, ncalls, d_nc, (size_t)k)))
+  if (problem != -1 && (!down(ctx, v, b.v, kd) || !down(ctx, logl, b.logl, (size_t)k) ||
+                        !down(ctx, ncalls, b.ncalls, (size_t)k)))
     return DH_ERR_HIP;
   if ((rc = dh_sync(ctx))) return rc;
   for (int i = 0; i < k; ++i) {
@@ -1463,34 +1448,23 @@ int dh_unif_friends_batch(dh_ctx* ctx, int problem, int k, int ndim, int kind, c
     if (a.prob.ndim != ndim) return fail(ctx, DH_ERR_ARG, "problem ndim %d != %d", a.prob.ndim, ndim);
   }
   if (ndim > kMaxRegDim) return fail(ctx, DH_ERR_ARG, "unif_friends: ndim=%d > %d not built", ndim, kMaxRegDim);
-  arena_reset(ctx);
   const size_t kd = (size_t)k * ndim, nd = (size_t)n * ndim, dd = (size_t)ndim * ndim;
-  int rc = arena_reserve(ctx, 2 * kd * 8 + 2 * nd * 8 + 2 * dd * 8 + (size_t)k * (8 + 8 + 64 + 32) + (size_t)ndim + 8192);
+  UnifFriendsBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_unif_friends(c, b, (size_t)k, (size_t)ndim, (size_t)n, bc != nullptr, rng32 != nullptr, rng32_out != nullptr);
+  });
   if (rc) return rc;
-  const double* d_c = arena_up(ctx, ctrs, nd);
-  const double* d_ax = arena_up(ctx, axes, dd);
-  const double* d_ai = arena_up(ctx, axes_inv, dd);
-  double* d_ct = (double*)arena_get(ctx, nd * 8);
-  const int8_t* d_bc = bc ? arena_up(ctx, bc, (size_t)ndim) : nullptr;
-  const uint64_t* d_rng = arena_up(ctx, rng, (size_t)k * 4);
-  double* d_u = (double*)arena_get(ctx, kd * 8);
-  double* d_v = (double*)arena_get(ctx, kd * 8);
-  double* d_l = (double*)arena_get(ctx, (size_t)k * 8);
-  int32_t* d_nc = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  int32_t* d_fl = (int32_t*)arena_get(ctx, (size_t)k * 4);
-  uint64_t* d_ro = (uint64_t*)arena_get(ctx, (size_t)k * 32);
-  const uint64_t* d_r32 = rng32 ? arena_up(ctx, rng32, (size_t)k * 2) : nullptr;
-  uint64_t* d_r32o = rng32_out ? (uint64_t*)arena_get(ctx, (size_t)k * 16) : nullptr;
-  if (!d_c || !d_ax || !d_ai || !d_ct || !d_rng || !d_u || !d_v || !d_l || !d_nc || !d_fl || !d_ro ||
-      (rng32 && !d_r32) || (rng32_out && !d_r32o))
+  if (!arena_fill(ctx, b.ctrs, ctrs, nd) || !arena_fill(ctx, b.axes, axes, dd) ||
+      !arena_fill(ctx, b.axes_inv, axes_inv, dd) || !arena_fill(ctx, b.bc, bc, (size_t)ndim) ||
+      !arena_fill(ctx, b.rng, rng, (size_t)k * 4) || !arena_fill(ctx, b.rng32, rng32, (size_t)k * 2))
     return DH_ERR_NOMEM;
-  if ((rc = friends_whiten_launch(ctx, d_c, d_ai, n, ndim, d_ct))) return rc;
+  if ((rc = friends_whiten_launch(ctx, b.ctrs, b.axes_inv, n, ndim, b.ct))) return rc;
   const int N = pad_dim(ndim);
   if ((rc = ensure_axes_t(ctx, (size_t)2 * N * N * 8))) return rc;
   double* at = ctx->axes_t;
   double* ap = ctx->axes_t + (size_t)N * N;
-  hipLaunchKernelGGL(pad_mats_kernel, dim3((N * N + 255) / 256), dim3(256), 0, ctx->stream, d_ax, 1, ndim, N, 1, at);
-  hipLaunchKernelGGL(pad_mats_kernel, dim3((N * N + 255) / 256), dim3(256), 0, ctx->stream, d_ai, 1, ndim, N, 1, ap);
+  hipLaunchKernelGGL(pad_mats_kernel, dim3((N * N + 255) / 256), dim3(256), 0, ctx->stream, b.axes, 1, ndim, N, 1, at);
+  hipLaunchKernelGGL(pad_mats_kernel, dim3((N * N + 255) / 256), dim3(256), 0, ctx->stream, b.axes_inv, 1, ndim, N, 1, ap);
   a.run_loglstar = nullptr;
   a.run_mode = nullptr;
   a.wpr = 1;
@@ -1500,35 +1474,35 @@ int dh_unif_friends_batch(dh_ctx* ctx, int problem, int k, int ndim, int kind, c
   a.ncdim = ndim;
   a.m = 1;
   a.loglstar = loglstar;
-  a.ctrs = d_c;
+  a.ctrs = b.ctrs;
   a.axes_t = at;
   a.ams_p = ap;
   a.cumprob = nullptr;
   a.fr_kind = kind;
   a.fr_n = n;
-  a.fr_ctrs = d_c;
-  a.fr_ct = d_ct;
-  a.rng32_in = d_r32;
-  a.rng32_out = d_r32o;
-  a.bc = d_bc;
-  a.rng_in = d_rng;
+  a.fr_ctrs = b.ctrs;
+  a.fr_ct = b.ct;
+  a.rng32_in = b.rng32;
+  a.rng32_out = b.rng32_out;
+  a.bc = b.bc;
+  a.rng_in = b.rng;
   a.max_tries = max_tries > 0 ? max_tries : ((int64_t)1 << 32);
-  a.u = d_u;
-  a.v = d_v;
-  a.logl = d_l;
-  a.ncalls = d_nc;
-  a.flags = d_fl;
-  a.rng_out = d_ro;
+  a.u = b.u;
+  a.v = b.v;
+  a.logl = b.logl;
+  a.ncalls = b.ncalls;
+  a.flags = b.flags;
+  a.rng_out = b.rng_out;
   a.zki = ctx->zki();
   a.zwi = ctx->zwi();
   a.zfi = ctx->zfi();
   if ((rc = unif_dispatch(ctx, a, N))) return rc;
   std::vector<int32_t> fl((size_t)k);
-  if (!down(ctx, u, d_u, kd) || !down(ctx, fl.data(), d_fl, (size_t)k) || !down(ctx, rng_out, d_ro, (size_t)k * 4) ||
-      (rng32_out && !down(ctx, rng32_out, d_r32o, (size_t)k * 2)))
+  if (!down(ctx, u, b.u, kd) || !down(ctx, fl.data(), b.flags, (size_t)k) || !down(ctx, rng_out, b.rng_out, (size_t)k * 4) ||
+      (rng32_out && !down(ctx, rng32_out, b.rng32_out, (size_t)k * 2)))
     return DH_ERR_HIP;
-  if (problem != -1 && (!down(ctx, v, d_v, kd) || !down(ctx, logl, d_l, (size_t)k) ||
-                        !down(ctx, ncalls, d_nc, (size_t)k)))
+  if (problem != -1 && (!down(ctx, v, b.v, kd) || !down(ctx, logl, b.logl, (size_t)k) ||
+                        !down(ctx, ncalls, b.ncalls, (size_t)k)))
     return DH_ERR_HIP;
   if ((rc = dh_sync(ctx))) return rc;
   for (int i = 0; i < k; ++i)
@@ -1545,30 +1519,21 @@ int dh_bound_draw(dh_ctx* ctx, const uint64_t* state4, int nsamp, int d, int m, 
   if (!state4 || !ctrs || !axes || !xs || !idxs || !qs || !state4_out || m < 1 || d < 1 ||
       (m > 1 && (!ams || !cumprob)))
     return fail(ctx, DH_ERR_ARG, "bound_draw: bad arguments");
-  arena_reset(ctx);
   const size_t dd = (size_t)d * d;
-  int rc = arena_reserve(ctx, ((size_t)m * (2 * dd + d + 1) + (size_t)nsamp * d + 2 * d) * 8 +
-                                  (size_t)nsamp * 8 + 8192);
+  BoundDrawBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) { carve_bound_draw(c, b, (size_t)nsamp, (size_t)d, (size_t)m); });
   if (rc) return rc;
-  const uint64_t* d_s = arena_up(ctx, state4, 4);
-  const double* d_c = arena_up(ctx, ctrs, (size_t)m * d);
-  const double* d_ax = arena_up(ctx, axes, (size_t)m * dd);
-  const double* d_am = m > 1 ? arena_up(ctx, ams, (size_t)m * dd) : nullptr;
-  const double* d_cp = m > 1 ? arena_up(ctx, cumprob, (size_t)m) : nullptr;
-  double* d_x = (double*)arena_get(ctx, (size_t)nsamp * d * 8);
-  int32_t* d_i = (int32_t*)arena_get(ctx, (size_t)nsamp * 4);
-  int32_t* d_q = (int32_t*)arena_get(ctx, (size_t)nsamp * 4);
-  int32_t* d_st = (int32_t*)arena_get(ctx, 4);
-  uint64_t* d_o = (uint64_t*)arena_get(ctx, 32);
-  double* d_w = (double*)arena_get(ctx, (size_t)2 * d * 8);
-  if (!d_s || !d_c || !d_ax || !d_x || !d_i || !d_q || !d_st || !d_o || !d_w) return DH_ERR_NOMEM;
-  hipLaunchKernelGGL(bound_draw_kernel, dim3(1), dim3(64), 0, ctx->stream, d_s, nsamp, d, m, d_c, d_ax,
-                     d_am, d_cp, return_q, d_x, d_i, d_q, d_st, d_o, d_w, ctx->zki(), ctx->zwi(),
+  if (!arena_fill(ctx, b.state, state4, 4) || !arena_fill(ctx, b.ctrs, ctrs, (size_t)m * d) ||
+      !arena_fill(ctx, b.axes, axes, (size_t)m * dd) ||
+      (m > 1 && (!arena_fill(ctx, b.ams, ams, (size_t)m * dd) || !arena_fill(ctx, b.cumprob, cumprob, (size_t)m))))
+    return DH_ERR_NOMEM;
+  hipLaunchKernelGGL(bound_draw_kernel, dim3(1), dim3(64), 0, ctx->stream, b.state, nsamp, d, m, b.ctrs, b.axes, b.ams,
+                     b.cumprob, return_q, b.x, b.idx, b.q, b.status, b.state_out, b.work, ctx->zki(), ctx->zwi(),
                      ctx->zfi());
   if (!hip_ok(ctx, hipGetLastError(), "bound_draw launch")) return DH_ERR_HIP;
   int32_t st = 0;
-  if (!down(ctx, xs, d_x, (size_t)nsamp * d) || !down(ctx, idxs, d_i, (size_t)nsamp) ||
-      !down(ctx, qs, d_q, (size_t)nsamp) || !down(ctx, &st, d_st, 1) || !down(ctx, state4_out, d_o, 4))
+  if (!down(ctx, xs, b.x, (size_t)nsamp * d) || !down(ctx, idxs, b.idx, (size_t)nsamp) ||
+      !down(ctx, qs, b.q, (size_t)nsamp) || !down(ctx, &st, b.status, 1) || !down(ctx, state4_out, b.state_out, 4))
     return DH_ERR_HIP;
   if ((rc = dh_sync(ctx))) return rc;
   if (st == DH_ERR_QZERO) return fail(ctx, DH_ERR_QZERO, "Ellipsoid check failed q=0");
@@ -1675,11 +1640,18 @@ int dh_slice_feed(dh_ctx* ctx, int k, int ndim, int kind, const double* axes, in
   if (!state6 || kind < 0 || kind > 2 || ndim < 1 || nlook < 0 || (nlook > 0 && !look) ||
       (kind == 0 && (!axes || !dirs || m < 1)) || (kind == 1 && !perm))
     return fail(ctx, DH_ERR_ARG, "slice_feed: bad argument (kind=%d ndim=%d nlook=%d)", kind, ndim, nlook);
-  arena_reset(ctx);
   const size_t kd = (size_t)k * ndim;
-  int rc = arena_reserve(ctx, (kind == 0 ? (size_t)m * ndim * ndim * 8 + kd * 8 : 0) + kd * 4 +
-                                  (size_t)k * (48 + 4 + 4 + (size_t)nlook * 8) + 8192);
+  SliceFeedBuf b;
+  const int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_slice_feed(c, b, (size_t)k, (size_t)ndim, kind, (size_t)m, (size_t)nlook, axes_idx != nullptr,
+                     consumed != nullptr);
+  });
   if (rc) return rc;
+  if ((kind == 0 && (!arena_fill(ctx, b.axes, axes, (size_t)m * ndim * ndim) ||
+                     !arena_fill(ctx, b.axes_idx, axes_idx, (size_t)k))) ||
+      !arena_fill(ctx, b.st6, state6, (size_t)k * 6) ||
+      !arena_fill(ctx, b.consumed, consumed, (size_t)k))
+    return DH_ERR_NOMEM;
   SliceFeedArgs a;
   a.k = k;
   a.ndim = ndim;
@@ -1687,19 +1659,16 @@ int dh_slice_feed(dh_ctx* ctx, int k, int ndim, int kind, const double* axes, in
   a.m = m;
   a.nlook = nlook;
   a.scale = scale;
-  a.axes = kind == 0 ? arena_up(ctx, axes, (size_t)m * ndim * ndim) : nullptr;
-  a.axes_idx = (kind == 0 && axes_idx) ? arena_up(ctx, axes_idx, (size_t)k) : nullptr;
-  a.st6 = arena_up(ctx, state6, (size_t)k * 6);
-  a.consumed = consumed ? arena_up(ctx, consumed, (size_t)k) : nullptr;
-  a.dirs = kind == 0 ? (double*)arena_get(ctx, kd * 8) : nullptr;
-  a.perm = kind == 1 ? (int32_t*)arena_get(ctx, kd * 4) : nullptr;
-  a.look = nlook ? (double*)arena_get(ctx, (size_t)k * nlook * 8) : nullptr;
+  a.axes = b.axes;
+  a.axes_idx = b.axes_idx;
+  a.st6 = b.st6;
+  a.consumed = b.consumed;
+  a.dirs = b.dirs;
+  a.perm = b.perm;
+  a.look = b.look;
   a.zki = ctx->zki();
   a.zwi = ctx->zwi();
   a.zfi = ctx->zfi();
-  if (!a.st6 || (kind == 0 && (!a.axes || !a.dirs)) || (kind == 1 && !a.perm) || (nlook && !a.look) ||
-      (consumed && !a.consumed) || (kind == 0 && axes_idx && !a.axes_idx))
-    return DH_ERR_NOMEM;
   hipLaunchKernelGGL(slice_feed_kernel, dim3(k), dim3(64), (size_t)ndim * 12 + 16, ctx->stream, a);
   if (!hip_ok(ctx, hipGetLastError(), "slice feed launch")) return DH_ERR_HIP;
   if (!down(ctx, state6, (const uint64_t*)a.st6, (size_t)k * 6)) return DH_ERR_HIP;
