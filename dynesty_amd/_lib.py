@@ -68,6 +68,7 @@ SIGNATURES = {
     "dh_seed_children": (_i, [_vp, _vp, _i, _u32, _i, _vp]),
     "dh_rng_stream": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "dh_contains": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "dh_contains_runs": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "dh_rebuild": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                         _vp, _vp, _vp]),
     "dh_rebuild_batch_dev": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp,
@@ -900,6 +901,26 @@ class Context:
                                          _ptr(ctrs), _ptr(ams), m, mode,
                                          _ptr(count), _ptr(mask), _ptr(quad)))
         return count, mask, quad
+
+    def contains_runs(self, x, wpr, ctrs, ams, nells=None, strict=1, run_mode=None, my_mode=0, bstatus=None,
+                      flag=None, first=None):
+        """The resident loop's membership test of its start points as one launch (dh_contains_runs, a diagnostic
+        entry).  x (runs * wpr, d); ctrs (runs, max_ells, d); ams (runs, max_ells, d, d); nells / run_mode / bstatus
+        (runs,) or None.  flag (default zeros) and first (None: not asked for) go up as given; returns the arrays that
+        came back, (flag, first)."""
+        ctrs = _f64(ctrs)
+        runs, max_ells, d = ctrs.shape
+        x = _f64(x).reshape(runs * wpr, d)
+        ams = _f64(ams).reshape(runs, max_ells, d, d)
+
+        def i32(a):
+            return None if a is None else np.array(a, dtype=np.int32).reshape(runs)
+        nells, run_mode, bstatus, first = i32(nells), i32(run_mode), i32(bstatus), i32(first)
+        flag = np.zeros(runs, dtype=np.int32) if flag is None else i32(flag)
+        self._check(self.lib.dh_contains_runs(self.handle, _ptr(x), runs, int(wpr), d, _ptr(ctrs), _ptr(ams),
+                                              _ptr(nells), max_ells, int(strict), _ptr(run_mode), int(my_mode),
+                                              _ptr(bstatus), _ptr(flag), _ptr(first)))
+        return flag, first
 
     # -- rebuild ------------------------------------------------------------------
     def rebuild(self, points, multi=True, max_ells=None, want_labels=False):

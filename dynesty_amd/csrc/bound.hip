@@ -247,6 +247,7 @@ int contains_runs_launch(dh_ctx* ctx, const double* x, int k, int d, int wpr, co
   if (k <= 0) return DH_OK;
   if (d > kMaxRegDim) {
     const int P = d <= 256 ? kWideBlock : 4;  // (LDS: P d + ceil(d / 64) P 64 doubles <= 32 KB)
+    static_assert((4 * kWideMaxD + (kWideMaxD + 63) / 64 * 4 * 64) * 8 <= 32 * 1024, "the wide form's LDS at the wide limit");
     const int bpr = (wpr + P - 1) / P, nruns = (k + wpr - 1) / wpr;
     const size_t lds = ((size_t)P * d + (size_t)((d + 63) / 64) * P * 64) * 8;
     hipLaunchKernelGGL(contains_runs_wide_kernel, dim3(nruns * bpr), dim3(256), lds, ctx->stream, x, k, d, wpr, P, ctrs, ams,
@@ -316,6 +317,37 @@ int dh_contains(dh_ctx* ctx, const double* x, int k, int d, const double* ctrs, 
   if (!down(ctx, count, b.count, (size_t)k) || !down(ctx, mask, b.mask, nwords * m) ||
       !down(ctx, quad, b.quad, (size_t)k * m))
     return DH_ERR_HIP;
+  return dh_sync(ctx);
+}
+
+// see include/dynhip.h: the resident loop's membership test (contains_runs_launch, unchanged) as an operator of its own
+int dh_contains_runs(dh_ctx* ctx, const double* x, int runs, int wpr, int d, const double* ctrs, const double* ams,
+                     const int32_t* nells, int max_ells, int strict, const int32_t* run_mode, int my_mode,
+                     const int32_t* bstatus, int32_t* flag, int32_t* first) {
+  DH_CHECK_CTX(ctx);
+  if (!x || !ctrs || !ams || !flag || runs < 1 || wpr < 1 || d < 1 || d > kWideMaxD || max_ells < 1 ||
+      (long long)runs * wpr > 0x7fffffffLL)
+    return fail(ctx, DH_ERR_ARG, "contains_runs: bad arguments (runs=%d wpr=%d d=%d max_ells=%d)", runs, wpr, d, max_ells);
+  if (nells)
+    for (int r = 0; r < runs; ++r)
+      if (nells[r] < 0 || nells[r] > max_ells)
+        return fail(ctx, DH_ERR_ARG, "contains_runs: nells[%d]=%d outside 0..%d", r, nells[r], max_ells);
+  const size_t R = (size_t)runs, me = (size_t)max_ells, dd = (size_t)d;
+  dh_stage::ContainsRunsBuf b;
+  int rc = arena_carve(ctx, [&](dh_stage::Carver& c) {
+    dh_stage::carve_contains_runs(c, b, R, (size_t)wpr, dd, me, nells != nullptr, run_mode != nullptr, bstatus != nullptr,
+                                  first != nullptr);
+  });
+  if (rc) return rc;
+  if (!arena_fill(ctx, b.x, x, R * wpr * dd) || !arena_fill(ctx, b.ctrs, ctrs, R * me * dd) ||
+      !arena_fill(ctx, b.ams, ams, R * me * dd * dd) || !arena_fill(ctx, b.nells, nells, R) ||
+      !arena_fill(ctx, b.run_mode, run_mode, R) || !arena_fill(ctx, b.bstatus, bstatus, R) ||
+      !arena_fill(ctx, b.flag, (const int32_t*)flag, R) || !arena_fill(ctx, b.first, (const int32_t*)first, R))
+    return DH_ERR_NOMEM;
+  rc = contains_runs_launch(ctx, b.x, runs * wpr, d, wpr, b.ctrs, b.ams, b.nells, max_ells, strict, b.run_mode, my_mode,
+                            b.bstatus, b.flag, b.first);
+  if (rc) return rc;
+  if (!down(ctx, flag, b.flag, R) || !down(ctx, first, b.first, R)) return DH_ERR_HIP;
   return dh_sync(ctx);
 }
 

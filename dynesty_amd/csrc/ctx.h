@@ -18,6 +18,7 @@
 #define DH_DIM_LIST(X) X(1) X(2) X(3) X(4) X(5) X(6) X(8) X(10) X(12) X(16) X(20) X(25) X(32)
 #endif
 constexpr int kMaxRegDim = 32;
+constexpr int kWideMaxD = 512;  // the wide path's limit (wide.hip; the LDS of bound.hip's wide membership form)
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute: the memo of what was already
 // set is kept per device ordinal (a process may hold contexts on several GPUs)
 constexpr int kMaxDev = 64;

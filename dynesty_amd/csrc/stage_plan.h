@@ -415,6 +415,24 @@ inline void carve_contains(Carver& c, ContainsBuf& b, size_t k, size_t d, size_t
   c(b.quad, "quad", k * m, quad);
 }
 
+// dh_contains_runs: runs queues of wpr candidates, each against its own run's max_ells slots; flag and first go up and
+// come back
+struct ContainsRunsBuf {
+  double *x, *ctrs, *ams;
+  int32_t *nells, *run_mode, *bstatus, *flag, *first;
+};
+inline void carve_contains_runs(Carver& c, ContainsRunsBuf& b, size_t runs, size_t wpr, size_t d, size_t max_ells,
+                                bool nells, bool run_mode, bool bstatus, bool first) {
+  c(b.x, "x", runs * wpr * d);
+  c(b.ctrs, "ctrs", runs * max_ells * d);
+  c(b.ams, "ams", runs * max_ells * d * d);
+  c(b.nells, "nells", runs, nells);
+  c(b.run_mode, "run_mode", runs, run_mode);
+  c(b.bstatus, "bstatus", runs, bstatus);
+  c(b.flag, "flag", runs);
+  c(b.first, "first", runs, first);
+}
+
 // ---- ns.hip ---------------------------------------------------------------------------------------------------------
 
 // dh_ns_consume: R runs of N live points and a queue of K; run_bytes = sizeof(NsRun); the per-point arrays come together

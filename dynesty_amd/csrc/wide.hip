@@ -28,7 +28,6 @@ using namespace dh;
 
 namespace {
 
-constexpr int kWideMaxD = 512;
 constexpr int kRT = 1024;  // threads of the wide rebuild workgroup
 constexpr int kTPMax = 64;  // points per LDS tile (32 / 16 where 64 rows of D | 1 doubles do not fit LDS)
 typedef double wacc __attribute__((ext_vector_type(4)));

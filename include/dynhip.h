@@ -142,6 +142,22 @@ int dh_rng_stream(dh_ctx* ctx, const uint64_t* state4, int n_normal, int n_unif,
 int dh_contains(dh_ctx* ctx, const double* x, int k, int d, const double* ctrs,
                 const double* ams, int m, int mode, int32_t* count,
                 uint64_t* mask, double* quad);
+/* diagnostic: the resident loop's membership test of its start points
+ * (Sampler.propose_live, sampler.py:484-489) as one launch of its own.  runs
+ * queues of wpr candidates (x: runs*wpr x d); candidate w of run r is tested
+ * against the first nells[r] of that run's max_ells ellipsoids (ctrs
+ * runs*max_ells*d, ams runs*max_ells*d*d; nells NULL: the first one only).
+ *   strict 1: inside iff some (x-c)^T A (x-c) < 1;  strict 0: sqrt(..) <= 1
+ * A run is served when run_mode[r] == my_mode (run_mode NULL: always) and
+ * bstatus[r] == 0 (bstatus NULL: always).  flag and first (runs each; first may
+ * be NULL) are IN/OUT: a served run with a candidate outside gets flag[r] |= 1
+ * and first[r] = min(first[r], lowest queue index outside); everything else
+ * comes back as it was sent.  DH_ERR_ARG: a NULL required pointer, runs / wpr /
+ * d / max_ells < 1, d > 512, an nells[r] outside 0..max_ells. */
+int dh_contains_runs(dh_ctx* ctx, const double* x, int runs, int wpr, int d,
+                     const double* ctrs, const double* ams, const int32_t* nells,
+                     int max_ells, int strict, const int32_t* run_mode, int my_mode,
+                     const int32_t* bstatus, int32_t* flag, int32_t* first);
 
 /* ---- rebuild -------------------------------------------------------------
  * mode 0: MultiEllipsoid.update(points) without bootstrap (bounding.py:632-686)

@@ -226,12 +226,21 @@ def lay_ns_consume(R, N, K, run_bytes, pt):
     return sizes, R * (run_bytes + N * 24 + K * 40 + 64) + 16384
 
 
+def lay_contains_runs(runs, wpr, d, me, nells, run_mode, bstatus, first):
+    """dh_contains_runs has no hand-written predecessor: its reserve is the sum of its arrays, each rounded up."""
+    sizes = [("x", runs * wpr * d * 8), ("ctrs", runs * me * d * 8), ("ams", runs * me * d * d * 8),
+             ("nells", opt(runs * 4, nells)), ("run_mode", opt(runs * 4, run_mode)), ("bstatus", opt(runs * 4, bstatus)),
+             ("flag", runs * 4), ("first", opt(runs * 4, first))]
+    return sizes, sum(al(b) for _, b in sizes if b is not None)
+
+
 LAYOUTS = {"propose": lay_propose, "rwalk": lay_rwalk, "eval": lay_eval, "seed": lay_seed, "stream": lay_stream,
            "slice": lay_slice, "unif": lay_unif, "unif_friends": lay_unif_friends, "bound_draw": lay_bound_draw,
            "slice_feed": lay_slice_feed, "friends_update": lay_friends_update, "friends_batch": lay_friends_batch,
            "friends_within": lay_friends_within, "friends_draw": lay_friends_draw, "rebuild": lay_rebuild,
            "ell_from_cov": lay_ell_from_cov, "improve_cov": lay_improve_cov, "scale_logvol": lay_scale_logvol,
-           "boot_expand": lay_boot_expand, "contains": lay_contains, "ns_consume": lay_ns_consume}
+           "boot_expand": lay_boot_expand, "contains": lay_contains, "ns_consume": lay_ns_consume,
+           "contains_runs": lay_contains_runs}
 
 # Shapes whose layout needs more than the parent reserved, with the exact excess in bytes: the parent under-counted.
 # dh_bootstrap_expand reserved 32 + 16 bytes per run beside the workspace and the points, and took 32 (entropy) + 8
@@ -296,6 +305,9 @@ def test_rebuild_boot_bound_layouts(dump):
     reqs += [("boot_expand", runs, n, d, wsb)
              for runs, (n, d), wsb in itertools.product((1, 64, 4096), ((2, 1), (2000, 25), (2, 512)), (1, 4097, 123456789))]
     reqs += [("contains", k, d, m, mask, quad) for k, d, m, mask, quad in itertools.product(K_ALL, D_ALL, (1, 40), FLAGS, FLAGS)]
+    reqs += [("contains_runs", runs, wpr, d, me, nells, rm, bs, first)
+             for runs, wpr, d, me, nells, rm, bs, first in itertools.product((1, 7, 64), (1, 83, 512), D_ALL, (1, 4), FLAGS, FLAGS,
+                                                                             FLAGS, FLAGS)]
     assert walk(dump, reqs) == set(UNDERCOUNTED)  # every named exception is met, with its exact excess
 
 
