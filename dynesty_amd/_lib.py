@@ -80,6 +80,7 @@ SIGNATURES = {
     "dh_scale_to_logvol": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dh_enlarge_batch_dev": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                   _dbl]),
+    "dh_enlarge_runs": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp]),
     "dh_rwalk_propose": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _dbl, _vp, _vp,
                               _vp, _vp, _vp]),
     "dh_rwalk_batch": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _dbl, _dbl,
@@ -1035,6 +1036,20 @@ class Context:
         self._check(self.lib.dh_scale_to_logvol(
             self.handle, m, d, _ptr(covs), _ptr(ams), _ptr(axes), _ptr(axlens),
             _ptr(logvols), _ptr(t)))
+
+    def enlarge_runs(self, covs, ams, axes, axlens, logvols, nells, log_enlarge, active=None, run_shift=None):
+        """The resident loop's enlarge launch as one launch (dh_enlarge_runs, a diagnostic entry), in place on
+        covs / ams / axes (runs, max_ells, d, d), axlens (runs, max_ells, d) and logvols (runs, max_ells), which must
+        be C-contiguous float64.  nells (runs,); active (runs,) int and run_shift (runs,) float or None."""
+        runs, max_ells, d = axlens.shape
+        for a in (covs, ams, axes, axlens, logvols):
+            assert a.flags.c_contiguous and a.dtype == np.float64
+        nells = np.array(nells, dtype=np.int32).reshape(runs)
+        active = None if active is None else np.array(active, dtype=np.int32).reshape(runs)
+        run_shift = None if run_shift is None else _f64(run_shift).reshape(runs)
+        self._check(self.lib.dh_enlarge_runs(self.handle, runs, max_ells, _ptr(nells), d, _ptr(covs), _ptr(ams),
+                                             _ptr(axes), _ptr(axlens), _ptr(logvols), float(log_enlarge),
+                                             _ptr(active), _ptr(run_shift)))
 
     # -- proposals ----------------------------------------------------------------
     def rwalk_batch(self, prob, u0, axes, scale, loglstar, walks, rng_states,

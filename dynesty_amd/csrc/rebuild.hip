@@ -4215,12 +4215,42 @@ int dh_enlarge_batch_dev(dh_ctx* ctx, int runs, int max_ells, const int32_t* nel
                                    nullptr);
 }
 
+// see include/dynhip.h: the resident loop's enlarge launch (enlarge_launch_masked, unchanged) as an operator of its own
+int dh_enlarge_runs(dh_ctx* ctx, int runs, int max_ells, const int32_t* nells, int d, double* covs, double* ams,
+                    double* axes, double* axlens, double* logvols, double log_enlarge, const int32_t* active,
+                    const double* run_shift) {
+  DH_CHECK_CTX(ctx);
+  if (!nells || !covs || !ams || !axes || !axlens || !logvols || runs < 1 || max_ells < 1 || d < 1 || d > kWideMaxD ||
+      (long long)runs * max_ells > 0x7fffffffLL)
+    return fail(ctx, DH_ERR_ARG, "enlarge_runs: bad arguments (runs=%d max_ells=%d d=%d)", runs, max_ells, d);
+  for (int r = 0; r < runs; ++r)
+    if (nells[r] < 0 || nells[r] > max_ells)
+      return fail(ctx, DH_ERR_ARG, "enlarge_runs: nells[%d]=%d outside 0..%d", r, nells[r], max_ells);
+  const size_t R = (size_t)runs, m = R * (size_t)max_ells, dd = (size_t)d * d;
+  EnlargeRunsBuf b;
+  int rc = arena_carve(ctx, [&](Carver& c) {
+    carve_enlarge_runs(c, b, R, (size_t)max_ells, (size_t)d, active != nullptr, run_shift != nullptr);
+  });
+  if (rc) return rc;
+  if (!arena_fill(ctx, b.covs, covs, m * dd) || !arena_fill(ctx, b.ams, ams, m * dd) || !arena_fill(ctx, b.axes, axes, m * dd) ||
+      !arena_fill(ctx, b.axlens, axlens, m * d) || !arena_fill(ctx, b.logvols, logvols, m) || !arena_fill(ctx, b.nells, nells, R) ||
+      !arena_fill(ctx, b.active, active, R) || !arena_fill(ctx, b.run_shift, run_shift, R))
+    return DH_ERR_NOMEM;
+  rc = dh::enlarge_launch_masked(ctx, runs, max_ells, b.nells, d, b.covs, b.ams, b.axes, b.axlens, b.logvols, log_enlarge,
+                                 b.active, b.run_shift);
+  if (rc) return rc;
+  if (!down(ctx, covs, b.covs, m * dd) || !down(ctx, ams, b.ams, m * dd) || !down(ctx, axes, b.axes, m * dd) ||
+      !down(ctx, axlens, b.axlens, m * d) || !down(ctx, logvols, b.logvols, m))
+    return DH_ERR_HIP;
+  return dh_sync(ctx);
+}
+
 int dh_scale_to_logvol(dh_ctx* ctx, int m, int d, double* covs, double* ams, double* axes, double* axlens,
                        double* logvols, const double* targets) {
   DH_CHECK_CTX(ctx);
   if (m <= 0) return DH_OK;
-  if (!covs || !ams || !axes || !axlens || !logvols || !targets || d < 1)
-    return fail(ctx, DH_ERR_ARG, "scale_to_logvol: bad arguments");
+  if (!covs || !ams || !axes || !axlens || !logvols || !targets || d < 1 || d > kWideMaxD)
+    return fail(ctx, DH_ERR_ARG, "scale_to_logvol: bad arguments (m=%d d=%d)", m, d);
   const size_t dd = (size_t)d * d;
   ScaleLogvolBuf b;
   const int rc = arena_carve(ctx, [&](Carver& c) { carve_scale_logvol(c, b, (size_t)m, (size_t)d); });

@@ -378,6 +378,25 @@ inline void carve_scale_logvol(Carver& c, ScaleLogvolBuf& b, size_t m, size_t d)
   c(b.targets, "targets", m);
 }
 
+// dh_enlarge_runs: runs bounds of max_ells slots each, scaled in place; the run mask and the per-run shift are optional
+struct EnlargeRunsBuf {
+  double *covs, *ams, *axes, *axlens, *logvols;
+  int32_t *nells, *active;
+  double* run_shift;
+};
+inline void carve_enlarge_runs(Carver& c, EnlargeRunsBuf& b, size_t runs, size_t max_ells, size_t d, bool active,
+                               bool run_shift) {
+  const size_t m = runs * max_ells;
+  c(b.covs, "covs", m * d * d);
+  c(b.ams, "ams", m * d * d);
+  c(b.axes, "axes", m * d * d);
+  c(b.axlens, "axlens", m * d);
+  c(b.logvols, "logvols", m);
+  c(b.nells, "nells", runs);
+  c(b.active, "active", runs, active);
+  c(b.run_shift, "run_shift", runs, run_shift);
+}
+
 // ---- boot.hip -------------------------------------------------------------------------------------------------------
 
 // dh_bootstrap_expand: ws of bootstrap_ws_bytes (boot.hip)

@@ -227,6 +227,18 @@ int dh_improve_covar_mat(dh_ctx* ctx, int m, int d, const double* covs_in, int32
 int dh_enlarge_batch_dev(dh_ctx* ctx, int runs, int max_ells, const int32_t* nells,
                          int d, double* covs, double* ams, double* axes,
                          double* axlens, double* logvols, double log_enlarge);
+/* diagnostic: the resident loop's enlarge launch as one launch of its own, on
+ * host arrays laid out as above (updated in place).  Slot s of run r is scaled
+ * to logvols + run_shift[r] + log_enlarge when s < nells[r] and active[r] != 0
+ * (active NULL: every run; run_shift NULL: no per-run shift).  With run_shift
+ * given, a run whose run_shift[r] == 0 is left alone when log_enlarge == 0 (a
+ * bootstrap expansion factor of 1).  Everything else comes back as it was sent.
+ * DH_ERR_ARG: a NULL required pointer, runs / max_ells / d < 1, d > 512, an
+ * nells[r] outside 0..max_ells.  dh_scale_to_logvol refuses d > 512 too. */
+int dh_enlarge_runs(dh_ctx* ctx, int runs, int max_ells, const int32_t* nells, int d,
+                    double* covs, double* ams, double* axes, double* axlens,
+                    double* logvols, double log_enlarge, const int32_t* active,
+                    const double* run_shift);
 
 /* ---- proposals ----------------------------------------------------------
  * RWalkSampler.sample over a batch of k walkers = generic_random_walk +

@@ -6,7 +6,7 @@
 //   friends_batch R n d nboot ws_bytes prev active | friends_within n d m bits | friends_draw nsamp n d |
 //   rebuild n d max_ells leaf | ell_from_cov m d | improve_cov m d | scale_logvol m d | boot_expand runs n d ws_bytes |
 //   contains k d m mask quad | ns_consume R N K run_bytes pt |
-//   contains_runs runs wpr d max_ells nells run_mode bstatus first
+//   contains_runs runs wpr d max_ells nells run_mode bstatus first | enlarge_runs runs max_ells d active run_shift
 // stdout, one JSON line per request: {"total": bytes of the size pass, "end": bytes of the pointer pass,
 // "slots": [[name, offset, bytes, null], ..]}
 #include <stdint.h>
@@ -40,8 +40,9 @@ int main() {
   const char* kinds[] = {"propose",       "rwalk",          "eval",         "seed",    "stream",      "slice",       "unif",
                          "unif_friends",  "bound_draw",     "slice_feed",   "friends_update", "friends_batch",
                          "friends_within", "friends_draw",  "rebuild",      "ell_from_cov", "improve_cov", "scale_logvol",
-                         "boot_expand",   "contains",       "ns_consume",   "contains_runs"};
-  const int nargs[] = {6, 7, 2, 2, 2, 5, 6, 6, 3, 7, 4, 7, 4, 3, 4, 2, 2, 2, 4, 5, 5, 8};
+                         "boot_expand",   "contains",       "ns_consume",   "contains_runs",
+                         "enlarge_runs"};
+  const int nargs[] = {6, 7, 2, 2, 2, 5, 6, 6, 3, 7, 4, 7, 4, 3, 4, 2, 2, 2, 4, 5, 5, 8, 5};
   const int nkinds = (int)(sizeof nargs / sizeof nargs[0]);
   while (scanf("%31s", word) == 1) {
     int kind = -1;
@@ -73,6 +74,7 @@ int main() {
       case 18: { BootExpandBuf s; dump([&](Carver& k) { carve_boot_expand(k, s, a, b, c, d); }); break; }
       case 19: { ContainsBuf s; dump([&](Carver& k) { carve_contains(k, s, a, b, c, v[3] != 0, v[4] != 0); }); break; }
       case 21: { ContainsRunsBuf s; dump([&](Carver& k) { carve_contains_runs(k, s, a, b, c, d, v[4] != 0, v[5] != 0, v[6] != 0, v[7] != 0); }); break; }
+      case 22: { EnlargeRunsBuf s; dump([&](Carver& k) { carve_enlarge_runs(k, s, a, b, c, v[3] != 0, v[4] != 0); }); break; }
       default: { NsConsumeBuf s; dump([&](Carver& k) { carve_ns_consume(k, s, a, b, c, d, v[4] != 0); }); break; }
     }
   }

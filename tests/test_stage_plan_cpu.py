@@ -234,13 +234,21 @@ def lay_contains_runs(runs, wpr, d, me, nells, run_mode, bstatus, first):
     return sizes, sum(al(b) for _, b in sizes if b is not None)
 
 
+def lay_enlarge_runs(runs, me, d, active, run_shift):
+    """dh_enlarge_runs has no hand-written predecessor either: the sum of its arrays, each rounded up."""
+    m, dd = runs * me, d * d
+    sizes = [("covs", m * dd * 8), ("ams", m * dd * 8), ("axes", m * dd * 8), ("axlens", m * d * 8), ("logvols", m * 8),
+             ("nells", runs * 4), ("active", opt(runs * 4, active)), ("run_shift", opt(runs * 8, run_shift))]
+    return sizes, sum(al(b) for _, b in sizes if b is not None)
+
+
 LAYOUTS = {"propose": lay_propose, "rwalk": lay_rwalk, "eval": lay_eval, "seed": lay_seed, "stream": lay_stream,
            "slice": lay_slice, "unif": lay_unif, "unif_friends": lay_unif_friends, "bound_draw": lay_bound_draw,
            "slice_feed": lay_slice_feed, "friends_update": lay_friends_update, "friends_batch": lay_friends_batch,
            "friends_within": lay_friends_within, "friends_draw": lay_friends_draw, "rebuild": lay_rebuild,
            "ell_from_cov": lay_ell_from_cov, "improve_cov": lay_improve_cov, "scale_logvol": lay_scale_logvol,
            "boot_expand": lay_boot_expand, "contains": lay_contains, "ns_consume": lay_ns_consume,
-           "contains_runs": lay_contains_runs}
+           "contains_runs": lay_contains_runs, "enlarge_runs": lay_enlarge_runs}
 
 # Shapes whose layout needs more than the parent reserved, with the exact excess in bytes: the parent under-counted.
 # dh_bootstrap_expand reserved 32 + 16 bytes per run beside the workspace and the points, and took 32 (entropy) + 8
@@ -308,6 +316,8 @@ def test_rebuild_boot_bound_layouts(dump):
     reqs += [("contains_runs", runs, wpr, d, me, nells, rm, bs, first)
              for runs, wpr, d, me, nells, rm, bs, first in itertools.product((1, 7, 64), (1, 83, 512), D_ALL, (1, 4), FLAGS, FLAGS,
                                                                              FLAGS, FLAGS)]
+    reqs += [("enlarge_runs", runs, me, d, act, rs)
+             for runs, me, d, act, rs in itertools.product((1, 5, 64), (1, 4, 40), D_ALL, FLAGS, FLAGS)]
     assert walk(dump, reqs) == set(UNDERCOUNTED)  # every named exception is met, with its exact excess
 
 
